@@ -2,6 +2,7 @@
 """bench.py — training molecules/s of the egnn_equihnns hot path on synthetic QM9-like batches.
 
     python bench.py --gpus N --steps K --warmup W           (N=1 default)
+    python bench.py --full                                  (everything below the headline as well)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = forward + MSE + backward + gradient all-reduce (RCCL) + Adam on ONE batch per rank
@@ -9,6 +10,11 @@ A step = forward + MSE + backward + gradient all-reduce (RCCL) + Adam on ONE bat
 scripts/run_qm9_3d.sh hyper-parameters).  Batches are pre-collated and resident in HBM before
 the timed region; the per-batch index build (CSR sort, kNN) is INSIDE the step.  Prints ONE
 JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly K steps and prints the headline.  --full adds the
+side measurements (collective probe, strong-scaling config 4, other configurations, roofline,
+loader-fed pipeline, CPU baseline; each can be dropped with its --no-* option) and the per-block
+spread with the shader clock.  --dump-outputs DIR writes what the last timed step computed.
 """
 from __future__ import annotations
 
@@ -68,9 +74,10 @@ def parse():
     p.add_argument("--pool", type=int, default=8, help="distinct pre-collated batches per rank")
     p.add_argument("--c4-steps", type=int, default=10,
                    help="timed steps of the strong-scaling BASELINE config 4 leg (PCQM-like, global batch 1024); 0 = skip")
-    p.add_argument("--blocks", type=int, default=15,
-                   help="timed blocks of --steps steps each (every block bracketed by barrier + synchronize); the line "
-                        "reports the MEDIAN block with min / max / spread, so that 1-2 %% steps are resolvable")
+    p.add_argument("--blocks", type=int, default=None,
+                   help="blocks the --steps timed steps are split into (every block bracketed by barrier + synchronize); the "
+                        "line reports min / median / max / spread of the blocks, so that 1-2 %% steps are resolvable "
+                        "(default 1; 15 with --full, where the side measurements time blocks of --steps steps each)")
     p.add_argument("--no-collective-probe", action="store_true",
                    help="skip `collective_probe` (N=1 only: the multi-rank step driven through a one-rank RCCL group)")
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -94,7 +101,16 @@ def parse():
                    help="only the scatter-kernel replay of `roofline` (the command the rocprofv3 --pmc passes profile)")
     p.add_argument("--only-saturation", action="store_true",
                    help="run just the cache-exceeding scatter probe (used for the rocprofv3 --pmc passes)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run every side measurement (each can be dropped with its --no-* option) "
+                        "and report the shader clock after each timed block")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (its loss, the trained parameters and floating-point "
+                        "buffers) as DIR/<name>.npy, float32, at most 64 MB in all")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0 or (a.blocks is not None and a.blocks < 1):
+        p.error("--steps and --blocks must be >= 1, --warmup >= 0")
+    return a
 
 
 class ClockProbe:
@@ -646,6 +662,30 @@ class _StdoutToStderr:
         os.close(self.saved)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- that step's loss and the model it trained
+    (parameters in ``named_parameters`` order, floating-point buffers such as BatchNorm running statistics in ``named_buffers``
+    order), flattened to float32.  At most DUMP_MAX_BYTES in all: a larger parameter vector is written as a fixed sample
+    (seed 0, ascending positions), the same for every run of the same arguments."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = lambda ts: (torch.cat([t.detach().reshape(-1).float() for t in ts]).cpu().numpy() if ts
+                       else np.zeros(0, np.float32))
+    params = flat([p for _, p in model.named_parameters()])
+    bufs = flat([b for _, b in model.named_buffers() if b.is_floating_point()])
+    room = DUMP_MAX_BYTES // 4 - 1 - bufs.size
+    if params.size > room:
+        params = params[np.sort(np.random.default_rng(0).choice(params.size, room, replace=False))]
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float32))
+    np.save(os.path.join(out_dir, "parameters.npy"), params)
+    if bufs.size:
+        np.save(os.path.join(out_dir, "buffers.npy"), bufs)
+
+
 def launch_ranks(a) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks (one process per GPU) through
     torch.distributed.run, as the reference's Trainer(devices="auto", strategy="ddp...") does (main.py:271-283).
@@ -720,11 +760,14 @@ def main():
               flush=True)
         return
     use_graph = (not a.no_graph) and a.method not in _EAGER_METHODS
+    blocks = a.blocks or (15 if a.full else 1)
 
-    probe = ClockProbe(dev)
+    probe = ClockProbe(dev) if a.full else None
 
-    def timed_run(method, batch, flavour, steps, warmup, cfg_id, trainer_kw=None, blocks=None):
-        """K timed steps of one workload on this rank (barrier + synchronize on both sides, MAX over ranks)."""
+    def timed_run(method, batch, flavour, steps, warmup, cfg_id, trainer_kw=None, blocks=1):
+        """Timed steps of one workload on this rank: `blocks` blocks of `steps` steps, or one block per entry of a list
+        `steps` (barrier + synchronize on both sides of each block, MAX over ranks)."""
+        sizes = steps if isinstance(steps, list) else [steps] * max(1, blocks)
         ns = default_args(method=method, batch_size=batch)
         torch.manual_seed(0)
         model = MODELS[method](1, ns).to(dev)
@@ -768,14 +811,15 @@ def main():
         for i in range(warmup):
             step(base + i)
         els, clocks = [], []
-        for blk in range(max(1, blocks or a.blocks)):
+        done = base + warmup
+        for n_blk in sizes:
             torch.cuda.synchronize(dev)
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
-            for i in range(steps):
-                loss = step(base + warmup + blk * steps + i)
+            for i in range(n_blk):
+                loss = step(done + i)
             torch.cuda.synchronize(dev)
             if world > 1:
                 dist.barrier()
@@ -785,11 +829,18 @@ def main():
             if world > 1:
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)      # the slowest rank's clock, per block
             els.append(float(t.item()))
-            clocks.append(probe.mhz())        # after the block's clock was read: not part of any timed region
+            done += n_blk
+            if probe is not None:
+                clocks.append(probe.mhz())    # after the block's clock was read: not part of any timed region
         return {"el": sorted(els)[len(els) // 2], "els": els, "loss": float(loss), "host": host, "batches": batches,
                 "model": model, "trainer": trainer, "args": ns, "clocks": clocks}
 
-    run = timed_run(a.method, a.batch, a.flavour, a.steps, a.warmup, 2)
+    # the headline: exactly --steps timed steps, split into `blocks` blocks as evenly as possible
+    n_blk = min(blocks, a.steps)
+    head_sizes = [a.steps // n_blk + (1 if i < a.steps % n_blk else 0) for i in range(n_blk)]
+    run = timed_run(a.method, a.batch, a.flavour, head_sizes, a.warmup, 2)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, run["loss"], run["model"])
     tr0 = run["trainer"]
     index_info = None
     if isinstance(tr0, GraphedTrainStep):
@@ -803,8 +854,8 @@ def main():
                                "inside the timed region (device-wide synchronize at both ends); the step graph starts with "
                                "one batched copy of the finished index" if on else
                                "the per-batch index is built at the head of the step's hipGraph")}
-    el, loss, host_batches, batches, model = run["el"], run["loss"], run["host"], run["batches"], run["model"]
-    block_ms = [round(e / a.steps * 1e3, 4) for e in run["els"]]
+    el, loss, host_batches, batches, model = sum(run["els"]), run["loss"], run["host"], run["batches"], run["model"]
+    block_ms = [round(e / n * 1e3, 4) for e, n in zip(run["els"], head_sizes)]
     block_clocks = run["clocks"]
     run_args = run["args"]
     mode = getattr(run["trainer"], "collective_mode", "none")
@@ -816,7 +867,7 @@ def main():
     # path -- broadcast, flat-gradient all-reduce, 1 / world scale -- once with the all-reduce captured into the step's graph
     # and once in the split form (graph A -> eager all-reduce -> graph B), same workload and batches as the headline.
     coll = None
-    if world == 1 and use_graph and not a.no_collective_probe:
+    if a.full and world == 1 and use_graph and not a.no_collective_probe:
         import socket
         coll = {"what": "the headline step through a 1-rank 'nccl' (RCCL) group with force_collective: all-reduce inside the "
                         "step's one hipGraph (in_graph) and eagerly between two hipGraphs (two_graph)",
@@ -833,13 +884,13 @@ def main():
                 dist.all_reduce(t0)
                 torch.cuda.synchronize(dev)
             try:
-                ref = timed_run(a.method, a.batch, a.flavour, a.steps, a.warmup, 2, blocks=min(a.blocks, 7),
+                ref = timed_run(a.method, a.batch, a.flavour, a.steps, a.warmup, 2, blocks=min(blocks, 7),
                                 trainer_kw=dict(collective=False))
                 coll["single_rank_again_ms_per_step"] = round(ref["el"] / a.steps * 1e3, 4)
                 del ref
                 for label, kw in (("in_graph", dict(force_collective=True)),
                                   ("two_graph", dict(force_collective=True, graph_collective=False))):
-                    r = timed_run(a.method, a.batch, a.flavour, a.steps, a.warmup, 2, trainer_kw=kw, blocks=min(a.blocks, 7))
+                    r = timed_run(a.method, a.batch, a.flavour, a.steps, a.warmup, 2, trainer_kw=kw, blocks=min(blocks, 7))
                     coll[f"{label}_ms_per_step"] = round(r["el"] / a.steps * 1e3, 4)
                     coll[f"{label}_mode"] = r["trainer"].collective_mode
                     if r["trainer"].capture_error:
@@ -857,9 +908,9 @@ def main():
     # BASELINE config 4 as a STRONG-scaling point: PCQM4Mv2-like molecules, global batch 1024 split over the ranks
     # (SURVEY.md §8d), beside the weak-scaling headline above.  Reported inside the same JSON line.
     strong = None
-    if a.method == "egnn_equihnns" and a.flavour == "qm9" and a.c4_steps > 0 and 1024 % world == 0:
+    if a.full and a.method == "egnn_equihnns" and a.flavour == "qm9" and a.c4_steps > 0 and 1024 % world == 0:
         del run
-        r4 = timed_run("egnn_equihnns", 1024 // world, "pcqm", a.c4_steps, 2, 4, blocks=min(a.blocks, 5))
+        r4 = timed_run("egnn_equihnns", 1024 // world, "pcqm", a.c4_steps, 2, 4, blocks=min(blocks, 5))
         strong = {"workload": "PCQM4Mv2-like synthetic molecules, --method egnn_equihnns, GLOBAL batch 1024 "
                               f"({1024 // world}/rank), hidden 256", "scaling": "strong", "n_gpus": observed_world,
                   "steps": a.c4_steps, "value": round(1024 * a.c4_steps / r4["el"], 1), "unit": "molecules/s",
@@ -870,7 +921,7 @@ def main():
     # BASELINE.json's other configurations on this one GPU (scripts/run_qm9_3d.sh:10-31 hyper-parameters, hidden 256): a few
     # graph-replayed training steps each, same harness as the headline (no CPU leg, no roofline): driver-visible ms per step.
     others = None
-    if (world == 1 and use_graph and not a.no_other_configs and a.method == "egnn_equihnns" and a.flavour == "qm9"
+    if (a.full and world == 1 and use_graph and not a.no_other_configs and a.method == "egnn_equihnns" and a.flavour == "qm9"
             and a.batch == 256):
         others = {}
         for label, (m_, b_, fl_, cfg_, what_) in {
@@ -902,10 +953,8 @@ def main():
             "unit": "molecules/s",
             "n_gpus": observed_world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(el / a.steps * 1e3, 3),
-            "timed_blocks_ms_per_step": block_ms,        # every block = --steps steps between barrier + synchronize; value = median
+            "timed_blocks_ms_per_step": block_ms,        # the --steps steps in blocks between barrier + synchronize; value = all of them
             "timed_blocks": block_stats(block_ms),
-            "shader_clock_mhz": {"after_each_block": block_clocks, "min": min(block_clocks), "max": max(block_clocks),
-                                 "how": "eqh_clock_probe right after each timed block: d s_memtime / d s_memrealtime x 100 MHz"},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{a.flavour}-like synthetic molecules, --method {a.method}, "
@@ -921,6 +970,9 @@ def main():
                                       if world > 1 else "none (single rank)")},
             "final_loss": round(float(loss), 6),
         }
+        if block_clocks:
+            result["shader_clock_mhz"] = {"after_each_block": block_clocks, "min": min(block_clocks), "max": max(block_clocks),
+                                          "how": "eqh_clock_probe right after each timed block: d s_memtime / d s_memrealtime x 100 MHz"}
         if index_info is not None:
             result["index_build"] = index_info
         if others is not None:
@@ -929,7 +981,7 @@ def main():
             result["strong_scaling_c4"] = strong
         if coll is not None:
             result["collective_probe"] = coll
-        if not a.no_roofline and use_graph:
+        if a.full and not a.no_roofline and use_graph:
             per, floor = measure_in_graph(a.method, a.batch, a.flavour, dev, a.timeline_replays)
             names = SCATTER_KERNELS + (FRAME_KERNELS if a.method == "faformer_equihnns" else ())
             result["roofline"] = scatter_roofline(per, floor, names)
@@ -1025,10 +1077,10 @@ def main():
                 result["roofline"]["operator_boundary"] = measure_operator_boundary(batches[0], dev)
                 result["roofline"]["saturation"] = saturation_probe(dev)
                 result["roofline"]["saturation"]["fused_kernels"] = fused_saturation(dev)
-        if not a.no_pipeline and use_graph and world == 1:
+        if a.full and not a.no_pipeline and use_graph and world == 1:
             result["pipeline"] = measure_pipeline(a.method, a.batch, a.flavour, dev, rank)
             result["pipeline"]["fraction_of_resident"] = round(result["pipeline"]["value"] / result["value"], 4)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # equiformer_equihnns at hidden 256 materialises 9.7 GB of radial weights per pair type at batch 128 on the
             # CPU (as the reference does); FAFormer at 15 k atoms a dense [N, N] search: bounded samples for those
             cb = a.cpu_batch or {"equiformer_equihnns": 8, "faformer_equihnns": 64}.get(a.method, a.batch)

@@ -561,7 +561,31 @@ def scan_trajectory_seeds(name, seeds):
         print(f"seed {seed}: relu margins per step {case['relu_margin']}  losses {case['loss']}")
 
 
+INSTALL_METHODS = ("egnn_equihnns", "mhnnm", "mhnn", "mhnns", "egnn_equihnn", "egnn_equihnnm")
+
+
+def state_dict_layout(klass, method):
+    """{key: [shape, dtype]} of ``klass(1, args)``'s state_dict at the small size tests/test_install.py builds."""
+    from equihgnn_amd.registry import default_args
+    sd = klass(1, default_args(method=method, MLP_hidden=32, output_hidden=16)).state_dict()
+    return {k: [list(v.shape), str(v.dtype)] for k, v in sd.items()}
+
+
+def write_state_dict_layouts(path=os.path.join(HERE, "reference_state_dicts.json")):
+    """The state_dict layout of the reference's own class for every method of INSTALL_METHODS: what
+    tests/test_install.py holds the drop-in classes to where the reference checkout is absent."""
+    import json
+    ref = import_reference(("equihnn_egnn", "mhnn"))
+    out = {m: state_dict_layout(ref.get_model_class(m), m) for m in INSTALL_METHODS}
+    with open(path, "w") as f:        # one line per method
+        f.write("{\n" + ",\n".join(f"{json.dumps(m)}: {json.dumps(out[m], sort_keys=True)}" for m in sorted(out)) + "\n}\n")
+    return path
+
+
 if __name__ == "__main__":
+    if "--state-dict-layouts" in sys.argv:
+        print(write_state_dict_layouts())
+        sys.exit(0)
     if "--scan-f64" in sys.argv:
         torch.set_num_threads(1)
         torch.use_deterministic_algorithms(True)

@@ -53,7 +53,7 @@ def test_launcher_starts_two_ranks_gloo_on_one_device():
 def test_two_ranks_with_the_roofline_measurement():
     """The in-graph roofline measurement runs on rank 0 alone while the other ranks wait at the final barrier: its trainer
     must be rank-local (GraphedTrainStep(collective=False)) -- a collective there has no partner and the job hangs."""
-    args = [a for a in SMALL if a != "--no-roofline"] + ["--timeline-replays", "2"]
+    args = [a for a in SMALL if a != "--no-roofline"] + ["--full", "--timeline-replays", "2"]
     r = _bench(["--gpus", "2"] + args, {"EQH_BACKEND": "gloo"}, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -63,8 +63,32 @@ def test_two_ranks_with_the_roofline_measurement():
 @pytest.mark.gpu
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (RCCL)")
 def test_launcher_starts_two_ranks_rccl():
-    r = _bench(["--gpus", "2"] + SMALL + ["--c4-steps", "2"])
+    r = _bench(["--gpus", "2"] + SMALL + ["--full", "--c4-steps", "2"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and "nccl" in line["config"]["collective"]
     assert line["strong_scaling_c4"]["n_gpus"] == 2 and line["strong_scaling_c4"]["scaling"] == "strong"
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, reports the headline alone, and --dump-outputs writes the loss
+    and the trained parameters of the last timed step as float32 .npy files within the 64 MB budget."""
+    import numpy as np
+    r = _bench(["--gpus", "1", "--batch", "32", "--steps", "3", "--warmup", "1", "--pool", "2",
+                "--dump-outputs", str(tmp_path)], timeout=400)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(r.stdout.strip().splitlines()) == 1
+    line = json.loads(r.stdout)
+    assert line["steps"] == 3 and line["timed_blocks"]["blocks"] == 1 and len(line["timed_blocks_ms_per_step"]) == 1
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(line["value"] - 32 / line["ms_per_step"] * 1e3) <= 1e-2 * line["value"]
+    for side in ("roofline", "cpu_baseline", "pipeline", "collective_probe", "other_configs", "strong_scaling_c4"):
+        assert side not in line, side
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["loss.npy", "parameters.npy"], files
+    loss, params = np.load(tmp_path / "loss.npy"), np.load(tmp_path / "parameters.npy")
+    assert loss.dtype == params.dtype == np.float32 and loss.shape == (1,)
+    assert abs(float(loss[0]) - line["final_loss"]) <= 1e-6 * max(1.0, abs(line["final_loss"]))
+    assert np.isfinite(params).all() and params.size > 10 ** 6
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20

@@ -14,9 +14,9 @@ if [ "$1" = tests ]; then
   exit $rc
 elif [ "$1" = 1 ]; then
   # the headline line, then the same command under the kernel trace (stats CSV + the order of one replayed step)
-  timeout -k 10 500 python bench.py > $O/${R}_bench.json 2> $O/bench.err || exit 1
+  timeout -k 10 500 python bench.py --full > $O/${R}_bench.json 2> $O/bench.err || exit 1
   tail -c 600 $O/${R}_bench.json
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_main -- python3 bench.py --no-cpu-baseline --no-pipeline --no-other-configs --c4-steps 0 > $O/${R}_bench_with_roofline_probes_under_rocprof.json 2> $O/rocprof.err || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_main -- python3 bench.py --full --no-cpu-baseline --no-pipeline --no-other-configs --c4-steps 0 > $O/${R}_bench_with_roofline_probes_under_rocprof.json 2> $O/rocprof.err || exit 1
   cp "$(find /tmp/prof_main -name '*kernel_stats.csv' | head -1)" $O/${R}_kernel_stats_with_roofline_probes.csv
   # kernel order of one replayed step: a trace of the step alone (no roofline probes after it)
   # and per-kernel averages of the training step ALONE (95 replays + 2 set-up steps; the CSV above also holds the
@@ -33,18 +33,18 @@ elif [ "$1" = 1b ]; then
 elif [ "$1" = 2 ]; then
   for spec in "egnn_equihnns 1024 pcqm" "mhnns 256 qm9" "mhnn 256 qm9" "mhnnm 256 qm9" "egnn_equihnn 256 qm9" "egnn_equihnnm 256 qm9"; do
     set -- $spec
-    timeout -k 10 300 python bench.py --method $1 --batch $2 --flavour $3 --steps 20 --warmup 5 --no-pipeline --no-other-configs --c4-steps 0 --cpu-seconds 8 > $O/${R}_bench_$1_$2.json 2>> $O/bench.err || exit 1
+    timeout -k 10 300 python bench.py --full --method $1 --batch $2 --flavour $3 --steps 20 --warmup 5 --no-pipeline --no-other-configs --c4-steps 0 --cpu-seconds 8 > $O/${R}_bench_$1_$2.json 2>> $O/bench.err || exit 1
     echo "$1 $2: $(cut -c1-160 $O/${R}_bench_$1_$2.json | tail -1)"
   done
 elif [ "$1" = 3 ]; then
-  timeout -k 10 500 python bench.py --method equiformer_equihnns --batch 128 --steps 20 --warmup 5 --no-pipeline --no-other-configs --c4-steps 0 --cpu-batch 16 --cpu-seconds 8 > $O/${R}_bench_equiformer_equihnns_128.json 2>> $O/bench.err || exit 1
+  timeout -k 10 500 python bench.py --full --method equiformer_equihnns --batch 128 --steps 20 --warmup 5 --no-pipeline --no-other-configs --c4-steps 0 --cpu-batch 16 --cpu-seconds 8 > $O/${R}_bench_equiformer_equihnns_128.json 2>> $O/bench.err || exit 1
   cut -c1-200 $O/${R}_bench_equiformer_equihnns_128.json | tail -1
-  timeout -k 10 600 python bench.py --method faformer_equihnns --batch 512 --flavour pcqm --steps 10 --warmup 3 --no-pipeline --no-other-configs --c4-steps 0 --cpu-batch 16 --cpu-seconds 8 > $O/${R}_bench_faformer_equihnns_512.json 2>> $O/bench.err || exit 1
+  timeout -k 10 600 python bench.py --full --method faformer_equihnns --batch 512 --flavour pcqm --steps 10 --warmup 3 --no-pipeline --no-other-configs --c4-steps 0 --cpu-batch 16 --cpu-seconds 8 > $O/${R}_bench_faformer_equihnns_512.json 2>> $O/bench.err || exit 1
   cut -c1-200 $O/${R}_bench_faformer_equihnns_512.json | tail -1
   for spec in "equiformer_equihnns 128 qm9" "faformer_equihnns 512 pcqm"; do
     set -- $spec
     rm -rf /tmp/prof_$1
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$1 -- python3 bench.py --method $1 --batch $2 --flavour $3 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-pipeline --c4-steps 0 > $O/${R}_bench_$1_$2_under_rocprof.json 2>> $O/rocprof.err || exit 1
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$1 -- python3 bench.py --full --method $1 --batch $2 --flavour $3 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-pipeline --c4-steps 0 > $O/${R}_bench_$1_$2_under_rocprof.json 2>> $O/rocprof.err || exit 1
     cp "$(find /tmp/prof_$1 -name '*kernel_stats.csv' | head -1)" $O/${R}_kernel_stats_$1_$2.csv
     # kernel order of one replayed step (launch count, ATen share)
     rm -rf /tmp/order_$1
