@@ -476,3 +476,121 @@ def shard_permutation(n_items: int, world_size: int, seed: int, epoch: int = 0, 
     total = -(-n_items // world_size) * world_size
     reps = -(-total // max(n_items, 1))
     return np.concatenate([perm] * reps)[:total] if total > n_items else perm
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# 2-D molecular graphs (the baselines of baseline_2d.py: PyG ``Data(x, edge_index, edge_attr, y)``, ogb mol2graph)
+# ------------------------------------------------------------------------------------------------------------------
+@dataclass
+class GBatch:
+    """A PyG ``Batch`` of 2-D molecular graphs with the fields GNN_2D reads:
+        x          [N, 9]  int64   ogb atom features
+        edge_index [2, E]  int64   (source, target) per directed edge, node ids offset per molecule
+        edge_attr  [E, F]  int64   ogb bond features (F = 3: type, stereo, conjugated; qm9_g keeps the type only)
+        batch      [N]     int64   molecule id per atom (sorted)
+        y          [B]     float32 regression target"""
+    x: torch.Tensor
+    edge_index: torch.Tensor
+    edge_attr: torch.Tensor
+    batch: torch.Tensor
+    y: torch.Tensor
+    num_nodes: int = 0
+    num_edges: int = 0
+    num_graphs: int = 0
+
+    def to(self, device, non_blocking: bool = False) -> "GBatch":
+        kw = {}
+        for f in fields(self):
+            v = getattr(self, f.name)
+            kw[f.name] = v.to(device, non_blocking=non_blocking) if torch.is_tensor(v) else v
+        out = GBatch(**kw)
+        if hasattr(self, "num_real_graphs"):
+            out.num_real_graphs = self.num_real_graphs
+        return out
+
+
+@dataclass
+class GMol:
+    x: np.ndarray            # [n, 9] int64
+    edge_index: np.ndarray   # [2, e] int64, local atom ids
+    edge_attr: np.ndarray    # [e, F] int64
+    y: float
+
+
+def collate_graphs(mols: Sequence[GMol]) -> GBatch:
+    """PyG ``Batch.from_data_list``: edge_index offset by the atoms of the molecules before, ``batch`` = molecule id."""
+    n = np.array([m.x.shape[0] for m in mols], dtype=np.int64)
+    start = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
+    F = mols[0].edge_attr.shape[1] if mols else 1
+    x = np.concatenate([m.x for m in mols], 0) if mols else np.zeros((0, 9), np.int64)
+    ei = np.concatenate([m.edge_index + s for m, s in zip(mols, start)], 1) if mols else np.zeros((2, 0), np.int64)
+    ea = np.concatenate([m.edge_attr.reshape(-1, F) for m in mols], 0) if mols else np.zeros((0, F), np.int64)
+    batch = np.repeat(np.arange(len(mols), dtype=np.int64), n)
+    y = np.array([m.y for m in mols], dtype=np.float32)
+    t = torch.from_numpy
+    return GBatch(x=t(np.ascontiguousarray(x, np.int64)), edge_index=t(np.ascontiguousarray(ei, np.int64)),
+                  edge_attr=t(np.ascontiguousarray(ea, np.int64)), batch=t(batch), y=t(y), num_nodes=int(x.shape[0]),
+                  num_edges=int(ei.shape[1]), num_graphs=len(mols))
+
+
+class GraphStore:
+    """In-memory list of 2-D molecules (the reference's ``*_g`` datasets) with numpy collate."""
+
+    def __init__(self, mols: Sequence[GMol]):
+        self.mols = list(mols)
+
+    def __len__(self):
+        return len(self.mols)
+
+    def collate(self, indices) -> GBatch:
+        return collate_graphs([self.mols[int(i)] for i in indices])
+
+
+def graph_bucket_sizes(n_nodes: int, n_edges: int, quantum: int = 128):
+    """Static extents of a padded 2-D batch: at least one padded atom (the padding molecule's)."""
+    return -(-(n_nodes + 1) // quantum) * quantum, -(-n_edges // quantum) * quantum
+
+
+def pad_graph_batch(b: GBatch, n_nodes: int, n_edges: int) -> GBatch:
+    """Pad to fixed extents with ONE extra molecule (id B) that owns every padded atom; padded edges join padded atoms
+    only (a ring over them), so no real row ever reads a padded one.  Real molecules keep identical outputs, gradients
+    and -- with the real-row mask of layers.real_row_mask -- BatchNorm statistics."""
+    N, E, B = b.x.shape[0], b.edge_index.shape[1], b.y.shape[0]
+    if n_nodes <= N or n_edges < E:
+        raise ValueError("pad_graph_batch: target extents must exceed the batch (atoms strictly)")
+    dev = b.x.device
+    pn, pe = n_nodes - N, n_edges - E
+    k = torch.arange(pe, dtype=torch.int64, device=dev)
+    pad_ei = torch.stack((N + k % pn, N + (k + 1) % pn))
+    out = GBatch(x=torch.cat((b.x, torch.zeros((pn, b.x.shape[1]), dtype=b.x.dtype, device=dev))),
+                 edge_index=torch.cat((b.edge_index, pad_ei.to(b.edge_index.dtype)), 1),
+                 edge_attr=torch.cat((b.edge_attr, torch.zeros((pe, b.edge_attr.shape[1]), dtype=b.edge_attr.dtype,
+                                                               device=dev))),
+                 batch=torch.cat((b.batch, torch.full((pn,), B, dtype=b.batch.dtype, device=dev))),
+                 y=torch.cat((b.y, torch.zeros(1, dtype=b.y.dtype, device=dev))),
+                 num_nodes=n_nodes, num_edges=n_edges, num_graphs=B + 1)
+    out.num_real_graphs = getattr(b, "num_real_graphs", B)
+    return out
+
+
+def synth_graph(rng: np.random.Generator, flavour: str = "qm9") -> GMol:
+    """2-D graph of one synth_molecule: its bonds in both directions (ogb mol2graph order: (i, j) then (j, i)),
+    1 bond column (qm9_g: the bond type) or 3 (pcqm_g / molecule_g: type, stereo, conjugated)."""
+    m = synth_molecule(rng, flavour)
+    bond = m.e_order == 2
+    nb = int(bond.sum())
+    pairs = m.edge_index0[: 2 * nb].reshape(nb, 2)
+    ei = np.empty((2, 2 * nb), dtype=np.int64)
+    ei[0, 0::2], ei[1, 0::2] = pairs[:, 0], pairs[:, 1]
+    ei[0, 1::2], ei[1, 1::2] = pairs[:, 1], pairs[:, 0]
+    cols = [m.edge_attr[:nb, 0]]
+    if flavour != "qm9":
+        cols += [rng.integers(0, 6, size=nb), rng.integers(0, 2, size=nb)]
+    attr = np.repeat(np.stack(cols, 1).astype(np.int64), 2, axis=0)
+    return GMol(x=m.x, edge_index=ei, edge_attr=attr, y=m.y)
+
+
+def synth_graph_batch(batch_size: int, seed: int, flavour: str = "qm9") -> GBatch:
+    """Seeded synthetic 2-D batch (qm9: 1 bond column; pcqm: 3).  Pure host code, deterministic per seed."""
+    rng = np.random.default_rng(seed)
+    return collate_graphs([synth_graph(rng, flavour) for _ in range(batch_size)])

@@ -265,6 +265,12 @@ SIGNATURES = {
     "geo_eigh3": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "hg_rowgemm_bwd": (c_int32, [c_void_p] * 5 + [c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                                 c_void_p]),
+    "hg_edge_codes": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "hg_edge_msg_fwd": (c_int32, [c_int32, c_void_p, c_void_p, c_int32, c_int32] + [c_void_p] * 6
+                        + [c_int64, c_int32, c_void_p, c_void_p]),
+    "hg_edge_msg_bwd_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "hg_edge_msg_bwd": (c_int32, [c_int32, c_void_p, c_void_p, c_int32, c_int32] + [c_void_p] * 6
+                        + [c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

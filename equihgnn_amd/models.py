@@ -346,6 +346,9 @@ class FAFormerEquiHNNS(nn.Module):
         return readout(self.mlp_out, self.dropout(x), index, taps, head)
 
 
+from .baseline_2d import GNN_2D  # noqa: E402  (registers gin / gcn; constructed as GNN_2D(1, gnn_type=...))
+
 MODELS = {"egnn_equihnns": EGNNEquiHNNS, "mhnnm": MHNNM, "equiformer_equihnns": EquiformerEquiHNNS,
           "faformer_equihnns": FAFormerEquiHNNS,
-          "mhnn": MHNN, "mhnns": MHNNS, "egnn_equihnn": EGNNEquiHNN, "egnn_equihnnm": EGNNEquiHNNM}
+          "mhnn": MHNN, "mhnns": MHNNS, "egnn_equihnn": EGNNEquiHNN, "egnn_equihnnm": EGNNEquiHNNM,
+          "gin": GNN_2D, "gcn": GNN_2D}

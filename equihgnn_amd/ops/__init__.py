@@ -16,6 +16,7 @@ One module per subsystem; everything is re-exported here, so cal
   egnn     EGNN edge kernels, feature node, weight packing
   readout  pooled readout head + MSE in one launch
   se3      Equiformer: row GEMMs, radial trunk, attention pooling, RMS norm, edge geometry
+  gnn2d    2-D baselines: graph index (edge CSRs, bond codes), GIN / GCN edge messages, mean pool
   frames   FAFormer: frame-averaged SwiGLU pieces, edge hidden layer, row dots, gates, attention sums, eigh3
 
 Module-level switches (``ops.GEMM_TILE``, ``ops.TIMELINE``, ``ops.KNN_GRID_MIN_POINTS``, ...) are read by the
@@ -83,6 +84,8 @@ from .frames import (  # noqa: F401
     attn_gather_sum_supported, _EdgeLogitWeights, edge_logit_weights, _LnRowDot, ln_rowdot, ln_rowdot_supported,
     _DropoutAdd, dropout_add, dropout_add_supported,
 )
+
+from .gnn2d import GraphIndex, edge_msg, mean_pool  # noqa: F401
 
 # switches that tests / tools / bench.py set as ``ops.NAME = value``: owner module of each
 _SWITCH_OWNER = {

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from .batch import MolStore
+from .batch import GMol, GraphStore, MolStore
 
 FIELDS = ("x", "pos", "edge_index0", "edge_index1", "edge_attr", "e_order", "y", "n_e")
 _FOREIGN = ("torch_geometric", "equihgnn")
@@ -52,12 +52,13 @@ class _PickleModule:
         return _Unpickler(f, **kw).load()
 
 
-def _find_fields(obj, depth=0) -> Optional[Dict[str, torch.Tensor]]:
-    """The first mapping (at any nesting depth of stand-ins / dicts / sequences) that holds the HData tensors."""
+def _find_fields(obj, depth=0, marker="edge_index0") -> Optional[Dict[str, torch.Tensor]]:
+    """The first mapping (at any nesting depth of stand-ins / dicts / sequences) that holds the HData tensors (``marker``:
+    a field name only that kind of record has)."""
     if depth > 8:
         return None
     if isinstance(obj, dict):
-        if "edge_index0" in obj and "x" in obj and torch.is_tensor(obj["x"]):
+        if marker in obj and "x" in obj and torch.is_tensor(obj["x"]):
             return obj
         children = list(obj.values())
     elif isinstance(obj, _Bag):
@@ -67,7 +68,7 @@ def _find_fields(obj, depth=0) -> Optional[Dict[str, torch.Tensor]]:
     else:
         return None
     for c in children:
-        hit = _find_fields(c, depth + 1)
+        hit = _find_fields(c, depth + 1, marker)
         if hit is not None:
             return hit
     return None
@@ -125,3 +126,40 @@ def store_from_slices(fields: Dict[str, torch.Tensor], slices: Dict[str, torch.T
 def read_processed(path, target: int = 0) -> MolStore:
     """MolStore of a reference ``processed/*.pt`` dataset file."""
     return store_from_slices(*load_processed(path), target=target)
+
+
+def read_processed_graph(path, target: int = 0):
+    """GraphStore (batch.py) of a reference 2-D dataset file (``g_data.pt`` of qm9_g / pcqm_g / molecule_g: PyG ``Data``
+    with x, edge_index [2, E] (atom ids local to their molecule), edge_attr [E, F], y; pos, z, smile and idx may be present
+    and are ignored).  Same unpickling as read_processed."""
+    obj = torch.load(path, map_location="cpu", pickle_module=_PickleModule, weights_only=False)
+    if not (isinstance(obj, (tuple, list)) and len(obj) >= 2):
+        raise ValueError(f"{path}: expected the (data, slices) pair of an InMemoryDataset")
+    fields = _find_fields(obj[0], marker="edge_index")
+    slices = obj[1] if isinstance(obj[1], dict) else _find_fields(obj[1], marker="edge_index")
+    if fields is None or not isinstance(slices, dict):
+        raise ValueError(f"{path}: no graph fields (x, edge_index, ...) found")
+    missing = [k for k in ("x", "edge_index", "edge_attr", "y") if k not in fields or k not in slices]
+    if missing:
+        raise ValueError(f"{path}: fields missing from the file: {missing}")
+    npy = lambda t, dt: np.ascontiguousarray(t.detach().cpu().numpy()).astype(dt, copy=False)
+    ns, es = npy(slices["x"], np.int64), npy(slices["edge_index"], np.int64)
+    if not np.array_equal(npy(slices["edge_attr"], np.int64), es):
+        raise ValueError("slices of edge_attr disagree with edge_index")
+    x = npy(fields["x"], np.int64).reshape(-1, 9)
+    ei = npy(fields["edge_index"], np.int64).reshape(2, -1)
+    ea = npy(fields["edge_attr"], np.int64).reshape(ei.shape[1], -1)
+    n_mol = ns.shape[0] - 1
+    y = npy(fields["y"], np.float32).reshape(n_mol, -1)[:, target]
+    if x.shape[0] != ns[-1] or ei.shape[1] != es[-1]:
+        raise ValueError("field lengths disagree with their slices")
+    from .ops.gnn2d import BOND_FEATURE_DIMS
+    if ea.shape[1] > len(BOND_FEATURE_DIMS) or any(
+            ea.shape[0] and (int(ea[:, f].min()) < 0 or int(ea[:, f].max()) >= d) for f, d in enumerate(BOND_FEATURE_DIMS[:ea.shape[1]])):
+        raise ValueError(f"edge_attr outside the ogb bond tables {BOND_FEATURE_DIMS}: the kernels would clamp it")
+    mols = [GMol(x=x[ns[i]:ns[i + 1]], edge_index=ei[:, es[i]:es[i + 1]], edge_attr=ea[es[i]:es[i + 1]], y=float(y[i]))
+            for i in range(n_mol)]
+    for m in mols:
+        if m.edge_index.size and int(m.edge_index.max()) >= m.x.shape[0]:
+            raise ValueError("edge_index is not local to its molecule")
+    return GraphStore(mols)

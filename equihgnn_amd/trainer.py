@@ -309,6 +309,8 @@ class GraphedTrainStep:
 
     @staticmethod
     def _key(b):
+        if not hasattr(b, "edge_index0"):       # a 2-D batch (batch.GBatch): atoms, edges, molecules
+            return (b.x.shape[0], b.edge_index.shape[1], b.y.shape[0])
         return (b.x.shape[0], b.edge_attr.shape[0], b.edge_index0.shape[0], b.y.shape[0])
 
     def _loss(self, data):

@@ -934,6 +934,40 @@ int egnn_pack_weights_bwd(const float* dw_cat, const float* db_cat, const float*
                           int32_t H, int32_t Hp, int32_t C, float* dw1, float* db1, float* dw2,
                           int32_t accumulate, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Edge messages of the 2-D baselines (csrc/gnn2d.hip): GINConv / GCNConv of baseline_2d.py:19-73 with the
+ * ogb BondEncoder summed on the fly (the [E, C] bond embedding is never materialised).
+ *
+ *   mode 0 (GIN): out_i = (1 + eps[0]) x_i + sum_{e: dst(e)=i} relu(x[src_e] + bond(e))
+ *   mode 1 (GCN): out_i = sum_{e: dst(e)=i} norm_e relu(x[src_e] + bond(e)) + relu(x_i + root) / deg_i,
+ *                 deg_i = #{e: src(e)=i} + 1, norm_e = deg_src^-1/2 deg_dst^-1/2
+ *   bond(e) = sum_{f<F} tables[code_f(e), :], tables = the F bond tables stacked, [T, C] with T <= 16, F <= 4.
+ *
+ * hg_edge_codes: code[q] = sum_f (off_host[f] + edge_attr[eid[q], f]) << 8f for the entries of one edge CSR (eid: its
+ *   perm = edge ids in CSR order); column f has off_host[f+1] - off_host[f] rows (the last: T - off_host[F-1]); values
+ *   outside a table are clamped to it.  Built once per batch for both CSRs.
+ * hg_edge_msg_fwd walks the by-dst CSR (in_rowptr, in_src = source atom of each entry, in_code); out_rowptr is the by-src
+ *   CSR's rowptr (GCN's degrees; may be NULL for GIN).  eps (GIN) / root [C] (GCN) are device pointers (capture safe).
+ * hg_edge_msg_bwd walks the by-src CSR (out_rowptr, out_dst, out_code) with dout = d out:
+ *   dx_j = sum_{e: src(e)=j} w_e [x_j + bond(e) > 0] dout[dst_e] + (GIN: (1 + eps) dout_j; GCN: [x_j + root > 0] dout_j / deg_j)
+ *   dtables [T, C] = per table row, the sum of w_e [x_src + bond(e) > 0] dout[dst_e] over the edges selecting it;
+ *   dextra [C]: GCN d root; GIN dextra[0] = d eps = sum_i <x_i, dout_i>, the rest zero.
+ *   dtables is overwritten, or added to with accumulate != 0 (then deferred inside eqh_defer_begin/flush: the five layers
+ *   that share the bond encoder add into its gradient); dextra is always overwritten, at once.
+ *   Workgroup partials in LDS, summed in a fixed order: no atomics, bitwise reproducible.
+ * C % 4 == 0 and C <= 1024; x, out, dout, dx, tables, root 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+int hg_edge_codes(const int64_t* edge_attr, int32_t F, const int32_t* off_host, int32_t T, const int32_t* eid,
+                  int64_t nnz, int32_t* code, void* stream);
+int hg_edge_msg_fwd(int32_t mode, const float* x, const float* tables, int32_t T, int32_t F, const int32_t* in_rowptr,
+                    const int32_t* in_src, const int32_t* in_code, const int32_t* out_rowptr, const float* eps,
+                    const float* root, int64_t N, int32_t C, float* out, void* stream);
+size_t hg_edge_msg_bwd_workspace_bytes(int64_t N, int32_t C, int32_t T);
+int hg_edge_msg_bwd(int32_t mode, const float* x, const float* tables, int32_t T, int32_t F, const int32_t* out_rowptr,
+                    const int32_t* out_dst, const int32_t* out_code, const float* eps, const float* root,
+                    const float* dout, int64_t N, int32_t C, float* dx, float* dtables, float* dextra,
+                    int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
