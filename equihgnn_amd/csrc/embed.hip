@@ -44,16 +44,17 @@ k_embed_fwd(const int64_t* __restrict__ x, const float* __restrict__ table, Offs
     }
 }
 
-// grid = (table_rows, n_chunks); each block sums the matching d out rows of its node chunk.
+// grid = (table_rows, chunks of this launch); block (g, y) sums the matching d out rows of node chunk chunk0 + y.
 template <int LPR>
 __global__ void __launch_bounds__(THREADS)
 k_embed_bwd_partial(const int64_t* __restrict__ x, const float* __restrict__ dout, Offsets offs,
-                    int F, int64_t N, int C, int table_rows, float* __restrict__ part) {
+                    int F, int64_t N, int C, int table_rows, int64_t chunk0, float* __restrict__ part) {
     constexpr int SUBS = THREADS / LPR;
     __shared__ float4 s_acc[THREADS];
     __shared__ int s_list[BWD_CHUNK];
     __shared__ int s_cnt[2];
-    const int g = blockIdx.x, chunk = blockIdx.y;
+    const int g = blockIdx.x;
+    const int64_t chunk = chunk0 + blockIdx.y;
     int f = 0;
     for (int t = 1; t < F; ++t)
         if (g >= offs.off[t]) f = t;
@@ -160,16 +161,21 @@ extern "C" int hg_embed_sum_bwd(const int64_t* x, const float* dout, const int32
     if (N == 0) return accumulate ? EQH_OK : eqh_zero_async(dtable, row_elems, stream);
     if (!x || !dout || !workspace) return EQH_ERR_ARG;
     if (workspace_bytes < hg_embed_sum_bwd_workspace_bytes(N, C, table_rows)) return EQH_ERR_ARG;
-    const int n_chunks = (int)((N + BWD_CHUNK - 1) / BWD_CHUNK);
-    if (n_chunks > 65535) return EQH_ERR_RANGE;
+    const int64_t n_chunks = (N + BWD_CHUNK - 1) / BWD_CHUNK;
+    if (n_chunks > INT32_MAX) return EQH_ERR_RANGE;
     float* part = static_cast<float*>(workspace);
-    rc = dispatch_lpr(C, [&](auto lpr) {
-        constexpr int LPR = decltype(lpr)::value;
-        hipLaunchKernelGGL((k_embed_bwd_partial<LPR>), dim3((unsigned)table_rows, (unsigned)n_chunks),
-                           dim3(THREADS), 0, stream, x, dout, o, F, N, C, (int)table_rows, part);
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
-    });
-    if (rc) return rc;
-    return eqh_reduce_slabs_async(part, n_chunks, row_elems, dtable, stream, accumulate);
+    // grid.y holds at most 65 535 chunks: a longer batch takes several launches, each writing its chunks' slabs of the one
+    // workspace, and a single reduction adds all of them in chunk order (the same sum as one launch would give)
+    for (int64_t c0 = 0; c0 < n_chunks; c0 += 65535) {
+        const unsigned ny = (unsigned)(n_chunks - c0 < 65535 ? n_chunks - c0 : 65535);
+        rc = dispatch_lpr(C, [&](auto lpr) {
+            constexpr int LPR = decltype(lpr)::value;
+            hipLaunchKernelGGL((k_embed_bwd_partial<LPR>), dim3((unsigned)table_rows, ny), dim3(THREADS), 0, stream, x, dout, o,
+                               F, N, C, (int)table_rows, c0, part);
+            EQH_CHECK_LAUNCH();
+            return EQH_OK;
+        });
+        if (rc) return rc;
+    }
+    return eqh_reduce_slabs_async(part, (int)n_chunks, row_elems, dtable, stream, accumulate);
 }

@@ -315,14 +315,16 @@ def wgrad(dy2, x2, alpha: float = 1.0, into=None):
 
 
 SKINNY_WGRAD = not os.environ.get("EQH_NO_SKINNY_WGRAD")
+SKINNY_MAX_ROWS = 64 * 65535   # hg_wgrad_skinny_f32: one workgroup row per 64 rows of dy, at most 65 535 of them (grid.y)
 
 
 def _wgrad_skinny(dy2, x2, tgt) -> bool:
     """tgt [O x J] += dy2.T @ x2 for an input block of at most 16 columns (the m_i block of the EGNN node MLP) through
-    hg_wgrad_skinny_f32: one small launch + the step's deferred slab reduction instead of a split-K library product."""
+    hg_wgrad_skinny_f32: one small launch + the step's deferred slab reduction instead of a split-K library product.
+    False (the caller's next path takes the block) past the kernel's SKINNY_MAX_ROWS."""
     if not (SKINNY_WGRAD and dy2.is_cuda and dy2.dim() == 2 and x2.dim() == 2 and x2.shape[1] <= 16 and dy2.shape[0] == x2.shape[0]
             and dy2.dtype == torch.float32 and x2.dtype == torch.float32 and dy2.stride(1) == 1 and x2.stride(1) == 1
-            and tgt.stride(1) == 1 and dy2.shape[0] > 0):
+            and tgt.stride(1) == 1 and 0 < dy2.shape[0] <= SKINNY_MAX_ROWS):
         return False
     K, O = dy2.shape
     J = x2.shape[1]
