@@ -264,7 +264,7 @@ class MolStore:
         counts = np.zeros(3, dtype=np.int64)
         a.out_counts = counts.ctypes.data
         rc = hip.lib().hb_collate(ctypes.byref(a))
-        if rc == -3 and pad_to is not None:       # EQH_ERR_RANGE: the extents do not fit (indices were checked above)
+        if rc == hip.EQH_ERR_RANGE and pad_to is not None:       # the extents do not fit (indices were checked above)
             raise ValueError("collate: pad_to must exceed the batch (nodes and hyperedges strictly)")
         hip.check(rc, "hb_collate")
         if pad_to is not None:

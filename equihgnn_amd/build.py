@@ -22,6 +22,11 @@ LIB = os.path.join(PKG, "libequihgnn_hip.so")
 # bench.py loads it BESIDE the product library to time the aggregation prologues that have no launch of their own
 STAMPS_LIB = os.path.join(PKG, "libequihgnn_panel_stamps.so")
 ARCH = "gfx950"
+# every compile of the sources, the product library's objects and the diagnostic variants alike
+FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC,
+         "-ffp-contract=off",  # a*b+c stays two roundings unless written fmaf(): the kNN
+                               # distances must match the reference's fp32 CPU arithmetic
+         "-Wall", "-Wno-unused-function"]
 
 
 def _hipcc() -> str:
@@ -43,6 +48,16 @@ def needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def compile_variant(srcs, defines, out: str, verbose: bool = True) -> str:
+    """A diagnostic build: the csrc files `srcs` (e.g. ["panel.hip", "api.hip"]) with the extra macros `defines`
+    (e.g. ["PN_STAMPS"], ["INC_ABLATE=1"]) compiled into the shared library `out`, with the product's flags."""
+    cmd = [_hipcc(), *FLAGS, "-shared", *(f"-D{d}" for d in defines), *(os.path.join(CSRC, s) for s in srcs), "-o", out]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build(force: bool = False, verbose: bool = True) -> str:
     if not force and not needs_build():
         return LIB
@@ -50,10 +65,6 @@ def build(force: bool = False, verbose: bool = True) -> str:
     bdir = os.path.join(PKG, "build")
     os.makedirs(bdir, exist_ok=True)
     hipcc = _hipcc()
-    common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC,
-              "-ffp-contract=off",  # a*b+c stays two roundings unless written fmaf(): the kNN
-                                    # distances must match the reference's fp32 CPU arithmetic
-              "-Wall", "-Wno-unused-function"]
     procs = []
     for src in sources():
         obj = os.path.join(bdir, os.path.basename(src).replace(".hip", ".o"))
@@ -62,7 +73,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
                 and all(os.path.getmtime(obj) > os.path.getmtime(h)
                         for h in glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")))):
             continue
-        cmd = [hipcc, *common, "-c", src, "-o", obj]
+        cmd = [hipcc, *FLAGS, "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd)))
@@ -73,10 +84,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    cmd = [hipcc, *common, "-shared", "-DPN_STAMPS", os.path.join(CSRC, "panel.hip"), os.path.join(CSRC, "api.hip"), "-o", STAMPS_LIB]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
+    compile_variant(["panel.hip", "api.hip"], ["PN_STAMPS"], STAMPS_LIB, verbose)
     return LIB
 
 

@@ -1,9 +1,11 @@
 """CPU-side checks of the drop-in boundary: the shared library loads and exports every symbol
-include/equihgnn_hip.h declares, the ctypes table matches the header, argument validation
-works without a GPU, and the product refuses to run on CPU tensors (no fallback)."""
+include/equihgnn_hip.h declares, the ctypes table derived from the header matches a second reading of it and the
+compiler's struct layout, argument validation works without a GPU, and the product refuses to run on CPU tensors
+(no fallback)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -16,6 +18,16 @@ def declared_functions():
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b([a-z_0-9]+)\s*\([^;{]*\)\s*;", text)))
+
+
+def declared_argument_counts():
+    """name -> number of parameters of every function the header declares (a reader independent of equihgnn_amd.hip)"""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return {name: 0 if args.strip() == "void" else args.count(",") + 1
+            for name, args in re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)}
+
+
+STRUCTS = ("HgSmallMM", "HgGemmProblem", "HgPanelPack", "HgConvPanel", "HgPanelMulti", "HgPanelSum", "HbCollate")
 
 
 def test_header_declares_functions():
@@ -32,6 +44,99 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(handle, name), f"{name} declared in the header but not exported"
     assert sorted(hip.SIGNATURES) == declared_functions()
     assert hip.lib().eqh_version() >= 1
+
+
+def test_signatures_take_the_header_argument_counts():
+    from equihgnn_amd import hip
+
+    counts = declared_argument_counts()
+    assert sorted(counts) == sorted(hip.SIGNATURES)
+    assert {n: len(hip.SIGNATURES[n][1]) for n in counts} == counts
+
+
+def test_struct_layout_matches_the_compiler(tmp_path):
+    """sizeof of every argument struct and offsetof / sizeof of every field, as the host compiler lays them out, against
+    the derived ctypes.Structure classes: a field swapped, dropped or mistyped is caught here, before a kernel reads it."""
+    from equihgnn_amd import build, hip
+
+    lines, want = [], {}
+    for s in STRUCTS:
+        cls = getattr(hip, s)
+        lines.append(f'std::printf("{s} %zu\\n", sizeof({s}));')
+        want[s] = str(ctypes.sizeof(cls))
+        for f, _ in cls._fields_:
+            lines.append(f'std::printf("{s}.{f} %zu %zu\\n", offsetof({s}, {f}), sizeof((({s}*)nullptr)->{f}));')
+            want[f"{s}.{f}"] = f"{getattr(cls, f).offset} {getattr(cls, f).size}"
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text('#include <cstddef>\n#include <cstdio>\n#include "equihgnn_hip.h"\nint main() {\n' + "\n".join(lines)
+                   + "\nreturn 0;\n}\n")
+    subprocess.check_call([build._hipcc(), "-x", "c++", "-I", build.INCLUDE, str(src), "-o", str(exe)])
+    got = dict(line.split(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    assert got == want
+
+
+def test_constants_match_the_header():
+    from equihgnn_amd import hip
+
+    text = open(HEADER).read()
+    defines = dict(re.findall(r"#define (EQH_\w+) \(?(-?\d+)\)?", text))
+    (enum,) = re.findall(r"enum \{([^}]*)\}", text)
+    stages = dict(re.findall(r"(\w+) = (\d+)", enum))
+    assert sorted(defines) == ["EQH_ERR_ALIGN", "EQH_ERR_ARG", "EQH_ERR_LAUNCH", "EQH_ERR_RANGE", "EQH_OK"]
+    assert list(stages) == ["HG_CONV_F1", "HG_CONV_F2", "HG_CONV_F3", "HG_CONV_B3", "HG_CONV_B1", "HG_EGNN_NODE_F",
+                            "HG_EGNN_NODE_B"]
+    for name, value in {**defines, **stages}.items():
+        assert getattr(hip, name) == int(value), name
+    assert hip.EQH_ERR_RANGE == -3 and hip.HG_CONV_F1 == 1 and hip.HG_EGNN_NODE_B == 7
+
+
+def test_header_reader_maps_each_c_type_and_refuses_the_rest():
+    from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_size_t, c_void_p
+
+    from equihgnn_amd import hip
+
+    structs, sigs, consts = hip.parse_header(
+        "#define EQH_X (-9)\n"
+        "enum { STAGE_A = 1, STAGE_B = 2 };\n"
+        "/* a comment */ typedef struct Tag {\n    int32_t n, k;\n    const void* w[3];\n    const float *in0, *in1;\n} S;\n"
+        "int f(int a, int32_t b, int64_t c, size_t d, float e, const float* const* g, void** h,\n"
+        "      const S* s, float* __restrict__ p, const uint8_t* m);\n"
+        "const char* name(int code);\n"
+        "void nothing(void);\n")
+    S = structs["S"]
+    assert [(n, t) for n, t in S._fields_ if n != "w"] == [("n", c_int32), ("k", c_int32), ("in0", c_void_p), ("in1", c_void_p)]
+    assert [n for n, _ in S._fields_] == ["n", "k", "w", "in0", "in1"]
+    w = dict(S._fields_)["w"]
+    assert (w._type_, w._length_) == (c_void_p, 3)
+    assert sigs == {"f": (c_int32, [c_int32, c_int32, c_int64, c_size_t, c_float, c_void_p, POINTER(c_void_p), POINTER(S),
+                                    c_void_p, c_void_p]),
+                    "name": (c_char_p, [c_int32]),
+                    "nothing": (None, [])}
+    assert consts == {"EQH_X": -9, "STAGE_A": 1, "STAGE_B": 2}
+    # no silent c_void_p: an unknown scalar, a pointer to an unknown type, a struct by value, an unreadable declaration
+    # (uint8_t is known as a pointer's target -- faf_edge_frame_fwd's mask -- but not as a value)
+    for snippet, line, decl in (("int f(int a,\n      double x);", 2, "double x"),
+                                ("typedef struct {\n    int32_t n;\n    double x;\n} T;", 3, "double x"),
+                                ("int f(uint8_t v);", 1, "uint8_t v"),
+                                ("int f(double* p);", 1, "double* p"),
+                                ("int f(unsigned int n);", 1, "unsigned int n"),
+                                ("typedef struct {\n    int32_t n;\n} T;\nint f(T t);", 4, "T t"),
+                                ("int f(int n);\ntypedef int32_t idx_t;", 2, "typedef int32_t idx_t"),
+                                ("int f(void (*cb)(int));", 1, "cb")):
+        with pytest.raises(ValueError, match=rf"^snippet\.h:{line}: cannot bind `.*{re.escape(decl)}"):
+            hip.parse_header(snippet, "snippet.h")
+
+
+def test_partial_load_of_a_diagnostic_build():
+    """hip.load(partial=True) types what a build of some of the sources exports; the full rule refuses that build."""
+    from equihgnn_amd import build, hip
+
+    build.build(verbose=False)
+    L = hip.load(build.STAMPS_LIB, partial=True)
+    assert list(L.hg_conv_panel.argtypes) == hip.SIGNATURES["hg_conv_panel"][1]
+    assert L.hg_conv_panel_slab_bytes.restype is ctypes.c_size_t
+    with pytest.raises(hip.HipLibraryError, match="does not export"):
+        hip.load(build.STAMPS_LIB)
 
 
 def test_argument_validation_without_gpu():

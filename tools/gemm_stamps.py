@@ -4,7 +4,6 @@ scratch library (the product library carries no stamps), runs one problem and pr
 counts of the pipeline phases (s_memtime) over the workgroups launched in the middle of the grid."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
-from equihgnn_amd import hip
+from equihgnn_amd import build, hip
 
 
 def main():
@@ -21,11 +20,8 @@ def main():
     ta = int(sys.argv[5]) if len(sys.argv) > 5 else 0
     tb = int(sys.argv[6]) if len(sys.argv) > 6 else 1
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libgemm_stamps.so")
-    extra = [f"-D{d}" for d in os.environ.get("GX_DEFS", "").split() if d]
-    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-DGX_STAMPS", *extra,
-                           "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "equihgnn_amd", "csrc"),
-                           os.path.join(ROOT, "equihgnn_amd", "csrc", "gemm_x6.hip"), os.path.join(ROOT, "equihgnn_amd", "csrc", "api.hip"), "-o", so])
-    L = ctypes.CDLL(so)
+    build.compile_variant(["gemm_x6.hip", "api.hip"], ["GX_STAMPS", *os.environ.get("GX_DEFS", "").split()], so)
+    L = hip.load(so, partial=True)
     dev = "cuda:0"
     g = torch.Generator(device=dev).manual_seed(0)
     A = torch.randn((K, M) if ta else (M, K), device=dev, generator=g)
@@ -39,8 +35,6 @@ def main():
     q.a, q.lda, q.b, q.ldb, q.c, q.ldc = A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0)
     q.m, q.n, q.k, q.trans_a, q.trans_b, q.alpha, q.beta = M, N, K, ta, tb, 1.0, 0.0
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.hg_gemm_x6_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(hip.HgGemmProblem), ctypes.c_int32, ctypes.c_void_p,
-                                   ctypes.c_size_t, ctypes.c_void_p]
     for _ in range(int(os.environ.get('GX_WARM', '2000'))):      # ~0.5 s of back-to-back launches: the clock the chip HOLDS under this load
         assert L.hg_gemm_x6_batch(1, pr, tile, None, 0, stream) == 0
     assert L.hg_gemm_x6_debug_stamps(ctypes.c_void_p(buf.data_ptr())) == 0

@@ -8,7 +8,6 @@ The algorithmic bytes of the launch over the `chain` time is the ceiling ANY ker
 this size; over the `no-LN` time, the ceiling of a pure gather-reduce.  python tools/inc_ablation.py"""
 import ctypes
 import os
-import subprocess
 import sys
 import time
 
@@ -16,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
-from equihgnn_amd import hip, ops
+from equihgnn_amd import build as _build, hip, ops
 from equihgnn_amd.batch import bucket_sizes, pad_batch, synth_batch
 from equihgnn_amd.index import HyperIndex
 
@@ -37,13 +36,8 @@ NCH = 40
 
 def build(flag):
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"libinc_ablate{flag}.so")
-    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", f"-DINC_ABLATE={flag}",
-                           "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "equihgnn_amd", "csrc"),
-                           os.path.join(ROOT, "equihgnn_amd", "csrc", "incidence.hip"), os.path.join(ROOT, "equihgnn_amd", "csrc", "api.hip"),
-                           "-o", so])
-    L = ctypes.CDLL(so)
-    L.hg_incidence_ln_reduce_fwd_col.argtypes = hip.SIGNATURES["hg_incidence_ln_reduce_fwd_col"][1]
-    return L
+    _build.compile_variant(["incidence.hip", "api.hip"], [f"INC_ABLATE={flag}"], so)
+    return hip.load(so, partial=True)
 
 
 def timeit(name, L):

@@ -10,7 +10,6 @@ the launch's (all panels).  Writes the JSON that bench.py reports as roofline.ke
 import ctypes
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -34,11 +33,8 @@ def measure(method="egnn_equihnns", batch=256, flavour="qm9", C=256, dev=None, v
     so = _build.STAMPS_LIB
     if not os.path.exists(so):
         so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libpanel_stamps.so")
-        subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-DPN_STAMPS",
-                               "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "equihgnn_amd", "csrc"),
-                               os.path.join(ROOT, "equihgnn_amd", "csrc", "panel.hip"), os.path.join(ROOT, "equihgnn_amd", "csrc", "api.hip"), "-o", so])
-    L = ctypes.CDLL(so)
-    L.hg_conv_panel.argtypes = hip.SIGNATURES["hg_conv_panel"][1]
+        _build.compile_variant(["panel.hip", "api.hip"], ["PN_STAMPS"], so)
+    L = hip.load(so, partial=True)
     dev = torch.device("cuda:0") if dev is None else dev
     host = synth_batch(batch, 2000, flavour)
     b = pad_batch(host, *bucket_sizes(host.num_nodes, host.num_hyperedges, host.nnz)).to(dev)

@@ -4,7 +4,6 @@ library (the product library carries no stamps), runs one [rows x 256] . [256 x 
 counts (s_memtime) of the phases over all workgroups.  python tools/panel_stamps.py [rows]"""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,18 +12,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
-from equihgnn_amd import hip, ops
+from equihgnn_amd import build, hip, ops
 
 
 def main():
     rows = int(sys.argv[1]) if len(sys.argv) > 1 else 4864
     C = 256
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libpanel_stamps.so")
-    extra = [f"-D{d}" for d in os.environ.get("PN_DEFS", "").split() if d]
-    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-DPN_STAMPS", *extra,
-                           "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "equihgnn_amd", "csrc"),
-                           os.path.join(ROOT, "equihgnn_amd", "csrc", "panel.hip"), os.path.join(ROOT, "equihgnn_amd", "csrc", "api.hip"), "-o", so])
-    L = ctypes.CDLL(so)
+    build.compile_variant(["panel.hip", "api.hip"], ["PN_STAMPS", *os.environ.get("PN_DEFS", "").split()], so)
+    L = hip.load(so, partial=True)
     dev = "cuda:0"
     g = torch.Generator(device=dev).manual_seed(0)
     x = torch.randn(rows, C, device=dev, generator=g)
@@ -34,7 +30,6 @@ def main():
     nb = (rows + 31) // 32
     buf = torch.zeros(nb * 4 * 8, dtype=torch.int64, device=dev)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.hg_panel_gemm_f32.argtypes = hip.SIGNATURES["hg_panel_gemm_f32"][1]
 
     def run():
         assert L.hg_panel_gemm_f32(x.data_ptr(), C, rows, C, img.data_ptr(), 1.0, None, 0, 0.0, None, 0, out.data_ptr(), C, stream) == 0

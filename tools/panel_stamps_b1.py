@@ -3,7 +3,6 @@
 -DPN_STAMPS into a scratch library.  python tools/panel_stamps_b1.py"""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
-from equihgnn_amd import hip, ops
+from equihgnn_amd import build, hip, ops
 from equihgnn_amd.batch import bucket_sizes, pad_batch, synth_batch
 from equihgnn_amd.index import HyperIndex
 
@@ -20,10 +19,8 @@ from equihgnn_amd.index import HyperIndex
 def main():
     C = 256
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libpanel_stamps.so")
-    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-DPN_STAMPS",
-                           "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "equihgnn_amd", "csrc"),
-                           os.path.join(ROOT, "equihgnn_amd", "csrc", "panel.hip"), os.path.join(ROOT, "equihgnn_amd", "csrc", "api.hip"), "-o", so])
-    L = ctypes.CDLL(so)
+    build.compile_variant(["panel.hip", "api.hip"], ["PN_STAMPS"], so)
+    L = hip.load(so, partial=True)
     dev = torch.device("cuda:0")
     host = synth_batch(256, 2000, "qm9")
     b = pad_batch(host, *bucket_sizes(host.num_nodes, host.num_hyperedges, host.nnz)).to(dev)
@@ -51,7 +48,6 @@ def main():
                      g1=vecs[3], out2=outs[2], out3=outs[3], out4=outs[4], acc_out=acc, slab2=slab2, dbias2=v3[0], dgamma2=v3[1],
                      dbeta2=v3[2]).items():
         setattr(a, k, t.data_ptr())
-    L.hg_conv_panel.argtypes = hip.SIGNATURES["hg_conv_panel"][1]
     run = lambda: L.hg_conv_panel(hip.HG_CONV_B1, a, stream)
     for _ in range(3):
         assert run() == 0

@@ -2,7 +2,6 @@
 """Diagnostic: phases of k_conv_f3 (no tail) by s_memtime stamps; builds csrc/panel.hip with -DPN_STAMPS into a scratch library."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -11,17 +10,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
-from equihgnn_amd import hip, ops
+from equihgnn_amd import build, hip, ops
 
 
 def main():
     rows = int(sys.argv[1]) if len(sys.argv) > 1 else 4736
     C = 256
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libpanel_stamps.so")
-    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-DPN_STAMPS",
-                           "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "equihgnn_amd", "csrc"),
-                           os.path.join(ROOT, "equihgnn_amd", "csrc", "panel.hip"), os.path.join(ROOT, "equihgnn_amd", "csrc", "api.hip"), "-o", so])
-    L = ctypes.CDLL(so)
+    build.compile_variant(["panel.hip", "api.hip"], ["PN_STAMPS"], so)
+    L = hip.load(so, partial=True)
     dev = "cuda:0"
     g = torch.Generator(device=dev).manual_seed(0)
     rn = lambda *sh: torch.randn(*sh, device=dev, generator=g)
@@ -37,7 +34,6 @@ def main():
     a.rows, a.C, a.eps, a.scale, a.relu, a.tail = rows, C, 1e-5, 0.5, 1, 0
     for k, t in dict(in0=s_, in1=cw, w0=i23, b0=b3a, g0=g3, be0=be3, w1=i3b, bias_out=b3b, out0=u, out1=x3, out2=xn).items():
         setattr(a, k, t.data_ptr())
-    L.hg_conv_panel.argtypes = hip.SIGNATURES["hg_conv_panel"][1]
     run = lambda: L.hg_conv_panel(hip.HG_CONV_F3, a, stream)
     for _ in range(3):
         assert run() == 0

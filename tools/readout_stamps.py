@@ -6,7 +6,6 @@ workgroup) in a -DRH_STAMPS build of csrc/readout.hip, on a BASELINE-shaped batc
 """
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
-from equihgnn_amd import hip, ops
+from equihgnn_amd import build, hip, ops
 
 NAMES = ["issue loads", "pool + vectors to LDS", "barrier", "layer 1 product", "LayerNorm 1", "layer 2 product", "LayerNorm 2",
          "output + dy", "LN2 backward + v3 slab", "dh1 product, v2 / w2 slabs", "barrier", "LN1 backward", "dx product",
@@ -24,14 +23,8 @@ NAMES = ["issue loads", "pool + vectors to LDS", "barrier", "layer 1 product", "
 
 def main():
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libreadout_stamps.so")
-    csrc = os.path.join(ROOT, "equihgnn_amd", "csrc")
-    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-DRH_STAMPS", "-ffp-contract=off",
-                           "-I", os.path.join(ROOT, "include"), "-I", csrc, os.path.join(csrc, "readout.hip"), os.path.join(csrc, "api.hip"),
-                           "-o", so])
-    L = ctypes.CDLL(so)
-    L.hg_readout_mse_f32.argtypes = hip.SIGNATURES["hg_readout_mse_f32"][1]
-    L.hg_readout_mse_workspace_bytes.restype = ctypes.c_size_t
-    L.hg_readout_mse_workspace_bytes.argtypes = hip.SIGNATURES["hg_readout_mse_workspace_bytes"][1]
+    build.compile_variant(["readout.hip", "api.hip"], ["RH_STAMPS"], so)
+    L = hip.load(so, partial=True)
     dev = torch.device("cuda:0")
     B, C, H = 257, 256, 128
     g = torch.Generator().manual_seed(0)

@@ -14,8 +14,7 @@ import torch
 from equihgnn_amd import build as _build, hip, ops
 
 rows, K, N = (int(v) for v in sys.argv[1:4]) if len(sys.argv) > 3 else (246016, 256, 256)
-L = ctypes.CDLL(_build.STAMPS_LIB)
-L.hg_panel_stream_gemm_f32.argtypes = hip.SIGNATURES["hg_panel_stream_gemm_f32"][1]
+L = hip.load(_build.STAMPS_LIB, partial=True)
 dev = torch.device("cuda:0")
 x = torch.randn(rows, K, device=dev)
 w = torch.randn(N, K, device=dev) * K ** -0.5
