@@ -70,6 +70,8 @@ class HyperIndex:
         self.has_v, self.has_e = has_v.unsqueeze(-1), has_e.unsqueeze(-1)
         self._knn = {}
         self._knn_pos = {}      # (k, mode) -> address of the coordinates the search ran on (GraphedTrainStep's index prefetch)
+        self._radius = {}       # (r, k) -> ops.RadiusGraph (ViSNet); _radius_args: (r, k) -> (pos address, means, betas)
+        self._radius_args = {}
         self._pad = None        # (batch, number of real molecules) of a padded batch, set by from_batch
         self._masks = None
         self._he_pool = None
@@ -102,6 +104,8 @@ class HyperIndex:
                 return hit
             if isinstance(v, ops.CSR):
                 return ops.CSR(**{k: cp(x) for k, x in v.__dict__.items()})
+            if isinstance(v, ops.RadiusGraph):
+                return ops.RadiusGraph(**{k: cp(x) for k, x in v.__dict__.items()})
             if isinstance(v, tuple):
                 return tuple(cp(x) for x in v)
             if isinstance(v, list):
@@ -112,10 +116,11 @@ class HyperIndex:
 
         out = HyperIndex.__new__(HyperIndex)
         for name, v in self.__dict__.items():
-            if name in ("_pad", "_masks", "_he_pool", "_knn_counts"):
+            if name in ("_pad", "_masks", "_he_pool", "_knn_counts", "_radius_args"):
                 continue
             setattr(out, name, cp(v))
         out._masks = out._he_pool = out._knn_counts = None
+        out._radius_args = dict(getattr(self, "_radius_args", {}))
         out._pad = None if self._pad is None else (batch.batch, self._pad[1])
         return out, dsts, srcs
 
@@ -180,4 +185,19 @@ class HyperIndex:
             csr_t = ops.csr_build(nbr.reshape(-1), None, self.N, counts=counts if counted else None)   # int32 keys: no widening copy
             hit = (nbr, key, csr_t)
             self._knn[(k, mode)] = hit
+        return hit
+
+    def radius(self, pos: torch.Tensor, r: float, k: int, means: torch.Tensor, betas: torch.Tensor):
+        """ops.RadiusGraph of ViSNet's Distance (radius ``r``, the first ``k`` = 16 atoms of each molecule in index order,
+        self-loops kept) with its per-slot geometry (ExpNormalSmearing ``means`` / ``betas``, Sphere lmax 2), built once
+        per batch like ``knn``.  Pad atoms of a padded batch keep only their self-loop."""
+        if k != 16:
+            raise ValueError(f"radius: the slot table holds 16 neighbours (got max_num_neighbors={k})")
+        key = (float(r), int(k))
+        cache = self.__dict__.setdefault("_radius", {})
+        hit = cache.get(key)
+        if hit is None:
+            self.__dict__.setdefault("_radius_args", {})[key] = ((pos.data_ptr(), tuple(pos.shape), pos.dtype), means, betas)
+            hit = ops.radius_graph(pos, self.batch32, self.pool.rowptr, self.n_box, means, betas, r)
+            cache[key] = hit
         return hit

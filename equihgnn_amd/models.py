@@ -15,6 +15,7 @@ from .index import HyperIndex
 from .layers import (EGNN, MLP, AtomEncoder, BondEncoder, MHNNConv, MHNNSConv, batch_norm_rows, head_loss, pool_sum, readout,
                      real_row_mask)
 from .registry import registry
+from .visnet import ViSNet
 
 _ACT = {"Id": nn.Identity, "relu": nn.ReLU, "prelu": nn.PReLU}
 
@@ -206,14 +207,18 @@ class _PairedBase(nn.Module):
                            dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
         self.with_egnn = with_egnn
 
-    def forward(self, data, taps=None, head=None):
-        from . import ops
-        index = HyperIndex.from_batch(data)
+    def _front(self, data, index, taps):
         x = self.atom_encoder(data.x)
         if self.with_egnn:
             x = self.egnn_layer(x, data.pos, index)
             if taps is not None:
                 taps["front_end"] = x
+        return x
+
+    def forward(self, data, taps=None, head=None):
+        from . import ops
+        index = HyperIndex.from_batch(data)
+        x = self._front(data, index, taps)
         e = self.bond_encoder(data.edge_attr)
         with _merged_scope([self.conv], x, e):      # the shared layer's weight-level products once per step
             for i in range(self.nlayer):
@@ -346,9 +351,96 @@ class FAFormerEquiHNNS(nn.Module):
         return readout(self.mlp_out, self.dropout(x), index, taps, head)
 
 
+def _visnet(args):
+    """The wrappers' ViSNet (equihnn_visnet.py:35-37,114-118,183-185)."""
+    return ViSNet(hidden_channels=args.MLP_hidden, lmax=2, max_num_neighbors=16)
+
+
+def _visnet_front(model, data, index, taps):
+    x = model.visnet_layer(data.x, data.pos, index)
+    if taps is not None:
+        taps["front_end"] = x
+    return x
+
+
+@registry.register_model("visnet_equihnn")
+class VisNetEquiHNN(_PairedBase):
+    """equihnn_visnet.py:11-89: ViSNet (its own two AtomEncoders) -> shared MHNNConv x L -> node and order > 2 hyperedge
+    pools -> head.  No AtomEncoder of its own."""
+
+    def __init__(self, num_target, args):
+        super().__init__(num_target, args, with_egnn=False)
+        del self.atom_encoder
+        self.visnet_layer = _visnet(args)
+
+    def _front(self, data, index, taps):
+        return _visnet_front(self, data, index, taps)
+
+
+@registry.register_model("visnet_equihnns")
+class VisNetEquiHNNS(nn.Module):
+    """equihnn_visnet.py:92-158: ViSNet (once) -> shared MHNNSConv x L -> pool -> head."""
+
+    def __init__(self, num_target, args):
+        super().__init__()
+        self.act = _ACT[args.activation]()
+        self.dropout = nn.Dropout(args.dropout)
+        self.mlp1_layers = args.MLP1_num_layers
+        self.mlp2_layers = args.MLP2_num_layers
+        self.mlp3_layers = args.MLP3_num_layers
+        self.nlayer = args.All_num_layers
+        self.visnet_layer = _visnet(args)
+        self.conv = MHNNSConv(args.MLP_hidden, mlp1_layers=self.mlp1_layers, mlp2_layers=self.mlp2_layers,
+                              mlp3_layers=self.mlp3_layers, aggr=args.aggregate, dropout=args.dropout,
+                              normalization=args.normalization)
+        self.mlp_out = MLP(in_channels=args.MLP_hidden, hidden_channels=args.output_hidden,
+                           out_channels=num_target, num_layers=args.output_num_layers,
+                           dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
+
+    def reset_parameters(self):
+        self.conv.reset_parameters()
+        self.mlp_out.reset_parameters()
+
+    def forward(self, data, taps=None, head=None):
+        index = HyperIndex.from_batch(data)
+        x = _visnet_front(self, data, index, taps)
+        x0 = x
+        res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
+        fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
+        x = _conv_layers(self, x, index, x0, res, fuse_act, taps)
+        return readout(self.mlp_out, self.dropout(x), index, taps, head)
+
+
+@registry.register_model("visnet_equihnnm")
+class VisNetEquiHNNM(MHNNM):
+    """equihnn_visnet.py:161-243: mhnnm with ViSNet in place of the AtomEncoder."""
+
+    def __init__(self, num_target, args):
+        super().__init__(num_target, args)
+        del self.atom_encoder
+        self.visnet_layer = _visnet(args)
+
+    def forward(self, data, taps=None, head=None):
+        index = HyperIndex.from_batch(data)
+        x = _visnet_front(self, data, index, taps)
+        e = self.bond_encoder(data.edge_attr)
+        mask = real_row_mask(data, x)   # padded batch: BatchNorm statistics over the real atoms only
+        for i, layer in enumerate(self.layers):
+            x, e = layer(x, e, index)
+            fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
+            x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
+            if taps is not None:
+                taps[f"bn{i}"] = x
+            if i != self.nlayer - 1:
+                x, e = (x if fuse else self.act(x)), self.act(e)
+            x, e = self.dropout(x), self.dropout(e)
+        return readout(self.mlp_out, x, index, taps, head)
+
+
 from .baseline_2d import GNN_2D  # noqa: E402  (registers gin / gcn; constructed as GNN_2D(1, gnn_type=...))
 
 MODELS = {"egnn_equihnns": EGNNEquiHNNS, "mhnnm": MHNNM, "equiformer_equihnns": EquiformerEquiHNNS,
           "faformer_equihnns": FAFormerEquiHNNS,
           "mhnn": MHNN, "mhnns": MHNNS, "egnn_equihnn": EGNNEquiHNN, "egnn_equihnnm": EGNNEquiHNNM,
-          "gin": GNN_2D, "gcn": GNN_2D}
+          "gin": GNN_2D, "gcn": GNN_2D,
+          "visnet_equihnn": VisNetEquiHNN, "visnet_equihnns": VisNetEquiHNNS, "visnet_equihnnm": VisNetEquiHNNM}

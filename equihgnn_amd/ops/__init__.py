@@ -18,6 +18,7 @@ One module per subsystem; everything is re-exported here, so cal
   se3      Equiformer: row GEMMs, radial trunk, attention pooling, RMS norm, edge geometry
   gnn2d    2-D baselines: graph index (edge CSRs, bond codes), GIN / GCN edge messages, mean pool
   frames   FAFormer: frame-averaged SwiGLU pieces, edge hidden layer, row dots, gates, attention sums, eigh3
+  visnet   ViSNet: per-molecule radius graph and slot geometry, neighbour / edge embedding, ViS_MP message and edge update
 
 Module-level switches (``ops.GEMM_TILE``, ``ops.TIMELINE``, ``ops.KNN_GRID_MIN_POINTS``, ...) are read by the
 submodule that owns them; assigning them on this package forwards the value there (_OpsModule below).
@@ -86,6 +87,9 @@ from .frames import (  # noqa: F401
 )
 
 from .gnn2d import GraphIndex, edge_msg, mean_pool  # noqa: F401
+from .visnet import (  # noqa: F401
+    RadiusGraph, radius_graph, vis_neighbor_sum, vis_edge_embed, vis_attn, vis_vec_msg, vis_edge_update,
+)
 
 # switches that tests / tools / bench.py set as ``ops.NAME = value``: owner module of each
 _SWITCH_OWNER = {

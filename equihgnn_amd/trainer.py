@@ -622,6 +622,9 @@ class GraphedTrainStep:
         keys = list(ixw._knn.keys())
         if any(ixw._knn_pos.get(k) != want for k in keys) or any(static.pos.shape[0] - 1 < k for k, m in keys if m == 1):
             return None
+        rkeys = list(getattr(ixw, "_radius_args", {}).items())      # (r, k) -> (coordinates, RBF means, betas): ViSNet
+        if any(at != want for _, (at, _m, _b) in rkeys):
+            return None
         staged = static.packed()
         staged.num_real_graphs = getattr(static, "num_real_graphs", None)
         from . import ops
@@ -636,6 +639,8 @@ class GraphedTrainStep:
             ix = HyperIndex.from_batch(staged)
             for k, m in keys:
                 ix.knn(staged.pos, k, m)
+            for (r, k), (_at, means, betas) in rkeys:
+                ix.radius(staged.pos, r, k, means, betas)
             return ix
         stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(stream):

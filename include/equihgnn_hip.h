@@ -968,6 +968,59 @@ int hg_edge_msg_bwd(int32_t mode, const float* x, const float* tables, int32_t T
                     const float* dout, int64_t N, int32_t C, float* dx, float* dtables, float* dextra,
                     int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ViSNet front-end (csrc/visnet.hip): visnet_layer.py's radius graph, NeighborEmbedding, EdgeEmbedding and ViS_MP
+ * message / aggregation / edge update on a static [N, 16] slot table.  Edge e = 16 i + s is the s-th kept source j of
+ * target i (slot[e] = j, or -1 for s >= cnt[i]); edge_vec = pos[j] - pos[i].  No [E, 8, C] tensor, no atomics.
+ *
+ * vis_radius_graph: for each target i, the first 16 atoms j of i's molecule (pool_rowptr, batch), ascending, i included,
+ *   with fp32 (dx^2 + dy^2) + dz^2 < cutoff^2 (torch_cluster radius_graph, loop = True, max_num_neighbors = 16).  Atoms
+ *   at index >= *n_real (device int32; NULL: none) keep only their self-loop.  Per slot [16 N]: r (0 for self), cut =
+ *   CosineCutoff(r), rbf [.., 32] = ExpNormalSmearing(r) (means, betas: device [32]), sh [.., 8] = Sphere(lmax 2) of the
+ *   normalised edge vector (0 for self); empty slots all 0.  By source: src_cnt[j] edges src_eid[src_start[j] ...].
+ * vis_nbr_fwd / bwd: y_i = sum_{s < cnt_i, j != i} x_j (W_e cut_e)  (dx, dW = d(W) per slot).
+ * vis_edge_embed_fwd / bwd: f_e = (x_i + x_j) W_e  (dx, dW).
+ * vis_attn_fwd / bwd: pre_{e,h} = sum_{c in head h} q_i k_j silu(dkr_e) (8 heads of C / 8), a = silu(pre) cut_e,
+ *   u_e = v_j silu(dvr_e) a, xagg_i = sum_e u_e; pre [16 N, 8] is saved; bwd takes du and dxagg, writes dq, dk, dv,
+ *   ddkr, ddvr and dpre [16 N, 8] (scratch).
+ * vis_vec_fwd / bwd: vo_i[m] = sum_e vec_j[m] silu(sr_e[:C]) + silu(sr_e[C:]) sh_e[m]  (vec, vo: [N, 8, C]; sr:
+ *   [16 N, 2 C]); bwd: dvec, dsr.
+ * vis_edge_update_fwd / bwd: df_e = silu(fr_e) sum_m rej(wt_i, sh_e)_m rej(ws_j, -sh_e)_m, rej(w, d) = w - (w . d) d
+ *   over the 8 components (wt, ws: [N, 8, C]); bwd: dwt, dws, dfr.
+ * Empty slots contribute 0 and their per-edge gradient rows are written as 0.  C % 8 == 0, C <= 512.
+ * ------------------------------------------------------------------------------------------- */
+int vis_radius_graph(const float* pos, const int32_t* batch, const int32_t* pool_rowptr, const int32_t* n_real,
+                     const float* means, const float* betas, int64_t N, float cutoff, int32_t* slot, int32_t* cnt,
+                     float* r, float* cut, float* rbf, float* sh, int32_t* src_start, int32_t* src_cnt,
+                     int32_t* src_eid, void* stream);
+int vis_nbr_fwd(const float* x, const float* W, const float* cut, const int32_t* slot, const int32_t* cnt, int64_t N,
+                int32_t C, float* y, void* stream);
+int vis_nbr_bwd(const float* x, const float* W, const float* cut, const int32_t* slot, const int32_t* cnt,
+                const int32_t* src_start, const int32_t* src_cnt, const int32_t* src_eid, const float* dy, int64_t N,
+                int32_t C, float* dx, float* dW, void* stream);
+int vis_edge_embed_fwd(const float* x, const float* W, const int32_t* slot, const int32_t* cnt, int64_t N, int32_t C,
+                       float* f, void* stream);
+int vis_edge_embed_bwd(const float* x, const float* W, const int32_t* slot, const int32_t* cnt,
+                       const int32_t* src_start, const int32_t* src_cnt, const int32_t* src_eid, const float* df,
+                       int64_t N, int32_t C, float* dx, float* dW, void* stream);
+int vis_attn_fwd(const float* q, const float* k, const float* v, const float* dkr, const float* dvr, const float* cut,
+                 const int32_t* slot, const int32_t* cnt, int64_t N, int32_t C, float* u, float* xagg, float* pre,
+                 void* stream);
+int vis_attn_bwd(const float* q, const float* k, const float* v, const float* dkr, const float* dvr, const float* cut,
+                 const float* pre, const int32_t* slot, const int32_t* cnt, const int32_t* src_start,
+                 const int32_t* src_cnt, const int32_t* src_eid, const float* du, const float* dxagg, int64_t N,
+                 int32_t C, float* dq, float* dk, float* dv, float* ddkr, float* ddvr, float* dpre, void* stream);
+int vis_vec_fwd(const float* vec, const float* sr, const float* sh, const int32_t* slot, const int32_t* cnt, int64_t N,
+                int32_t C, float* vo, void* stream);
+int vis_vec_bwd(const float* vec, const float* sr, const float* sh, const int32_t* slot, const int32_t* cnt,
+                const int32_t* src_start, const int32_t* src_cnt, const int32_t* src_eid, const float* dvo, int64_t N,
+                int32_t C, float* dvec, float* dsr, void* stream);
+int vis_edge_update_fwd(const float* wt, const float* ws, const float* fr, const float* sh, const int32_t* slot,
+                        const int32_t* cnt, int64_t N, int32_t C, float* df, void* stream);
+int vis_edge_update_bwd(const float* wt, const float* ws, const float* fr, const float* sh, const int32_t* slot,
+                        const int32_t* cnt, const int32_t* src_start, const int32_t* src_cnt, const int32_t* src_eid,
+                        const float* ddf, int64_t N, int32_t C, float* dwt, float* dws, float* dfr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
