@@ -27,6 +27,16 @@ def declared_argument_counts():
             for name, args in re.findall(r"\b([a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text)}
 
 
+def vis_entry_points():
+    """name -> [(C type, parameter name)] of every vis_* function the header declares"""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for name, args in re.findall(r"\b(vis_[a-z_0-9]+)\s*\(([^;{]*)\)\s*;", text):
+        out[name] = [(m.group(1).replace(" ", ""), m.group(2)) for m in
+                     (re.fullmatch(r"\s*(?:const\s+)?(\w+\s*\*?)\s*(\w+)\s*", a) for a in args.split(","))]
+    return out
+
+
 STRUCTS = ("HgSmallMM", "HgGemmProblem", "HgPanelPack", "HgConvPanel", "HgPanelMulti", "HgPanelSum", "HbCollate")
 
 
@@ -152,6 +162,52 @@ def test_argument_validation_without_gpu():
     assert b"argument" in L.eqh_error_string(-1)
     with pytest.raises(hip.HipLibraryError):
         hip.check(-2, "demo")
+    # the 11 vis_* entries: width and extent are checked before any pointer is read, pointers before any launch
+    vis = vis_entry_points()
+    assert len(vis) == 11
+    held = ctypes.create_string_buffer(64)       # an address that is never read: every call below names a null pointer too
+    for name, params in vis.items():
+        fn = getattr(L, name)
+
+        def call(N, C=64, null=None, name=name, params=params, fn=fn):
+            args = []
+            for ctype, arg in params:
+                if ctype.endswith("*"):
+                    filled = null is not None and arg != null and arg != "stream"
+                    args.append(ctypes.addressof(held) if filled else None)
+                else:
+                    args.append({"N": N, "C": C, "cutoff": 5.0}[arg])
+            assert null is None or null in [a for _, a in params], null
+            return fn(*args)
+
+        assert call(0) == hip.EQH_OK, name
+        assert call(4) == hip.EQH_ERR_ARG, name
+        assert call(-1) == hip.EQH_ERR_ARG, name
+        assert call(2 ** 27) == hip.EQH_ERR_RANGE, name                  # 16 N = 2^31
+        assert call(2 ** 27 - 1) == hip.EQH_ERR_ARG, name                # the largest N in range: on to the pointers
+        for ctype, arg in params:
+            if ctype.endswith("*") and arg not in ("n_real", "stream"):  # (n_real may be null: an unpadded batch)
+                assert call(4, null=arg) == hip.EQH_ERR_ARG, (name, arg)
+        if name != "vis_radius_graph":
+            for C in (12, 520, 0, -8):
+                assert call(4, C) == hip.EQH_ERR_ARG, (name, C)
+                assert call(0, C) == hip.EQH_ERR_ARG, (name, C)
+            assert call(2 ** 27, 520) == hip.EQH_ERR_ARG, name
+            for C in (8, 72, 512):
+                assert call(0, C) == hip.EQH_OK, (name, C)
+
+
+def test_visnet_rejects_unsupported_widths():
+    from equihgnn_amd.visnet import ViS_MP, ViSNet
+
+    with pytest.raises(ValueError, match=r"hidden channels \(got 12\) must be evenly divisible by the number of "
+                                         r"attention heads \(got 8\)"):
+        ViS_MP(8, 12, 5.0)
+    with pytest.raises(ValueError, match=r"at most 512 hidden channels \(got 520\)"):
+        ViS_MP(8, 520, 5.0)
+    with pytest.raises(ValueError, match=r"at most 512 hidden channels \(got 520\)"):
+        ViSNet(hidden_channels=520, lmax=2, max_num_neighbors=16)
+    assert ViS_MP(8, 512, 5.0).head_dim == 64
 
 
 def test_no_cpu_fallback():

@@ -1,5 +1,6 @@
 """GPU: the three ViSNet wrappers against the golden vectors of the reference's own equihnn_visnet.py
 (tests/golden/make_golden_visnet.py), and each vis_* operator pair, forward and backward, against float64 torch."""
+import functools
 import math
 
 import numpy as np
@@ -119,11 +120,8 @@ def _check(op, ref, inputs, n_out, live_rows):
         assert float((b.grad.cpu().double() - ga).abs().max()) <= 2e-5 * scale + 1e-7, ("bwd", k)
 
 
-def _silu(t):
-    return torch.nn.functional.silu(t)
-
-
-@pytest.mark.parametrize("C", [64, 256])
+# 8: one channel per head, 56 idle lanes; 72: a partial second lane round; 128: ViSNet's default width; 512: all 8 rounds
+@pytest.mark.parametrize("C", [64, 256, 8, 72, 128, 320, 512])
 def test_operator_pairs_against_float64(C):
     from equihgnn_amd import ops
     g, src, dst, eid = _graph()
@@ -132,42 +130,18 @@ def test_operator_pairs_against_float64(C):
     sh = g.sh.cpu().double()
     live = torch.zeros(E, dtype=torch.bool)
     live[eid] = True
-    m = src != dst
-    D = C // 8
-
-    def nbr_ref(x, W):
-        return torch.zeros(N, C, dtype=x.dtype).index_add(0, dst[m], x[src[m]] * (W[eid[m]] * cut[eid[m]].unsqueeze(-1)))
-    _check(lambda x, W: ops.vis_neighbor_sum(x, W, g), nbr_ref, [_rand(N, C, seed=1), _rand(E, C, seed=2)], 1, live)
-
-    def eemb_ref(x, W):
-        f = torch.zeros(E, C, dtype=x.dtype)
-        return f.index_put((eid,), (x[dst] + x[src]) * W[eid])
-    _check(lambda x, W: ops.vis_edge_embed(x, W, g), eemb_ref, [_rand(N, C, seed=3), _rand(E, C, seed=4)], 1, live)
-
-    def attn_ref(q, k, v, dkr, dvr):
-        pre = (q[dst] * k[src] * _silu(dkr[eid])).view(-1, 8, D).sum(-1)
-        a = _silu(pre) * cut[eid].unsqueeze(-1)
-        u_e = ((v[src] * _silu(dvr[eid])).view(-1, 8, D) * a.unsqueeze(-1)).view(-1, C)
-        u = torch.zeros(E, C, dtype=q.dtype).index_put((eid,), u_e)
-        return u, torch.zeros(N, C, dtype=q.dtype).index_add(0, dst, u_e)
-    _check(lambda *t: ops.vis_attn(*t, g), attn_ref,
+    G = visnet_ref.EdgeList(N, src, dst, eid, cut, sh)
+    ref = {n: functools.partial(getattr(visnet_ref, n), G) for n in ("nbr_ref", "eemb_ref", "attn_ref", "vec_ref",
+                                                                      "eupd_ref")}
+    _check(lambda x, W: ops.vis_neighbor_sum(x, W, g), ref["nbr_ref"], [_rand(N, C, seed=1), _rand(E, C, seed=2)], 1,
+           live)
+    _check(lambda x, W: ops.vis_edge_embed(x, W, g), ref["eemb_ref"], [_rand(N, C, seed=3), _rand(E, C, seed=4)], 1,
+           live)
+    _check(lambda *t: ops.vis_attn(*t, g), ref["attn_ref"],
            [_rand(N, C, seed=5), _rand(N, C, seed=6), _rand(N, C, seed=7), _rand(E, C, seed=8), _rand(E, C, seed=9)],
            2, live)
-
-    def vec_ref(vec, sr):
-        s = _silu(sr[eid])
-        msg = vec[src] * s[:, :C].unsqueeze(1) + s[:, C:].unsqueeze(1) * sh[eid].unsqueeze(2)
-        return torch.zeros(N, 8, C, dtype=vec.dtype).index_add(0, dst, msg)
-    _check(lambda vec, sr: ops.vis_vec_msg(vec, sr, g), vec_ref, [_rand(N, 8, C, seed=10), _rand(E, 2 * C, seed=11)],
-           1, live)
-
-    def rej(a, d):
-        return a - (a * d.unsqueeze(2)).sum(dim=1, keepdim=True) * d.unsqueeze(2)
-
-    def eupd_ref(wt, ws, fr):
-        d = sh[eid]
-        df = _silu(fr[eid]) * (rej(wt[dst], d) * rej(ws[src], -d)).sum(1)
-        return torch.zeros(E, C, dtype=wt.dtype).index_put((eid,), df)
-    _check(lambda *t: ops.vis_edge_update(*t, g), eupd_ref,
+    _check(lambda vec, sr: ops.vis_vec_msg(vec, sr, g), ref["vec_ref"],
+           [_rand(N, 8, C, seed=10), _rand(E, 2 * C, seed=11)], 1, live)
+    _check(lambda *t: ops.vis_edge_update(*t, g), ref["eupd_ref"],
            [_rand(N, 8, C, seed=12), _rand(N, 8, C, seed=13), _rand(E, C, seed=14)], 1, live)
     assert math.isfinite(float(g.rbf.sum()))

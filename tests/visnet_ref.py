@@ -19,12 +19,16 @@ def radius_graph(pos, batch, r=CUTOFF, k=K, n_real=None):
     n_real = N if n_real is None else int(n_real)
     src, dst = [], []
     r2 = torch.tensor(r, dtype=torch.float32) * torch.tensor(r, dtype=torch.float32)
+    ordered = bool((b[1:] >= b[:-1]).all())             # a sorted batch vector: each molecule is one index range
+    if ordered:
+        lo = torch.searchsorted(b, b, right=False).tolist()
+        hi = torch.searchsorted(b, b, right=True).tolist()
     for i in range(N):
         if i >= n_real:
             src.append(i)
             dst.append(i)
             continue
-        same = torch.nonzero(b == b[i]).reshape(-1)
+        same = torch.arange(lo[i], hi[i]) if ordered else torch.nonzero(b == b[i]).reshape(-1)
         d = p[same] - p[i]
         d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
         keep = same[d2 < r2][:k]
@@ -44,9 +48,11 @@ def _sphere(v):
                         s3 / 2.0 * (z * z - x * x)], -1)
 
 
-def visnet(sd, z, pos, batch, prefix="", n_real=None, dtype=torch.float64):
-    """Per-atom output [N, C] of ViSNet(hidden_channels=C, lmax=2, max_num_neighbors=16) with the state dict ``sd``
-    (tensors that require grad are used as they are, so gradients flow back to them)."""
+def visnet(sd, z, pos, batch, prefix="", n_real=None, dtype=torch.float64, num_layers=6, with_repr=False, vec0=None):
+    """Per-atom output [N, C] of ViSNet(hidden_channels=C, lmax=2, max_num_neighbors=16, num_layers=num_layers) with the
+    state dict ``sd`` (tensors that require grad are used as they are, so gradients flow back to them).  ``with_repr``:
+    return (output, x, vec) with the representation model's pair as well.  ``vec0`` [N, 8, C]: the vector features the
+    first layer starts from (the model's own start is zero)."""
     P = lambda n: sd[prefix + n]
     rm = "representation_model."
     z = z.cpu()
@@ -87,9 +93,9 @@ def visnet(sd, z, pos, batch, prefix="", n_real=None, dtype=torch.float64):
     x = lin(torch.cat([x, xn], 1), ne + "combine")
     C = x.shape[1]
     D = C // 8
-    vec = torch.zeros(N, 8, C, dtype=dtype)
+    vec = torch.zeros(N, 8, C, dtype=dtype) if vec0 is None else vec0
     f = (x[dst] + x[src]) * lin(rbf, rm + "edge_embedding.edge_proj")
-    L = 6
+    L = num_layers
     for l in range(L):
         p = f"{rm}vis_mp_layers.{l}."
         xl = ln(x, p + "layernorm")
@@ -118,6 +124,7 @@ def visnet(sd, z, pos, batch, prefix="", n_real=None, dtype=torch.float64):
         x = x + dx
         vec = vec + dvec
     x = ln(x, rm + "out_norm")
+    x_repr = x
     v = vec
     for bb in range(2):
         p = f"output_model.output_network.{bb}."
@@ -127,7 +134,97 @@ def visnet(sd, z, pos, batch, prefix="", n_real=None, dtype=torch.float64):
         x, v = torch.split(h, C, dim=-1)
         v = v.unsqueeze(1) * v2
         x = silu(x)
-    return (x + v.sum() * 0) * P("std")
+    out = (x + v.sum() * 0) * P("std")
+    return (out, x_repr, vec) if with_repr else out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the five vis_* operators on plain torch, over the kept edges of a slot table
+# ----------------------------------------------------------------------------------------------------------------------
+class EdgeList:
+    """The kept edges of a [N, 16] slot table, in edge-id order: ``src`` / ``dst`` [n] (atom ids), ``eid`` [n] (slot ids
+    16 i + s), and the per-slot ``cut`` [16 N] and ``sh`` [16 N, 8] the operators read."""
+
+    def __init__(self, N, src, dst, eid, cut, sh):
+        self.N, self.E, self.src, self.dst, self.eid, self.cut, self.sh = int(N), K * int(N), src, dst, eid, cut, sh
+
+    def rows(self, a0, a1):
+        """The edges of atoms [a0, a1), a range of whole molecules, renumbered from 0."""
+        m = (self.dst >= a0) & (self.dst < a1)
+        return EdgeList(a1 - a0, self.src[m] - a0, self.dst[m] - a0, self.eid[m] - K * a0, self.cut[K * a0:K * a1],
+                        self.sh[K * a0:K * a1])
+
+    def to(self, dtype):
+        return EdgeList(self.N, self.src, self.dst, self.eid, self.cut.to(dtype), self.sh.to(dtype))
+
+
+class _AbsSilu(torch.autograd.Function):
+    """|silu(t)| forward; backward the two terms of silu'(t) = s + t s (1 - s), s = sigmoid(t), by their absolute values
+    (they cancel at t = -1.28)."""
+
+    @staticmethod
+    def forward(ctx, t):
+        ctx.save_for_backward(t)
+        return torch.nn.functional.silu(t).abs()
+
+    @staticmethod
+    def backward(ctx, g):
+        (t,) = ctx.saved_tensors
+        s = torch.sigmoid(t)
+        return g * (s * (1 + t.abs() * (1 - s)))
+
+
+def _act(t, magnitude):
+    return _AbsSilu.apply(t) if magnitude else torch.nn.functional.silu(t)
+
+
+# Each reference takes ``magnitude``: with it, every term enters by its absolute value -- an activation as |silu|, with
+# |silu'| as its derivative, a harmonic as |sh|, a difference as a sum -- so that on inputs whose linear operands (q, k,
+# v, vec, wt, ws, x, W and the upstream gradients) were made non-negative by the caller, an output element, and a
+# gradient element after backward, is the sum of the absolute values of the terms that make up the plain element: the
+# scale A of a per-element rounding bound.
+def nbr_ref(G, x, W, magnitude=False):
+    m = G.src != G.dst
+    C = x.shape[1]
+    return torch.zeros(G.N, C, dtype=x.dtype).index_add(
+        0, G.dst[m], x[G.src[m]] * (W[G.eid[m]] * G.cut[G.eid[m]].unsqueeze(-1)))
+
+
+def eemb_ref(G, x, W, magnitude=False):
+    f = torch.zeros(G.E, x.shape[1], dtype=x.dtype)
+    return f.index_put((G.eid,), (x[G.dst] + x[G.src]) * W[G.eid])
+
+
+def attn_ref(G, q, k, v, dkr, dvr, magnitude=False):
+    C = q.shape[1]
+    D = C // 8
+    src, dst, eid = G.src, G.dst, G.eid
+    pre = (q[dst] * k[src] * _act(dkr[eid], magnitude)).view(-1, 8, D).sum(-1)
+    a = _act(pre, magnitude) * G.cut[eid].unsqueeze(-1)
+    u_e = ((v[src] * _act(dvr[eid], magnitude)).view(-1, 8, D) * a.unsqueeze(-1)).view(-1, C)
+    u = torch.zeros(G.E, C, dtype=q.dtype).index_put((eid,), u_e)
+    return u, torch.zeros(G.N, C, dtype=q.dtype).index_add(0, dst, u_e)
+
+
+def vec_ref(G, vec, sr, magnitude=False):
+    C = vec.shape[2]
+    sh = G.sh.abs() if magnitude else G.sh
+    s = _act(sr[G.eid], magnitude)
+    msg = vec[G.src] * s[:, :C].unsqueeze(1) + s[:, C:].unsqueeze(1) * sh[G.eid].unsqueeze(2)
+    return torch.zeros(G.N, 8, C, dtype=vec.dtype).index_add(0, G.dst, msg)
+
+
+def eupd_ref(G, wt, ws, fr, magnitude=False):
+    C = wt.shape[2]
+    sign = 1.0 if magnitude else -1.0
+
+    def rej(a, d):
+        return a + sign * (a * d.unsqueeze(2)).sum(dim=1, keepdim=True) * d.unsqueeze(2)
+
+    d = G.sh[G.eid]
+    d, nd = (d.abs(), d.abs()) if magnitude else (d, -d)
+    df = _act(fr[G.eid], magnitude) * (rej(wt[G.dst], d) * rej(ws[G.src], nd)).sum(1)
+    return torch.zeros(G.E, C, dtype=wt.dtype).index_put((G.eid,), df)
 
 
 def restore_visnet_buffers(model):
