@@ -10,7 +10,9 @@
 // reference is never built.  d Wv / d w leave through per-workgroup slabs and the fixed-order reducer.
 #include <float.h>
 
+#include "act.h"
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -20,30 +22,13 @@ constexpr int AP_K = 16;     // neighbour slots
 constexpr int AP_V = 48;     // value channels
 constexpr int AP_F = 4;      // logit features
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16(float v) {
-    v += dpp_move<0xB1>(v);
-    v += dpp_move<0x4E>(v);
-    v += dpp_move<0x124>(v);
-    v += dpp_move<0x128>(v);
-    return v;
-}
-__device__ __forceinline__ float bcast(float v, int j) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v = row16(v);
+// wave.h's wave_sum (the same additions in the same order) spelled through bcast, for the four closing sums of
+// k_attn_pool_bwd only: with the shared spelling the compiler packs their scalar adds into other v_pk_add_f32 pairs,
+// and the move of the primitives into headers was to leave every kernel's instructions as they were.
+__device__ __forceinline__ float ap_wave_sum(float v) {
+    v = row16_sum(v);
     return (bcast(v, 0) + bcast(v, 16)) + (bcast(v, 32) + bcast(v, 48));
 }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 __device__ __forceinline__ const float* slot_row(const float* __restrict__ me, const float* __restrict__ edge, int64_t n,
                                                  int s, int D) {
@@ -158,7 +143,7 @@ k_attn_pool_bwd(const float* __restrict__ me, const float* __restrict__ edge, co
 #pragma unroll
         for (int c = 0; c < AP_V; ++c) mine[lane * AP_V + c] = dW[c];
     }
-    const float sx = wave_sum(dw.x), sy = wave_sum(dw.y), sz = wave_sum(dw.z), sw = wave_sum(dw.w);
+    const float sx = ap_wave_sum(dw.x), sy = ap_wave_sum(dw.y), sz = ap_wave_sum(dw.z), sw = ap_wave_sum(dw.w);
     if (lane == 0) { mine[AP_V * AP_V] = sx; mine[AP_V * AP_V + 1] = sy; mine[AP_V * AP_V + 2] = sz; mine[AP_V * AP_V + 3] = sw; }
     __syncthreads();
     float* __restrict__ sl = slab + (int64_t)blockIdx.x * (AP_V * AP_V + AP_F);

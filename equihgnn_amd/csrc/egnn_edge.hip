@@ -27,29 +27,19 @@
 // third kernel in block order, so every result is bitwise reproducible.
 #include <cstdlib>
 
+#include "act.h"
 #include "common.h"
 #include "bf16x3.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KNB = 16;    // neighbours per node
 constexpr int MDIM = 16;   // m_dim
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// sigmoid via v_exp_f32 / v_rcp_f32 (each ~1 ulp); silu(x) = x * sigmoid(x)
-__device__ __forceinline__ float sigmoid_fast(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
-__device__ __forceinline__ float silu_fast(float x) { return x * sigmoid_fast(x); }
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// the same silu on two values with the non-transcendental steps packed
+// act.h's silu_fast on two values with the non-transcendental steps packed
 __device__ __forceinline__ f32x2 silu_fast2(f32x2 x) {
     const f32x2 t = x * f32x2{-1.442695041f, -1.442695041f};
     const f32x2 d = f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + f32x2{1.0f, 1.0f};
@@ -296,7 +286,6 @@ k_edge_fwd(const float* __restrict__ ab, const float* __restrict__ wd, const flo
 // are split ONCE at kernel start and stay in registers; B rows / the A row go row-contiguously through a private LDS tile
 // into MFMA operand order, as above (lane (j = lane & 15, kg = lane >> 4) multiplies units 8 kg .. 8 kg + 7 of neighbour j).
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int F2_SPLIT = 4;                              // wavefronts per node
 constexpr int F2_LD = 32 + 4;                            // floats per staged row (32 hidden units + pad)

@@ -8,13 +8,15 @@
 // stored -- with the seed in device memory (a fresh draw per launch, also under hipGraph replay).
 #include <cstdlib>
 
+#include "act.h"
 #include "common.h"
 #include "drop_hash.h"
+#include "row.h"
+#include "wave.h"
 
 namespace {
 
 // (dropout decisions: drop_hash.h -- shared with the fused fc2 epilogue of gemm_x6.hip)
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 __global__ void __launch_bounds__(256)
 k_swiglu_drop_fwd(const float* __restrict__ pre, int64_t R, int H, const int64_t* __restrict__ seed_ptr,
@@ -330,20 +332,6 @@ namespace {
 constexpr int FP_THREADS = 256;
 constexpr int FP_WAVES = FP_THREADS / 64;
 
-template <int CTRL>
-__device__ __forceinline__ float fp_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float fp_wave_sum(float v) {
-    v += fp_dpp<0xB1>(v);
-    v += fp_dpp<0x4E>(v);
-    v += fp_dpp<0x124>(v);
-    v += fp_dpp<0x128>(v);
-    const int b = __float_as_int(v);
-    return (__int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16))) +
-           (__int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48)));
-}
-
 __device__ __forceinline__ float4 f4_combo(const float4& t0, const float4& t1, const float4& t2, const float4& b, int f) {
     const float s0 = (f & 4) ? 1.f : -1.f, s1 = (f & 2) ? 1.f : -1.f, s2 = (f & 1) ? 1.f : -1.f;
     return make_float4(fmaf(s0, t0.x, fmaf(s1, t1.x, fmaf(s2, t2.x, b.x))), fmaf(s0, t0.y, fmaf(s1, t1.y, fmaf(s2, t2.y, b.y))),
@@ -397,9 +385,9 @@ k_frame_pre_bwd(const float* __restrict__ y, const float* __restrict__ w3, const
             f4_fma(r2, g[f], (f & 1) ? 1.f : -1.f);
         }
         *reinterpret_cast<float4*>(dbase + e * H + h) = sb;
-        const float d0 = fp_wave_sum((r0.x * w0.x + r0.y * w0.y) + (r0.z * w0.z + r0.w * w0.w));
-        const float d1 = fp_wave_sum((r1.x * w1.x + r1.y * w1.y) + (r1.z * w1.z + r1.w * w1.w));
-        const float d2 = fp_wave_sum((r2.x * w2.x + r2.y * w2.y) + (r2.z * w2.z + r2.w * w2.w));
+        const float d0 = wave_sum((r0.x * w0.x + r0.y * w0.y) + (r0.z * w0.z + r0.w * w0.w));
+        const float d1 = wave_sum((r1.x * w1.x + r1.y * w1.y) + (r1.z * w1.z + r1.w * w1.w));
+        const float d2 = wave_sum((r2.x * w2.x + r2.y * w2.y) + (r2.z * w2.z + r2.w * w2.w));
         if (lane == 0) { dy[e * 3] = d0; dy[e * 3 + 1] = d1; dy[e * 3 + 2] = d2; }
         const float y0 = y[e * 3], y1 = y[e * 3 + 1], y2 = y[e * 3 + 2];
         f4_fma(a0, r0, y0);
@@ -495,11 +483,11 @@ k_frame_hidden_fwd(const float* __restrict__ y, const float* __restrict__ w3, co
             v0[f] = h0; v1[f] = h1;
         }
 #pragma unroll
-        for (int f = 0; f < 8; ++f) mu[f] = fp_wave_sum(v0[f] + v1[f]) * (1.0f / 128.0f);
+        for (int f = 0; f < 8; ++f) mu[f] = wave_sum(v0[f] + v1[f]) * (1.0f / 128.0f);
 #pragma unroll
         for (int f = 0; f < 8; ++f) {
             const float d0 = v0[f] - mu[f], d1 = v1[f] - mu[f];
-            const float r = 1.0f / sqrtf(fp_wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f) + eps);
+            const float r = 1.0f / sqrtf(wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f) + eps);
             float2 o;
             o.x = fmaf(L.g0, d0 * r, L.be0);
             o.y = fmaf(L.g1, d1 * r, L.be1);
@@ -566,15 +554,15 @@ k_frame_hidden_bwd(const float* __restrict__ y, const float* __restrict__ w3, co
                 keep_scale2(seed, idx, threshold, inv_keep, k0, k1);
             }
             const float h0 = s0 * b0 * k0, h1 = s1 * b1 * k1;
-            const float mu = fp_wave_sum(h0 + h1) * (1.0f / 128.0f);
+            const float mu = wave_sum(h0 + h1) * (1.0f / 128.0f);
             const float d0 = h0 - mu, d1 = h1 - mu;
-            const float rstd = 1.0f / sqrtf(fp_wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f) + eps);
+            const float rstd = 1.0f / sqrtf(wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f) + eps);
             const float x0 = d0 * rstd, x1 = d1 * rstd;
             ab0 += g[f].x; ab1 += g[f].y;
             ag0 = fmaf(g[f].x, x0, ag0); ag1 = fmaf(g[f].y, x1, ag1);
             const float q0 = g[f].x * L.g0, q1 = g[f].y * L.g1;
-            const float m1 = fp_wave_sum(q0 + q1) * (1.0f / 128.0f);
-            const float m2 = fp_wave_sum(q0 * x0 + q1 * x1) * (1.0f / 128.0f);
+            const float m1 = wave_sum(q0 + q1) * (1.0f / 128.0f);
+            const float m2 = wave_sum(q0 * x0 + q1 * x1) * (1.0f / 128.0f);
             const float dh0 = rstd * (q0 - m1 - x0 * m2) * k0, dh1 = rstd * (q1 - m1 - x1 * m2) * k1;
             const float dp[4] = {dh0 * b0 * fmaf(s0, 1.0f - sg0, sg0), dh1 * b1 * fmaf(s1, 1.0f - sg1, sg1), dh0 * s0, dh1 * s1};
             const float sg[3] = {(f & 4) ? 1.f : -1.f, (f & 2) ? 1.f : -1.f, (f & 1) ? 1.f : -1.f};
@@ -595,13 +583,13 @@ k_frame_hidden_bwd(const float* __restrict__ y, const float* __restrict__ w3, co
                 adx[c] = fmaf(sb[c], ex, adx[c]);
             }
             if (extra) {
-                const float de = fp_wave_sum((sb[0] * wxv[0] + sb[1] * wxv[1]) + (sb[2] * wxv[2] + sb[3] * wxv[3]));
+                const float de = wave_sum((sb[0] * wxv[0] + sb[1] * wxv[1]) + (sb[2] * wxv[2] + sb[3] * wxv[3]));
                 if (lane == 0) dextra[e] = de;
             }
         }
-        const float dd0 = fp_wave_sum((r[0][0] * L.wa0[0] + r[1][0] * L.wa1[0]) + (r[2][0] * L.wb0[0] + r[3][0] * L.wb1[0]));
-        const float dd1 = fp_wave_sum((r[0][1] * L.wa0[1] + r[1][1] * L.wa1[1]) + (r[2][1] * L.wb0[1] + r[3][1] * L.wb1[1]));
-        const float dd2 = fp_wave_sum((r[0][2] * L.wa0[2] + r[1][2] * L.wa1[2]) + (r[2][2] * L.wb0[2] + r[3][2] * L.wb1[2]));
+        const float dd0 = wave_sum((r[0][0] * L.wa0[0] + r[1][0] * L.wa1[0]) + (r[2][0] * L.wb0[0] + r[3][0] * L.wb1[0]));
+        const float dd1 = wave_sum((r[0][1] * L.wa0[1] + r[1][1] * L.wa1[1]) + (r[2][1] * L.wb0[1] + r[3][1] * L.wb1[1]));
+        const float dd2 = wave_sum((r[0][2] * L.wa0[2] + r[1][2] * L.wa1[2]) + (r[2][2] * L.wb0[2] + r[3][2] * L.wb1[2]));
         if (lane == 0) { dy[e * 3] = dd0; dy[e * 3 + 1] = dd1; dy[e * 3 + 2] = dd2; }
         const float yv[3] = {y0, y1, y2};
 #pragma unroll
@@ -972,24 +960,12 @@ constexpr int RD_THREADS = 256;
 constexpr int RD_WAVES = RD_THREADS / 64;
 
 template <int NV>
-struct RdRow {
-    float4 v[NV];
-};
-template <int NV>
-__device__ __forceinline__ void rd_load(const float* __restrict__ p, int C, int lane, RdRow<NV>& r) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        r.v[i] = (c < C) ? *reinterpret_cast<const float4*>(p + c) : f4_zero();
-    }
-}
-template <int NV>
-__device__ __forceinline__ float rd_dot(const RdRow<NV>& a, const RdRow<NV>& b) {
+__device__ __forceinline__ float rd_dot(const Row<NV>& a, const Row<NV>& b) {
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
         s += (a.v[i].x * b.v[i].x + a.v[i].y * b.v[i].y) + (a.v[i].z * b.v[i].z + a.v[i].w * b.v[i].w);
-    return fp_wave_sum(s);
+    return wave_sum(s);
 }
 
 template <int NV, int J>
@@ -997,12 +973,12 @@ __global__ void __launch_bounds__(RD_THREADS)
 k_rowdot_fwd(const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias, int64_t R, int C,
              float* __restrict__ y) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    RdRow<NV> u[J];
+    Row<NV> u[J];
 #pragma unroll
-    for (int j = 0; j < J; ++j) rd_load<NV>(U + (int64_t)j * C, C, lane, u[j]);
+    for (int j = 0; j < J; ++j) load_row<NV>(U + (int64_t)j * C, 0, C, lane, u[j]);
     for (int64_t r = (int64_t)blockIdx.x * RD_WAVES + wave; r < R; r += (int64_t)gridDim.x * RD_WAVES) {
-        RdRow<NV> xr;
-        rd_load<NV>(x + r * C, C, lane, xr);
+        Row<NV> xr;
+        load_row<NV>(x + r * C, 0, C, lane, xr);
         float o[J];
 #pragma unroll
         for (int j = 0; j < J; ++j) o[j] = rd_dot<NV>(xr, u[j]) + (bias ? bias[j] : 0.f);
@@ -1019,17 +995,17 @@ k_rowdot_bwd(const float* __restrict__ x, const float* __restrict__ U, const flo
              const float* __restrict__ dx_add, int64_t R, int C, float* __restrict__ dx, float* __restrict__ slab) {
     __shared__ float4 s_red[RD_THREADS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    RdRow<NV> u[J], au[J];
+    Row<NV> u[J], au[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) {
-        rd_load<NV>(U + (int64_t)j * C, C, lane, u[j]);
+        load_row<NV>(U + (int64_t)j * C, 0, C, lane, u[j]);
 #pragma unroll
         for (int i = 0; i < NV; ++i) au[j].v[i] = f4_zero();
     }
     for (int64_t r = (int64_t)blockIdx.x * RD_WAVES + wave; r < R; r += (int64_t)gridDim.x * RD_WAVES) {
-        RdRow<NV> xr, acc;
-        rd_load<NV>(x + r * C, C, lane, xr);
-        if (dx_add) rd_load<NV>(dx_add + r * C, C, lane, acc);
+        Row<NV> xr, acc;
+        load_row<NV>(x + r * C, 0, C, lane, xr);
+        if (dx_add) load_row<NV>(dx_add + r * C, 0, C, lane, acc);
         else {
 #pragma unroll
             for (int i = 0; i < NV; ++i) acc.v[i] = f4_zero();
@@ -1068,7 +1044,7 @@ k_rowdot_bwd(const float* __restrict__ x, const float* __restrict__ U, const flo
 }
 
 template <int NV>
-__device__ __forceinline__ void rd_dropout(RdRow<NV>& xr, const DropKey& seed, int64_t r, int C, int lane, uint32_t threshold,
+__device__ __forceinline__ void rd_dropout(Row<NV>& xr, const DropKey& seed, int64_t r, int C, int lane, uint32_t threshold,
                                            float inv_keep) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -1084,13 +1060,13 @@ k_gate_fwd(const float* __restrict__ x, const float* __restrict__ w, const float
            int64_t R, int C, const int64_t* __restrict__ seed_ptr, uint32_t threshold, float inv_keep, float* __restrict__ out) {
     const DropKey seed = drop_key(threshold ? (uint64_t)*seed_ptr : 0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    RdRow<NV> wr;
-    rd_load<NV>(w, C, lane, wr);
+    Row<NV> wr;
+    load_row<NV>(w, 0, C, lane, wr);
     const float b0 = b[0];
     for (int64_t r = (int64_t)blockIdx.x * RD_WAVES + wave; r < R; r += (int64_t)gridDim.x * RD_WAVES) {
-        RdRow<NV> xr, rr;
-        rd_load<NV>(x + r * C, C, lane, xr);
-        if (res) rd_load<NV>(res + r * C, C, lane, rr);
+        Row<NV> xr, rr;
+        load_row<NV>(x + r * C, 0, C, lane, xr);
+        if (res) load_row<NV>(res + r * C, 0, C, lane, rr);
         if (threshold) rd_dropout<NV>(xr, seed, r, C, lane, threshold, inv_keep);
         const float g = sigmoid_fast(rd_dot<NV>(xr, wr) + b0);
 #pragma unroll
@@ -1113,21 +1089,21 @@ k_gate_bwd(const float* __restrict__ x, const float* __restrict__ w, const float
     __shared__ float s_b[RD_WAVES];
     const DropKey seed = drop_key(threshold ? (uint64_t)*seed_ptr : 0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    RdRow<NV> wr, aw, ax;          // ax: column sums of dx (slab_dx given) = the bias gradient of the Linear that produced x
-    rd_load<NV>(w, C, lane, wr);
+    Row<NV> wr, aw, ax;          // ax: column sums of dx (slab_dx given) = the bias gradient of the Linear that produced x
+    load_row<NV>(w, 0, C, lane, wr);
 #pragma unroll
     for (int i = 0; i < NV; ++i) aw.v[i] = ax.v[i] = f4_zero();
     float ab = 0.f;
     const float b0 = b[0];
     for (int64_t r = (int64_t)blockIdx.x * RD_WAVES + wave; r < R; r += (int64_t)gridDim.x * RD_WAVES) {
-        RdRow<NV> xr, dr;
-        rd_load<NV>(x + r * C, C, lane, xr);
-        rd_load<NV>(dout + r * C, C, lane, dr);
+        Row<NV> xr, dr;
+        load_row<NV>(x + r * C, 0, C, lane, xr);
+        load_row<NV>(dout + r * C, 0, C, lane, dr);
         if (threshold) rd_dropout<NV>(xr, seed, r, C, lane, threshold, inv_keep);
         const float g = sigmoid_fast(rd_dot<NV>(xr, wr) + b0);
         const float coef = rd_dot<NV>(dr, xr) * g * (1.0f - g);      // d loss / d (xd . w + b)
         ab += coef;
-        RdRow<NV> dxd;
+        Row<NV> dxd;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             dxd.v[i] = make_float4(fmaf(dr.v[i].x, g, coef * wr.v[i].x), fmaf(dr.v[i].y, g, coef * wr.v[i].y),
@@ -1185,13 +1161,6 @@ inline int rd_check(int64_t R, int32_t C) {
     if ((C & 3) || C > 1024) return EQH_ERR_ALIGN;
     return EQH_OK;
 }
-template <typename F>
-int rd_dispatch(int C, F&& f) {
-    if (C <= 256) return f(std::integral_constant<int, 1>{});
-    if (C <= 512) return f(std::integral_constant<int, 2>{});
-    return f(std::integral_constant<int, 4>{});
-}
-
 }  // namespace
 
 extern "C" int faf_rowdot_fwd(const float* x, const float* U, const float* bias, int64_t R, int32_t C, int32_t J, float* y,
@@ -1204,7 +1173,7 @@ extern "C" int faf_rowdot_fwd(const float* x, const float* U, const float* bias,
     if (!eqh_aligned16(x) || !eqh_aligned16(U)) return EQH_ERR_ALIGN;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const dim3 grid(eqh_grid_for(R, RD_WAVES, 8192));
-    return rd_dispatch(C, [&](auto nv) {
+    return dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         switch (J) {
             case 1: hipLaunchKernelGGL((k_rowdot_fwd<NV, 1>), grid, dim3(RD_THREADS), 0, stream, x, U, bias, R, (int)C, y); break;
@@ -1237,7 +1206,7 @@ extern "C" int faf_rowdot_bwd(const float* x, const float* U, const float* dy, c
     if (workspace_bytes < faf_rowdot_bwd_workspace_bytes(R, C, J)) return EQH_ERR_ARG;
     const int blocks = rd_blocks(R);
     float* slab = static_cast<float*>(workspace);
-    return rd_dispatch(C, [&](auto nv) {
+    return dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         switch (J) {
             case 1: hipLaunchKernelGGL((k_rowdot_bwd<NV, 1>), dim3(blocks), dim3(RD_THREADS), 0, stream, x, U, dy, dx_add, R, (int)C, dx, slab); break;
@@ -1259,7 +1228,7 @@ extern "C" int faf_gate_fwd(const float* x, const float* w, const float* b, cons
     if (!x || !w || !b || !out || (p > 0.f && !seed)) return EQH_ERR_ARG;
     if (!eqh_aligned16(x) || !eqh_aligned16(w) || !eqh_aligned16(res) || !eqh_aligned16(out)) return EQH_ERR_ALIGN;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return rd_dispatch(C, [&](auto nv) {
+    return dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         hipLaunchKernelGGL((k_gate_fwd<NV>), dim3(eqh_grid_for(R, RD_WAVES, 8192)), dim3(RD_THREADS), 0, stream, x, w, b, res, R,
                            (int)C, seed, ew_threshold(p), drop_inv_keep(p), out);
@@ -1297,7 +1266,7 @@ extern "C" int faf_gate_bwd(const float* x, const float* w, const float* b, cons
     const int blocks = rd_blocks(R);
     float* slab = static_cast<float*>(workspace);
     float* slab_dx = dx_colsum ? slab + (size_t)blocks * (C + 4) + 4 : nullptr;
-    return rd_dispatch(C, [&](auto nv) {
+    return dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         hipLaunchKernelGGL((k_gate_bwd<NV>), dim3(blocks), dim3(RD_THREADS), 0, stream, x, w, b, dout, R, (int)C, seed,
                            ew_threshold(p), drop_inv_keep(p), dx, slab, slab_dx);
@@ -1358,9 +1327,9 @@ k_edge_hidden_fwd(const float* __restrict__ A, const float* __restrict__ B, cons
                 keep_scale2(seed, idx, threshold, inv_keep, kk0, kk1);      // (idx is even: one hash for the pair)
                 h0 *= kk0; h1 *= kk1;
             }
-            const float mu = fp_wave_sum(h0 + h1) * (1.0f / 128.0f);
+            const float mu = wave_sum(h0 + h1) * (1.0f / 128.0f);
             const float d0 = h0 - mu, d1 = h1 - mu;
-            const float rstd = 1.0f / sqrtf(fp_wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f) + eps);
+            const float rstd = 1.0f / sqrtf(wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f) + eps);
             *reinterpret_cast<float2*>(out + r * 128 + 2 * lane) = make_float2(fmaf(g0, d0 * rstd, be0), fmaf(g1, d1 * rstd, be1));
         }
     }
@@ -1402,15 +1371,15 @@ k_edge_hidden_bwd(const float* __restrict__ A, const float* __restrict__ B, cons
                 keep_scale2(seed, idx, threshold, inv_keep, k0, k1);
             }
             const float h0 = s0 * b0 * k0, h1 = s1 * b1 * k1;
-            const float mu = fp_wave_sum(h0 + h1) * (1.0f / 128.0f);
+            const float mu = wave_sum(h0 + h1) * (1.0f / 128.0f);
             const float d0 = h0 - mu, d1 = h1 - mu;
-            const float rstd = 1.0f / sqrtf(fp_wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f) + eps);
+            const float rstd = 1.0f / sqrtf(wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f) + eps);
             const float x0 = d0 * rstd, x1 = d1 * rstd;
             ab0 += g.x; ab1 += g.y;
             ag0 = fmaf(g.x, x0, ag0); ag1 = fmaf(g.y, x1, ag1);
             const float q0 = g.x * g0, q1 = g.y * g1;
-            const float m1 = fp_wave_sum(q0 + q1) * (1.0f / 128.0f);
-            const float m2 = fp_wave_sum(q0 * x0 + q1 * x1) * (1.0f / 128.0f);
+            const float m1 = wave_sum(q0 + q1) * (1.0f / 128.0f);
+            const float m2 = wave_sum(q0 * x0 + q1 * x1) * (1.0f / 128.0f);
             const float dh0 = rstd * (q0 - m1 - x0 * m2) * k0, dh1 = rstd * (q1 - m1 - x1 * m2) * k1;
             const float da0 = dh0 * b0 * fmaf(s0, 1.0f - sg0, sg0), da1 = dh1 * b1 * fmaf(s1, 1.0f - sg1, sg1);
             const float db0 = dh0 * s0, db1 = dh1 * s1;

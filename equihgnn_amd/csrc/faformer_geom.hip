@@ -10,6 +10,7 @@
 //   k_cloud_frame_*      y = (x - c m) V, V = eigenvectors of the masked covariance about c (no gradient through V, :98-99)
 //   k_edge_frame_*       the same per atom over its K <= 16 neighbour offsets x_i - x_j, with |x_i - x_j|^2 (:357-372)
 //   k_attn_logits_*      logits a_q[i] + a_k[j] + l_e, radius mask, softmax over the K slots, dropout (:483-496)
+#include "act.h"
 #include "common.h"
 #include "drop_hash.h"
 #include "eigh3.h"
@@ -19,8 +20,6 @@ namespace {
 constexpr int GM_THREADS = 256;
 constexpr int GM_MAXP = 128;     // workgroups of a moments pass = rows of its partial table (<= GM_THREADS, sum_partials)
 constexpr int GM_NQ = 10;        // weight, weight * a (3), weight * a a^T upper triangle (6)
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // partial[b][q], b = blockIdx.x.  w_n = (m ? (m[n] > 0) : 1) * (s ? (s_sigmoid ? sigmoid(s[n]) : s[n]) : 1)
 __global__ void __launch_bounds__(GM_THREADS)
@@ -34,7 +33,7 @@ k_moments(const float* __restrict__ a, const float* __restrict__ m, const float*
     for (int64_t n = (int64_t)blockIdx.x * GM_THREADS + threadIdx.x; n < N; n += stride) {
         if (m && !(m[n] > 0.f)) continue;
         double w = 1.0;
-        if (s) w = s_sigmoid ? (double)sigmoid_f(s[n]) : (double)s[n];
+        if (s) w = s_sigmoid ? (double)sigmoid_exact(s[n]) : (double)s[n];
         const double x = a[n * 3 + 0], y = a[n * 3 + 1], z = a[n * 3 + 2];
         acc[0] += w;
         acc[1] += w * x; acc[2] += w * y; acc[3] += w * z;
@@ -97,7 +96,7 @@ k_centre_mix_fwd(const float* __restrict__ geo, const float* __restrict__ logit,
     if (blockIdx.x == 0 && threadIdx.x == 0) { aux[0] = c0; aux[1] = c1; aux[2] = c2; aux[3] = (float)cnt; }
     const int64_t n = (int64_t)blockIdx.x * GM_THREADS + threadIdx.x;
     if (n >= N) return;
-    const float g = sigmoid_f(logit[n]), h = 1.0f - g;
+    const float g = sigmoid_exact(logit[n]), h = 1.0f - g;
     out[n * 3 + 0] = c0 * g + geo[n * 3 + 0] * h;
     out[n * 3 + 1] = c1 * g + geo[n * 3 + 1] * h;
     out[n * 3 + 2] = c2 * g + geo[n * 3 + 2] * h;
@@ -114,7 +113,7 @@ k_centre_mix_bwd(const float* __restrict__ dout, const float* __restrict__ geo, 
     if (n >= N) return;
     const float cnt = aux[3];
     const float share = (m && !(m[n] > 0.f)) ? 0.f : 1.0f / cnt;
-    const float g = sigmoid_f(logit[n]), h = 1.0f - g;
+    const float g = sigmoid_exact(logit[n]), h = 1.0f - g;
     float dg = 0.f;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {

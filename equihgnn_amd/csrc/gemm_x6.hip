@@ -38,15 +38,13 @@
 #include "common.h"
 #include "bf16x3.h"
 #include "drop_hash.h"
+#include "mfma.h"
 
 #ifdef GX_ABLATE_SPLIT   // diagnostic build: the stagers store raw bits (no split arithmetic); results are garbage
 #define split_pair(x, y, a, b, c) ((a) = __float_as_uint(x), (b) = __float_as_uint(y), (c) = (a) ^ (b))
 #endif
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int GX_STAGERS = 512;      // eight wavefronts load, split and stage (two groups of four), behind the multiplying wavefronts (2 x 2; 2 x 4 for the 128 x 256 tile)
 constexpr int GX_BK = 32;

@@ -738,13 +738,6 @@ int check(int64_t rows, int C) {
     return EQH_OK;
 }
 
-template <typename F>
-int dispatch_nv(int C, F&& f) {
-    if (C <= 256) return f(std::integral_constant<int, 1>{});
-    if (C <= 512) return f(std::integral_constant<int, 2>{});
-    return f(std::integral_constant<int, 4>{});
-}
-
 }  // namespace
 
 extern "C" int hg_incidence_ln_reduce_fwd(const float* pa, const float* qb, const int32_t* ia,

@@ -183,13 +183,10 @@ inline int lr_blocks(int64_t rows) { return eqh_grid_for(rows, LR_WAVES * 4, row
 
 template <typename F>
 int lr_dispatch(int C, int J, F&& f) {
-    auto with_j = [&](auto nv) {
+    return dispatch_nv(C, [&](auto nv) {
         if (J == 1) return f(nv, std::integral_constant<int, 1>{});
         return f(nv, std::integral_constant<int, 2>{});
-    };
-    if (C <= 256) return with_j(std::integral_constant<int, 1>{});
-    if (C <= 512) return with_j(std::integral_constant<int, 2>{});
-    return with_j(std::integral_constant<int, 4>{});
+    });
 }
 
 inline int lr_check(int64_t R, int32_t C, int32_t J) {

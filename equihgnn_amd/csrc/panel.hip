@@ -30,14 +30,13 @@
 #include <cstdlib>
 #include <initializer_list>
 
+#include "act.h"
 #include "common.h"
 #include "bf16x3.h"
+#include "mfma.h"
 #include "rowln.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int PN_ROWS = 32;        // rows per panel = one MFMA row tile
 constexpr int PN_STG_LD = 260;     // floats per staged row: 256 + 4 keeps the accumulators' 16-byte stores conflict-free
@@ -1349,9 +1348,10 @@ PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
 // goes through the staging tile in two halves of C columns; the C + 16 columns of dnode_in are nine column tiles (the image is
 // zero-padded to C + 32).
 // =============================================================================================================================
-__device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
+// SiLU as ONE division, x / (1 + e^-x): not x * sigmoid_exact(x), which rounds twice
+__device__ __forceinline__ float silu_div(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float silu_grad_f(float x) {
-    const float sg = 1.0f / (1.0f + expf(-x));
+    const float sg = sigmoid_exact(x);
     return sg * (1.0f + x * (1.0f - sg));
 }
 
@@ -1420,7 +1420,7 @@ PN_KERNEL(NW) k_node_f(const ConvPanelArgs p) {
         if (P.live) rt_store<C, NW>(t, p.out1 + half * C, 2 * C, P.row, P.c4);
 #pragma unroll
         for (int j = 0; j < S::NJ; ++j)
-            t.v[j] = make_float4(silu_f(t.v[j].x), silu_f(t.v[j].y), silu_f(t.v[j].z), silu_f(t.v[j].w));
+            t.v[j] = make_float4(silu_div(t.v[j].x), silu_div(t.v[j].y), silu_div(t.v[j].z), silu_div(t.v[j].w));
         if (P.live) rt_store<C, NW>(t, p.out2 + half * C, 2 * C, P.row, P.c4);
         rt_a_put<C, NW, KS2>(t, s_img, P.lrow, P.c, half * (C / 4));
         if (half == 0) {

@@ -12,7 +12,10 @@
 // DPP network.  The backward recomputes the forward from d (nothing is saved but the input) and keeps the
 // weight-gradient row of its lane in registers; wavefronts are combined through LDS in wavefront order and
 // workgroups by the fixed-order slab reducer: bitwise reproducible.
+#include "act.h"
 #include "common.h"
+#include "mfma.h"
+#include "wave.h"
 
 namespace {
 
@@ -21,25 +24,6 @@ constexpr int RT_THREADS = 512;
 constexpr int RT_WAVES = RT_THREADS / 64;
 constexpr int RT_VEC = 5;          // db1 | dg2 | dg1 | db0 | dw0
 constexpr int RT_SLAB = RT_M * RT_M + RT_VEC * RT_M;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// all-lanes sum of a wavefront: quad butterflies, row rotations, then the four row totals through scalar reads
-__device__ __forceinline__ float wave_sum(float v) {
-    v += dpp_move<0xB1>(v);
-    v += dpp_move<0x4E>(v);
-    v += dpp_move<0x124>(v);
-    v += dpp_move<0x128>(v);
-    const int bits = __float_as_int(v);
-    return (__int_as_float(__builtin_amdgcn_readlane(bits, 0)) + __int_as_float(__builtin_amdgcn_readlane(bits, 16))) +
-           (__int_as_float(__builtin_amdgcn_readlane(bits, 32)) + __int_as_float(__builtin_amdgcn_readlane(bits, 48)));
-}
-__device__ __forceinline__ float bcast(float v, int j) {   // j: compile-time constant after unrolling
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
-}
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 struct RtParams {
     const float *w0, *b0, *g1, *be1, *w1, *b1, *g2, *be2;
@@ -191,15 +175,6 @@ constexpr int RM_THREADS = 256;
 constexpr int RM_WAVES = RM_THREADS / 64;
 constexpr int RM_LD = RT_M + 4;
 
-typedef float rt_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float row16_sum(float v) {    // sum over the 16 lanes of a DPP row, in every lane of the row
-    v += dpp_move<0xB1>(v);
-    v += dpp_move<0x4E>(v);
-    v += dpp_move<0x124>(v);
-    v += dpp_move<0x128>(v);
-    return v;
-}
 __device__ __forceinline__ float q4_sum(float v) {       // sum over the four lanes r, r + 16, r + 32, r + 48
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
@@ -250,18 +225,18 @@ __device__ __forceinline__ void rm_layer0(const float (&vec)[7][RT_M], float d, 
 }
 
 // acc[nt][g] = sum_k h1[edge 4 q + g ... as the A operand][k] W1[16 nt + r][k]  (no bias)
-__device__ __forceinline__ void rm_matmul(const float* w1, const float4 (&h1)[4], int r, int q, rt_f32x4 (&acc)[4]) {
+__device__ __forceinline__ void rm_matmul(const float* w1, const float4 (&h1)[4], int r, int q, f32x4 (&acc)[4]) {
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) acc[nt] = rt_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
             const float4 w = *reinterpret_cast<const float4*>(w1 + (16 * nt + r) * RM_LD + 16 * t + 4 * q);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1[t].x, w.x, acc[nt], 0, 0, 0);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1[t].y, w.y, acc[nt], 0, 0, 0);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1[t].z, w.z, acc[nt], 0, 0, 0);
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1[t].w, w.w, acc[nt], 0, 0, 0);
+            acc[nt] = mfma16(h1[t].x, w.x, acc[nt]);
+            acc[nt] = mfma16(h1[t].y, w.y, acc[nt]);
+            acc[nt] = mfma16(h1[t].z, w.z, acc[nt]);
+            acc[nt] = mfma16(h1[t].w, w.w, acc[nt]);
         }
 }
 
@@ -277,7 +252,7 @@ k_radial_fwd_mfma(const float* __restrict__ dist, RtParams p, int64_t E, float e
         const float d = e0 + r < E ? dist[e0 + r] : 0.f;
         float4 h1[4];
         rm_layer0(S.vec, d, q, eps, h1);
-        rt_f32x4 acc[4];
+        f32x4 acc[4];
         rm_matmul(S.w1, h1, r, q, acc);
         // lane (r, q): channels n = 16 nt + r of edges 4 q + g
         float b1[4], g2[4], be2[4];
@@ -353,11 +328,11 @@ k_radial_bwd_mfma(const float* __restrict__ dist, RtParams p, const float* __res
         w0c[x] = S.vec[0][16 * x + r]; b0c[x] = S.vec[1][16 * x + r]; g1c[x] = S.vec[2][16 * x + r];
         be1c[x] = S.vec[3][16 * x + r]; b1c[x] = S.vec[4][16 * x + r]; g2c[x] = S.vec[5][16 * x + r];
     }
-    rt_f32x4 accW[4][4];
+    f32x4 accW[4][4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt) accW[nt][kt] = rt_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kt = 0; kt < 4; ++kt) accW[nt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float a_db1[4] = {0, 0, 0, 0}, a_dg2[4] = {0, 0, 0, 0}, a_dg1[4] = {0, 0, 0, 0}, a_db0[4] = {0, 0, 0, 0}, a_dw0[4] = {0, 0, 0, 0};
     const int64_t tiles = (E + 15) / 16, stride = (int64_t)gridDim.x * RM_WAVES;
     for (int64_t tile = (int64_t)blockIdx.x * RM_WAVES + wave; tile < tiles; tile += stride) {
@@ -387,7 +362,7 @@ k_radial_bwd_mfma(const float* __restrict__ dist, RtParams p, const float* __res
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) { xh1[kt][g] = a[kt] * r1[g]; h1d[kt][g] = fmaf(xh1[kt][g], g1c[kt], be1c[kt]); }
         }
-        rt_f32x4 z2[4];
+        f32x4 z2[4];
         rm_matmul(S.w1, h1a, r, q, z2);
         // ---- LayerNorm 2 / SiLU 2 backward (DL)
         float dz2[4][4];
@@ -425,7 +400,7 @@ k_radial_bwd_mfma(const float* __restrict__ dist, RtParams p, const float* __res
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                 for (int sgn = 0; sgn < 4; ++sgn)
-                    accW[nt][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(dz2[nt][sgn], h1d[kt][sgn], accW[nt][kt], 0, 0, 0);
+                    accW[nt][kt] = mfma16(dz2[nt][sgn], h1d[kt][sgn], accW[nt][kt]);
         // ---- dh1 = dz2 W1: dz2 into AL through the wavefront's LDS tile
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -439,18 +414,18 @@ k_radial_bwd_mfma(const float* __restrict__ dist, RtParams p, const float* __res
 #pragma unroll
         for (int t = 0; t < 4; ++t) dz2a[t] = *reinterpret_cast<const float4*>(wt + r * RM_LD + 16 * t + 4 * q);
         __builtin_amdgcn_wave_barrier();
-        rt_f32x4 dh1[4];
+        f32x4 dh1[4];
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt) dh1[kt] = rt_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kt = 0; kt < 4; ++kt) dh1[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
                 const float4 w = *reinterpret_cast<const float4*>(S.w1t + (16 * kt + r) * RM_LD + 16 * t + 4 * q);
-                dh1[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(dz2a[t].x, w.x, dh1[kt], 0, 0, 0);
-                dh1[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(dz2a[t].y, w.y, dh1[kt], 0, 0, 0);
-                dh1[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(dz2a[t].z, w.z, dh1[kt], 0, 0, 0);
-                dh1[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(dz2a[t].w, w.w, dh1[kt], 0, 0, 0);
+                dh1[kt] = mfma16(dz2a[t].x, w.x, dh1[kt]);
+                dh1[kt] = mfma16(dz2a[t].y, w.y, dh1[kt]);
+                dh1[kt] = mfma16(dz2a[t].z, w.z, dh1[kt]);
+                dh1[kt] = mfma16(dz2a[t].w, w.w, dh1[kt]);
             }
         // ---- LayerNorm 1 / SiLU 1 backward (DL)
 #pragma unroll

@@ -25,10 +25,9 @@
 // D[m = 4 q + g][n = r] in accumulator component g.  Four MFMAs share one float4 of K: the j-th of them
 // takes component j on both sides, i.e. k = 16 s + 4 q + j (a permutation of K, which a sum does not see).
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef RH_STAMPS   // diagnostic build only (tools/readout_stamps.py): s_memtime stamps of the phases, wavefront 0 of every workgroup
 __device__ unsigned long long* rh_stamp_buf = nullptr;
@@ -43,10 +42,6 @@ __device__ unsigned long long* rh_stamp_buf = nullptr;
 constexpr int RH_THREADS = 512;
 constexpr int RH_WAVES = RH_THREADS / 64;
 constexpr int RH_ROWS = 16;  // molecules per workgroup = the M of one MFMA tile
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 struct RhWeights {
     const float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *w3, *b3;

@@ -4,39 +4,13 @@
 // one launch each way, a wavefront per row (float4 per lane, C <= 1024), the scale gradient through per-workgroup
 // slabs and the fixed-order reducer.
 #include "common.h"
+#include "row.h"
+#include "wave.h"
 
 namespace {
 
 constexpr int RN_THREADS = 256;
 constexpr int RN_WAVES = RN_THREADS / 64;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v += dpp_move<0xB1>(v);
-    v += dpp_move<0x4E>(v);
-    v += dpp_move<0x124>(v);
-    v += dpp_move<0x128>(v);
-    const int bits = __float_as_int(v);
-    return (__int_as_float(__builtin_amdgcn_readlane(bits, 0)) + __int_as_float(__builtin_amdgcn_readlane(bits, 16))) +
-           (__int_as_float(__builtin_amdgcn_readlane(bits, 32)) + __int_as_float(__builtin_amdgcn_readlane(bits, 48)));
-}
-
-template <int NV>
-struct Row {
-    float4 v[NV];
-};
-
-template <int NV>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, int64_t r, int C, int lane, Row<NV>& x) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        x.v[i] = c < C ? *reinterpret_cast<const float4*>(p + r * C + c) : f4_zero();
-    }
-}
 
 template <int NV>
 __device__ __forceinline__ float sum_sq(const Row<NV>& x) {
@@ -127,13 +101,6 @@ k_rms_bwd(const float* __restrict__ x, const float* __restrict__ g, const float*
 
 inline int rn_blocks(int64_t rows) { return eqh_grid_for(rows, RN_WAVES * 4, 256); }
 
-template <typename F>
-int rn_dispatch(int C, F&& f) {
-    if (C <= 256) return f(std::integral_constant<int, 1>{});
-    if (C <= 512) return f(std::integral_constant<int, 2>{});
-    return f(std::integral_constant<int, 4>{});
-}
-
 int rn_check(int64_t n_rows, int32_t C) {
     if (n_rows < 0 || C <= 0 || n_rows > INT32_MAX) return EQH_ERR_ARG;
     if ((C & 3) || C > 1024) return EQH_ERR_RANGE;
@@ -150,7 +117,7 @@ extern "C" int eqf_rms_norm_fwd(const float* x, const float* g, int64_t n_rows, 
     if (!x || !g || !out) return EQH_ERR_ARG;
     if (!eqh_aligned16(x) || !eqh_aligned16(g) || !eqh_aligned16(out)) return EQH_ERR_ALIGN;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return rn_dispatch(C, [&](auto nv) {
+    return dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         hipLaunchKernelGGL((k_rms_fwd<NV>), dim3(eqh_grid_for(n_rows, RN_WAVES, 4096)), dim3(RN_THREADS), 0, stream, x, g,
                            out, (int)n_rows, (int)C, scale, eps);
@@ -178,7 +145,7 @@ extern "C" int eqf_rms_norm_bwd(const float* x, const float* g, const float* dy,
     if (workspace_bytes < eqf_rms_norm_bwd_workspace_bytes(n_rows, C)) return EQH_ERR_ARG;
     const int blocks = rn_blocks(n_rows);
     float* slab = static_cast<float*>(workspace);
-    return rn_dispatch(C, [&](auto nv) {
+    return dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         hipLaunchKernelGGL((k_rms_bwd<NV>), dim3(blocks), dim3(RN_THREADS), 0, stream, x, g, dy, dx, slab, (int)n_rows,
                            (int)C, scale, eps);

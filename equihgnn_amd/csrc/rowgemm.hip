@@ -14,16 +14,12 @@
 // Backward: dz[e] = dout[e] · w[row]ᵀ and dw[row] = sum_e z[e]ᵀ ⊗ dout[e]; every dw[row] is written
 // by exactly one wavefront (no atomics, reproducible).
 #include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 __device__ __forceinline__ int entry_at(const int* __restrict__ perm, int pos, int end) {
     if (pos >= end) return -1;

@@ -1,40 +1,14 @@
 // Row-wise LayerNorm arithmetic shared by the aggregation kernels (incidence.hip) and the panel GEMM kernels
 // (panel.hip): one 64-lane wavefront per row, a row of C <= 1024 channels is NV float4 per lane (lane l holds channels
 // 4 (l + 64 i) .. + 3).  ONE definition, so that a LayerNorm fused into a GEMM prologue / epilogue gives bit-identical
-// results to the stand-alone row kernels (mlp.py:91-99: Linear -> ReLU -> LayerNorm).
+// results to the stand-alone row kernels (mlp.py:91-99: Linear -> ReLU -> LayerNorm).  The row itself is row.h's Row<NV>, the
+// sums are wave.h's wave_sum.
 #pragma once
 #include "common.h"
+#include "row.h"
+#include "wave.h"
 
 namespace {
-
-// Wavefront all-reduce on the DPP cross-lane network (no LDS round trips): quad butterflies, then
-// rotations inside each 16-lane row, then the four row totals are combined through scalar reads.
-// Every lane of the wavefront must be active.  Fixed summation order => reproducible.
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_move<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_move<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_move<0x124>(v);  // row_ror:4
-    v += dpp_move<0x128>(v);  // row_ror:8
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    const int bits = __float_as_int(row16_sum(v));  // readlane moves 32-bit integers
-    return (__int_as_float(__builtin_amdgcn_readlane(bits, 0)) + __int_as_float(__builtin_amdgcn_readlane(bits, 16))) +
-           (__int_as_float(__builtin_amdgcn_readlane(bits, 32)) + __int_as_float(__builtin_amdgcn_readlane(bits, 48)));
-}
-__device__ __forceinline__ void wave_sum2(float& a, float& b) {
-    a = wave_sum(a);
-    b = wave_sum(b);
-}
-
-template <int NV>
-struct Row {
-    float4 v[NV];
-};
 
 // h = relu(u + w) (RELU) or u + w; returns xhat in `x`, rstd in *rstd, relu mask in `pos` (bit per comp)
 template <int NV, bool RELU = true>
@@ -70,6 +44,5 @@ __device__ __forceinline__ void norm_pair(const Row<NV>& u, const Row<NV>& w, in
 #pragma unroll
     for (int i = 0; i < NV; ++i) { x.v[i].x *= r; x.v[i].y *= r; x.v[i].z *= r; x.v[i].w *= r; }
 }
-
 
 }  // namespace

@@ -20,6 +20,7 @@
 //
 // Activations of the edge projections (silu of dk_proj, dv_proj, s_proj, f_proj) are applied inside the kernels on the
 // raw Linear outputs, and their derivative is folded into the returned edge gradients.
+#include "act.h"
 #include "common.h"
 
 namespace {
@@ -32,10 +33,10 @@ constexpr int LANES = 64;
 constexpr int MAXV = 8;        // channels per lane: C <= 512
 constexpr int GRID_CAP = 16384;
 
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float silu(float x) { return x * sigm(x); }
+// SiLU as x * sigmoid_exact(x): a division, then a product (two roundings)
+__device__ __forceinline__ float silu_exact(float x) { return x * sigmoid_exact(x); }
 __device__ __forceinline__ float dsilu(float x) {
-    const float s = sigm(x);
+    const float s = sigmoid_exact(x);
     return s * (1.f + x * (1.f - s));
 }
 
@@ -295,13 +296,13 @@ k_vis_attn_fwd(const float* __restrict__ q, const float* __restrict__ k, const f
             }
             const int64_t j = slot[e];
             float p[MAXV] = {};
-            VIS_LANE_CH(t, c, C) p[t] = (q[i * C + c] * k[j * C + c]) * silu(dkr[e * C + c]);
+            VIS_LANE_CH(t, c, C) p[t] = (q[i * C + c] * k[j * C + c]) * silu_exact(dkr[e * C + c]);
             head_sums(p, C, s_p, s_h);
             const float ce = cut[e];
             if (threadIdx.x < HEADS) pre[e * HEADS + threadIdx.x] = s_h[threadIdx.x];
             VIS_LANE_CH(t, c, C) {
-                const float a = silu(s_h[c / D]) * ce;
-                const float m = (v[j * C + c] * silu(dvr[e * C + c])) * a;
+                const float a = silu_exact(s_h[c / D]) * ce;
+                const float m = (v[j * C + c] * silu_exact(dvr[e * C + c])) * a;
                 u[e * C + c] = m;
                 acc[t] += m;
             }
@@ -340,9 +341,9 @@ k_vis_attn_bwd_edge(const float* __restrict__ q, const float* __restrict__ k, co
                 const float g = du[e * C + c] + dxagg[i * C + c];
                 const float dvv = dvr[e * C + c];
                 const float ph = pre[e * HEADS + c / D];
-                const float a = silu(ph) * ce;
+                const float a = silu_exact(ph) * ce;
                 ddvr[e * C + c] = ((g * a) * v[j * C + c]) * dsilu(dvv);
-                p[t] = g * (v[j * C + c] * silu(dvv));
+                p[t] = g * (v[j * C + c] * silu_exact(dvv));
             }
             head_sums(p, C, s_p, s_h);
             if (threadIdx.x < HEADS) {
@@ -355,7 +356,7 @@ k_vis_attn_bwd_edge(const float* __restrict__ q, const float* __restrict__ k, co
                 const float dp = s_h[c / D];
                 const float dkk = dkr[e * C + c];
                 ddkr[e * C + c] = ((dp * q[i * C + c]) * k[j * C + c]) * dsilu(dkk);
-                acc[t] += (dp * k[j * C + c]) * silu(dkk);
+                acc[t] += (dp * k[j * C + c]) * silu_exact(dkk);
             }
             __syncthreads();
         }
@@ -379,9 +380,9 @@ k_vis_attn_bwd_node(const float* __restrict__ q, const float* __restrict__ dkr, 
             const float ce = cut[e];
             VIS_LANE_CH(t, c, C) {
                 const int h = c / D;
-                ak[t] += (dpre[e * HEADS + h] * q[i * C + c]) * silu(dkr[e * C + c]);
+                ak[t] += (dpre[e * HEADS + h] * q[i * C + c]) * silu_exact(dkr[e * C + c]);
                 const float g = du[e * C + c] + dxagg[i * C + c];
-                av[t] += (g * (silu(pre[e * HEADS + h]) * ce)) * silu(dvr[e * C + c]);
+                av[t] += (g * (silu_exact(pre[e * HEADS + h]) * ce)) * silu_exact(dvr[e * C + c]);
             }
         }
         VIS_LANE_CH(t, c, C) { dk[j * C + c] = ak[t]; dv[j * C + c] = av[t]; }
@@ -404,7 +405,7 @@ k_vis_vec_fwd(const float* __restrict__ vec, const float* __restrict__ sr, const
             float d[NSH];
             for (int m = 0; m < NSH; ++m) d[m] = sh[e * NSH + m];
             VIS_LANE_CH(t, c, C) {
-                const float s1 = silu(sr[e * 2 * C + c]), s2 = silu(sr[e * 2 * C + C + c]);
+                const float s1 = silu_exact(sr[e * 2 * C + c]), s2 = silu_exact(sr[e * 2 * C + C + c]);
 #pragma unroll
                 for (int m = 0; m < NSH; ++m) acc[m][t] += vec[(j * NSH + m) * C + c] * s1 + s2 * d[m];
             }
@@ -456,7 +457,7 @@ k_vis_vec_bwd_node(const float* __restrict__ sr, const int32_t* __restrict__ src
         for (int qq = q0; qq < q1; ++qq) {
             const int64_t e = src_eid[qq], i = e / K;
             VIS_LANE_CH(t, c, C) {
-                const float s1 = silu(sr[e * 2 * C + c]);
+                const float s1 = silu_exact(sr[e * 2 * C + c]);
 #pragma unroll
                 for (int m = 0; m < NSH; ++m) acc[m][t] += dvo[(i * NSH + m) * C + c] * s1;
             }
@@ -515,7 +516,7 @@ k_vis_eupd_fwd(const float* __restrict__ wt, const float* __restrict__ ws, const
             VIS_LANE_CH(t, c, C) {
                 float a[NSH], b[NSH];
                 const float dot = edge_pair(wt, ws, i, j, c, C, d, nd, a, b);
-                df[e * C + c] = silu(fr[e * C + c]) * dot;
+                df[e * C + c] = silu_exact(fr[e * C + c]) * dot;
             }
         }
     }
@@ -544,7 +545,7 @@ k_vis_eupd_bwd_edge(const float* __restrict__ wt, const float* __restrict__ ws, 
                 const float dot = edge_pair(wt, ws, i, j, c, C, d, nd, a, b);
                 const float g = ddf[e * C + c], f = fr[e * C + c];
                 dfr[e * C + c] = (g * dot) * dsilu(f);
-                const float gd = g * silu(f);
+                const float gd = g * silu_exact(f);
 #pragma unroll
                 for (int m = 0; m < NSH; ++m) da[m] = gd * b[m];
                 rejection(da, d, ja);
@@ -575,7 +576,7 @@ k_vis_eupd_bwd_node(const float* __restrict__ wt, const float* __restrict__ ws, 
             VIS_LANE_CH(t, c, C) {
                 float a[NSH], b[NSH], db[NSH], jb[NSH];
                 edge_pair(wt, ws, i, j, c, C, d, nd, a, b);
-                const float gd = ddf[e * C + c] * silu(fr[e * C + c]);
+                const float gd = ddf[e * C + c] * silu_exact(fr[e * C + c]);
 #pragma unroll
                 for (int m = 0; m < NSH; ++m) db[m] = gd * a[m];
                 rejection(db, nd, jb);

@@ -21,18 +21,13 @@
 
 #include "common.h"
 #include "bf16x3.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int THREADS = 256;
 constexpr int WAVES = 4;
 constexpr int AHEAD = 2;  // k-steps (of 4 rows) per register stage
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 struct Stage {
     float4 a[AHEAD], b[AHEAD];
@@ -230,8 +225,6 @@ k_wgrad_batch(WgradBatch b, int O, int I, int tiles_i, int tiles, int splits) {
 // the 64 x 64 quadrant (qi, qj) over the kh-th half of the chunk (a quadrant's operand rows are shared with its neighbours through
 // L1, so a product's operands cross L2 -> CU twice instead of four times); the two K-halves meet in LDS, one slab per chunk.
 // ------------------------------------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int WX_THREADS = 512;
 
 struct WxStage {
