@@ -216,7 +216,6 @@ class _PairedBase(nn.Module):
         return x
 
     def forward(self, data, taps=None, head=None):
-        from . import ops
         index = HyperIndex.from_batch(data)
         x = self._front(data, index, taps)
         e = self.bond_encoder(data.edge_attr)
@@ -226,14 +225,23 @@ class _PairedBase(nn.Module):
                 if i != self.nlayer - 1:
                     x, e = self.act(x), self.act(e)
                 x, e = self.dropout(x), self.dropout(e)
-        xp = pool_sum(x, index)
-        he_csr, he_key = index.hyperedge_pool(data.n_e)
-        keep = (data.e_order > 2).to(e.dtype).unsqueeze(-1)            # mhnn.py:58,72
-        ep = ops.reduce_entries(e * keep, he_csr, he_key, "sum")
-        both = torch.cat((xp, ep), -1)
+        both = self._pool(x, e, index, data)
         if taps is not None:
             taps["pool"] = both
         return head_loss(self.mlp_out(both, mask=index.pad_masks()[3]).view(-1), head)
+
+    fused_pool = False   # the read-out as ONE launch each way (ops.pool_pair) instead of mask, product, two reduces and a cat
+
+    def _pool(self, x, e, index, data):
+        """[B, 2C]: node rows and hyperedge rows of order > 2 summed per molecule, side by side (mhnn.py:58,72)."""
+        from . import ops
+        if self.fused_pool:
+            return ops.pool_pair(x, e, index, data.n_e, data.e_order)
+        xp = pool_sum(x, index)
+        he_csr, he_key = index.hyperedge_pool(data.n_e)
+        keep = (data.e_order > 2).to(e.dtype).unsqueeze(-1)
+        ep = ops.reduce_entries(e * keep, he_csr, he_key, "sum")
+        return torch.cat((xp, ep), -1)
 
 
 @registry.register_model("mhnn")
@@ -351,6 +359,65 @@ class FAFormerEquiHNNS(nn.Module):
         return readout(self.mlp_out, self.dropout(x), index, taps, head)
 
 
+def _faformer(args):
+    """The wrappers' FAFormer (equihnn_fa_former.py:36-49,130-143,210-223)."""
+    return FAFormer(args.MLP_hidden, n_layers=2, n_heads=2, n_neighbors=16, valid_radius=5.0)
+
+
+def _faformer_front(model, data, index, taps):
+    x = model.atom_encoder(data.x)
+    if taps is not None:
+        taps["atom_encoder"] = x
+    x = model.fa_former(x, data.pos, index, real_row_mask(data, x))
+    if taps is not None:
+        taps["front_end"] = x
+    return x
+
+
+@registry.register_model("faformer_equihnn")
+class FAFormerEquiHNN(_PairedBase):
+    """equihnn_fa_former.py:12-102: AtomEncoder -> FAFormer (once) -> ONE shared MHNNConv x L on (x, e) -> node and
+    order > 2 hyperedge pools side by side (one launch, ops.pool_pair) -> head on [B, 2C].  A molecule without a hyperedge
+    of order > 2 gets a zero row in the hyperedge pool; the reference sizes that pool by ``he_batch.max() + 1`` and fails in
+    ``torch.cat`` (:101) when the LAST molecules of a batch have none.  The reference keeps proj_drop = attn_drop = 0.1
+    inside FAFormer in training mode (fa_former_layer.py:20-21), whatever ``--dropout`` says."""
+
+    fused_pool = True
+
+    def __init__(self, num_target, args):
+        super().__init__(num_target, args, with_egnn=False)
+        self.fa_former = _faformer(args)
+
+    def _front(self, data, index, taps):
+        return _faformer_front(self, data, index, taps)
+
+
+@registry.register_model("faformer_equihnnm")
+class FAFormerEquiHNNM(MHNNM):
+    """equihnn_fa_former.py:187-283: mhnnm with the FAFormer front-end applied once to the atom embeddings.  FAFormer keeps
+    its own proj_drop = attn_drop = 0.1 in training mode (fa_former_layer.py:20-21), whatever ``--dropout`` says."""
+
+    def __init__(self, num_target, args):
+        super().__init__(num_target, args)
+        self.fa_former = _faformer(args)
+
+    def forward(self, data, taps=None, head=None):
+        index = HyperIndex.from_batch(data)
+        x = _faformer_front(self, data, index, taps)
+        e = self.bond_encoder(data.edge_attr)
+        mask = real_row_mask(data, x)   # padded batch: BatchNorm statistics over the real atoms only
+        for i, layer in enumerate(self.layers):
+            x, e = layer(x, e, index)
+            fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
+            x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
+            if taps is not None:
+                taps[f"bn{i}"] = x
+            if i != self.nlayer - 1:
+                x, e = (x if fuse else self.act(x)), self.act(e)
+            x, e = self.dropout(x), self.dropout(e)
+        return readout(self.mlp_out, x, index, taps, head)
+
+
 def _visnet(args):
     """The wrappers' ViSNet (equihnn_visnet.py:35-37,114-118,183-185)."""
     return ViSNet(hidden_channels=args.MLP_hidden, lmax=2, max_num_neighbors=16)
@@ -443,4 +510,5 @@ MODELS = {"egnn_equihnns": EGNNEquiHNNS, "mhnnm": MHNNM, "equiformer_equihnns": 
           "faformer_equihnns": FAFormerEquiHNNS,
           "mhnn": MHNN, "mhnns": MHNNS, "egnn_equihnn": EGNNEquiHNN, "egnn_equihnnm": EGNNEquiHNNM,
           "gin": GNN_2D, "gcn": GNN_2D,
-          "visnet_equihnn": VisNetEquiHNN, "visnet_equihnns": VisNetEquiHNNS, "visnet_equihnnm": VisNetEquiHNNM}
+          "visnet_equihnn": VisNetEquiHNN, "visnet_equihnns": VisNetEquiHNNS, "visnet_equihnnm": VisNetEquiHNNM,
+          "faformer_equihnn": FAFormerEquiHNN, "faformer_equihnnm": FAFormerEquiHNNM}

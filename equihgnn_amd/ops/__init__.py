@@ -14,7 +14,7 @@ One module per subsystem; everything is re-exported here, so cal
   linears  nn.Linear-shaped autograd nodes, merged consecutive Linears, matmul fans
   rows     per-incidence hidden layer + reduce, bias/ReLU/LayerNorm rows, BatchNorm / LayerNorm rows, residual mix
   egnn     EGNN edge kernels, feature node, weight packing
-  readout  pooled readout head + MSE in one launch
+  readout  pooled readout head + MSE in one launch, paired node / hyperedge pool
   se3      Equiformer: row GEMMs, radial trunk, attention pooling, RMS norm, edge geometry
   gnn2d    2-D baselines: graph index (edge CSRs, bond codes), GIN / GCN edge messages, mean pool
   frames   FAFormer: frame-averaged SwiGLU pieces, edge hidden layer, row dots, gates, attention sums, eigh3
@@ -69,7 +69,8 @@ from .egnn import (  # noqa: F401
     egnn_node_mlp_supported, egnn_node_mlp_ln, NODE_LN_FOLD,
 )
 from .readout import (  # noqa: F401
-    _MseLoss, mse_loss, _READOUT_STATE, _readout_state, _ReadoutMse, readout_mse_supported, readout_mse,
+    _MseLoss, mse_loss, _READOUT_STATE, _readout_state, _ReadoutMse, readout_mse_supported, readout_mse, _PoolPair, pool_pair,
+    pool_pair_bytes,
 )
 from .se3 import (  # noqa: F401
     _RowGemm, _RowGemm2, _RadialWeightLayout, radial_weight_layout, _AttnPool, attn_pool_supported, attn_pool,

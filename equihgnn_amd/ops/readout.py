@@ -1,4 +1,4 @@
-"""Readout head (pool + output MLP + MSE in one launch) and the fused MSE loss.
+"""Readout head (pool + output MLP + MSE in one launch), the paired node / high-order-hyperedge pool and the fused MSE loss.
 
 Part of equihgnn_amd.ops (host-side operators over libequihgnn_hip.so; no CPU fallback).
 """
@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import hip
-from ._base import (ACC_PARAMS, LINEAR_PARAMS, _acc_target, _f32c, _hand_out, _ptr, _require_gpu, _stream, _workspace)
+from ._base import (ACC_PARAMS, LINEAR_PARAMS, _acc_target, _f32c, _hand_out, _ptr, _require_gpu, _stream, _workspace, timed)
 
 
 class _MseLoss(torch.autograd.Function):
@@ -40,6 +40,57 @@ def mse_loss(pred, target):
     if pred.is_cuda and pred.dtype == torch.float32 and 0 < pred.numel() <= 65536 and not target.requires_grad:
         return _MseLoss.apply(pred.reshape(-1), target.reshape(-1))
     return F.mse_loss(pred, target)
+
+
+def pool_pair_bytes(N: int, M: int, B: int, C: int) -> tuple:
+    """Algorithmic bytes of (hg_pool_pair_fwd, hg_pool_pair_bwd): forward 4C (N + M) rows (an upper bound: hyperedge rows of
+    order <= 2 are skipped) + 4 (N + M) entries + 8 M orders + 8 (B + 1) row pointers + 8 C B output; backward 4C (N + M)
+    rows written + 4 (N + M) molecule ids + 8 M orders + 8 C B read."""
+    return (4 * C * (N + M) + 4 * (N + M) + 8 * M + 8 * (B + 1) + 8 * C * B, 4 * C * (N + M) + 4 * (N + M) + 8 * M + 8 * C * B)
+
+
+class _PoolPair(torch.autograd.Function):
+    """[global_add_pool(x, batch) | global_add_pool(e[e_order > 2], he_batch)] as ONE launch each way (hg_pool_pair_fwd/bwd):
+    no mask tensor, no [M, C] product, no concatenation."""
+
+    @staticmethod
+    def forward(ctx, x, e, pool, x_mol, he_pool, e_mol, e_order):
+        _require_gpu(x, "pool_pair")
+        x, e = _f32c(x), _f32c(e)
+        (N, C), M, B = x.shape, e.shape[0], pool.n_rows
+        out = torch.empty((B, 2 * C), dtype=torch.float32, device=x.device)
+        timed("k_pool_pair_fwd", pool_pair_bytes(N, M, B, C)[0],
+              lambda: hip.check(hip.lib().hg_pool_pair_fwd(_ptr(x), _ptr(pool.rowptr), _ptr(pool.perm), N, _ptr(e),
+                                                           _ptr(he_pool.rowptr), _ptr(he_pool.perm), _ptr(e_order), M,
+                                                           _ptr(out), B, C, _stream(x.device)), "hg_pool_pair_fwd"))
+        ctx.keys, ctx.sizes = (x_mol, e_mol, e_order), (N, M, B, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x_mol, e_mol, e_order = ctx.keys
+        N, M, B, C = ctx.sizes
+        dout = _f32c(dout)
+        dx = torch.empty((N, C), dtype=torch.float32, device=dout.device)
+        de = torch.empty((M, C), dtype=torch.float32, device=dout.device)
+        timed("k_pool_pair_bwd", pool_pair_bytes(N, M, B, C)[1],
+              lambda: hip.check(hip.lib().hg_pool_pair_bwd(_ptr(dout), _ptr(x_mol), N, _ptr(e_mol), _ptr(e_order), M, _ptr(dx),
+                                                           _ptr(de), B, C, _stream(dout.device)), "hg_pool_pair_bwd"))
+        return dx, de, None, None, None, None, None
+
+
+def pool_pair(x, e, index, n_e, e_order):
+    """[B, 2C]: per molecule the sum of its node rows ``x`` [N, C] next to the sum of its hyperedge rows ``e`` [M, C] of order
+    > 2 (equihnn_fa_former.py:99-101) -- zeros where a molecule has none.  ``index``: the batch's HyperIndex (its atom pool
+    and, from ``n_e``, its hyperedge pool); ``e_order`` int64 [M]."""
+    if x.dim() != 2 or e.dim() != 2 or x.shape[1] != e.shape[1]:
+        raise ValueError(f"pool_pair: x [N, C] and e [M, C] of one width, got {tuple(x.shape)} and {tuple(e.shape)}")
+    he_pool, e_mol = index.hyperedge_pool(n_e)
+    if he_pool.n_rows != index.pool.n_rows or e_order.shape[0] != e.shape[0] or x.shape[0] != index.N:
+        raise ValueError("pool_pair: x, e, n_e and e_order do not belong to this index's batch")
+    if e_order.dtype != torch.int64:
+        raise TypeError(f"pool_pair: e_order must be int64, got {e_order.dtype}")
+    return _PoolPair.apply(x, e, index.pool, index.batch32, he_pool, e_mol, e_order.contiguous())
 
 
 _READOUT_STATE = {}

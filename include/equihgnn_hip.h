@@ -396,6 +396,30 @@ int hg_segment_reduce_w_f32(const float* src, const int32_t* idx, const int32_t*
                             int64_t n_out_rows, int32_t C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Paired pool — the read-out of the models that pool nodes and hyperedges of order > 2 side by side:
+ * global_add_pool(x, batch), global_add_pool(e[e_order > 2], he_batch) and their torch.cat at
+ * equihnn_fa_former.py:99-101 (mhnn.py:58,72 is the same read-out), one launch each way.
+ *
+ *   out[b, 0:C]  = sum_{q in [x_rowptr[b], x_rowptr[b+1])} x[x_perm[q], :]
+ *   out[b, C:2C] = sum_{q in [e_rowptr[b], e_rowptr[b+1])} e[e_perm[q], :]   over the q with e_order[e_perm[q]] > 2
+ *
+ * out is [B, 2C], every entry written (zeros for a molecule without a qualifying row: the reference's pool has no such
+ * row at all and fails in torch.cat when the LAST molecules of a batch have none).  x is [n_x, C], e is [n_e, C], e_order
+ * [n_e] int64 as the batch holds it; the two CSRs are per-molecule row lists (hg_csr_build of `batch` and of the
+ * hyperedges' molecule ids); a perm of NULL is the identity.  Entries that are negative or >= the row count are null and
+ * skipped.  n_e == 0 (no hyperedge in the whole batch) needs none of the e pointers.  Summation order is the CSR order.
+ * The backward writes EVERY row of dx [n_x, C] and de [n_e, C] (no pre-zeroed destination):
+ *   dx[i, :] = dout[x_mol[i], 0:C],   de[j, :] = e_order[j] > 2 ? dout[e_mol[j], C:2C] : 0
+ * with x_mol / e_mol the int32 molecule id per row; an id that is negative or >= B gives a zero row.
+ * C a multiple of 4 up to 1024 (EQH_ERR_RANGE above, and for row counts past int32).
+ * ------------------------------------------------------------------------------------------- */
+int hg_pool_pair_fwd(const float* x, const int32_t* x_rowptr, const int32_t* x_perm, int64_t n_x, const float* e,
+                     const int32_t* e_rowptr, const int32_t* e_perm, const int64_t* e_order, int64_t n_e, float* out,
+                     int64_t B, int32_t C, void* stream);
+int hg_pool_pair_bwd(const float* dout, const int32_t* x_mol, int64_t n_x, const int32_t* e_mol, const int64_t* e_order,
+                     int64_t n_e, float* dx, float* de, int64_t B, int32_t C, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Embedding-sum — ogb AtomEncoder (equihnn_egnn.py:121,157; mhnn.py:164,201) and
  * nn.Embedding(6, C) for bond types (mhnn.py:165,202).
  *   out[n,:] = sum_{f<F} table[off_host[f] + x[n,f], :]      (f ascending, as ogb does)
