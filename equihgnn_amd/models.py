@@ -3,12 +3,20 @@
 Constructor and call contract of main.py:28-34,46-47: ``cls(num_target, args)``;
 ``model(data) -> float32 Tensor[B]`` on ``data.x.device``.  Parameter / buffer names and shapes are
 identical to the reference's, so its checkpoints load with ``strict=True``.
+
+The thirteen hypergraph methods are five front-ends (none, EGNN, Equiformer, FAFormer, ViSNet: the ``_Front`` rows below)
+times three tails (``_STail``, ``_PairedBase``, ``_MTail``).  A registered class is a subclass of one tail that names its
+front-end; a new method is a new row or a new three-line class, never a new ``forward``.
 """
 from __future__ import annotations
+
+import contextlib
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
+from . import ops
 from .equiformer import Equiformer
 from .faformer import FAFormer
 from .index import HyperIndex
@@ -18,6 +26,79 @@ from .registry import registry
 from .visnet import ViSNet
 
 _ACT = {"Id": nn.Identity, "relu": nn.ReLU, "prelu": nn.PReLU}
+
+
+class _Front(NamedTuple):
+    """A geometric front-end as the reference's wrappers attach it: applied once, in front of the hypergraph layers."""
+    attr: str                 # the reference's attribute name (a state-dict prefix)
+    build: Callable           # args -> module
+    embeds: bool = True       # fed the wrapper's AtomEncoder rows (ViSNet takes data.x and embeds with its own two)
+    masked: bool = False      # also takes real_row_mask (FAFormer: centroid and frames over the real rows of a padded batch)
+
+
+_EGNN = _Front("egnn_layer", lambda a: EGNN(dim=a.MLP_hidden, num_nearest_neighbors=16))
+_EQUIFORMER = _Front("equiformer_layer",
+                     lambda a: Equiformer(dim=a.MLP_hidden, dim_head=48, num_neighbors=16, valid_radius=5.0))
+_FAFORMER = _Front("fa_former",    # equihnn_fa_former.py:36-49,130-143,210-223
+                   lambda a: FAFormer(a.MLP_hidden, n_layers=2, n_heads=2, n_neighbors=16, valid_radius=5.0), masked=True)
+_VISNET = _Front("visnet_layer",   # equihnn_visnet.py:35-37,114-118,183-185
+                 lambda a: ViSNet(hidden_channels=a.MLP_hidden, lmax=2, max_num_neighbors=16), embeds=False)
+
+
+def _mhnn_conv(args):
+    return MHNNConv(args.MLP_hidden, mlp1_layers=args.MLP1_num_layers, mlp2_layers=args.MLP2_num_layers,
+                    mlp3_layers=args.MLP3_num_layers, mlp4_layers=args.MLP4_num_layers,
+                    aggr=args.aggregate, dropout=args.dropout, normalization=args.normalization)
+
+
+def _head(num_target, args, width=1):
+    return MLP(in_channels=args.MLP_hidden * width, hidden_channels=args.output_hidden * width,
+               out_channels=num_target, num_layers=args.output_num_layers,
+               dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
+
+
+def _merged_scope(convs, x, e):
+    """ops.merged_scope on the GPU (the panel path of MHNNConv); a no-op context elsewhere."""
+    return ops.merged_scope(convs, x, e) if x.is_cuda else contextlib.nullcontext()
+
+
+class _Wrapper(nn.Module):
+    """What the three tails share: the scalar hyper-parameters and the one path to the front-end.  Each tail's ``__init__``
+    creates its sub-modules in the reference's order for that tail (it is the order of ``state_dict()`` and of the seeded
+    random draws), so each decides where ``_build_front`` goes."""
+
+    front: Optional[_Front] = None
+
+    def __init__(self, args):
+        super().__init__()
+        self.act = _ACT[args.activation]()
+        self.dropout = nn.Dropout(args.dropout)
+        self.mlp1_layers = args.MLP1_num_layers
+        self.mlp2_layers = args.MLP2_num_layers
+        self.mlp3_layers = args.MLP3_num_layers
+        self.nlayer = args.All_num_layers
+
+    @property
+    def _embeds(self):
+        return self.front is None or self.front.embeds
+
+    def _build_front(self, args):
+        if self.front is not None:
+            setattr(self, self.front.attr, self.front.build(args))
+
+    def _apply_front(self, data, index, taps):
+        """Node features in front of the hypergraph layers, with the ``atom_encoder`` / ``front_end`` taps."""
+        x = data.x
+        if self._embeds:
+            x = self.atom_encoder(x)
+            if taps is not None:
+                taps["atom_encoder"] = x
+        if self.front is not None:
+            extra = (real_row_mask(data, x),) if self.front.masked else ()
+            x = getattr(self, self.front.attr)(x, data.pos, index, *extra)
+            if taps is not None:
+                taps["front_end"] = x
+        return x
 
 
 def _conv_layers(model, x, index, x0, res, fuse_act, taps):
@@ -36,27 +117,19 @@ def _conv_layers(model, x, index, x0, res, fuse_act, taps):
     return x
 
 
-@registry.register_model("egnn_equihnns")
-class EGNNEquiHNNS(nn.Module):
-    """equihnn_egnn.py:98-169: AtomEncoder -> EGNN (once) -> shared MHNNSConv x L -> pool -> head."""
+class _STail(_Wrapper):
+    """The S tail: [AtomEncoder ->] front-end (once) -> shared MHNNSConv x L -> pool -> head."""
 
     def __init__(self, num_target, args):
-        super().__init__()
-        self.act = _ACT[args.activation]()
-        self.dropout = nn.Dropout(args.dropout)
-        self.mlp1_layers = args.MLP1_num_layers
-        self.mlp2_layers = args.MLP2_num_layers
-        self.mlp3_layers = args.MLP3_num_layers
-        self.nlayer = args.All_num_layers
-        self.atom_encoder = AtomEncoder(emb_dim=args.MLP_hidden)
-        self.egnn_layer = EGNN(dim=args.MLP_hidden, num_nearest_neighbors=16)
+        super().__init__(args)
+        if self._embeds:
+            self.atom_encoder = AtomEncoder(emb_dim=args.MLP_hidden)
+        self._build_front(args)
         self.conv = MHNNSConv(args.MLP_hidden, mlp1_layers=self.mlp1_layers,
                               mlp2_layers=self.mlp2_layers, mlp3_layers=self.mlp3_layers,
                               aggr=args.aggregate, dropout=args.dropout,
                               normalization=args.normalization)
-        self.mlp_out = MLP(in_channels=args.MLP_hidden, hidden_channels=args.output_hidden,
-                           out_channels=num_target, num_layers=args.output_num_layers,
-                           dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
+        self.mlp_out = _head(num_target, args)
 
     def reset_parameters(self):  # equihnn_egnn.py:151-153
         self.conv.reset_parameters()
@@ -64,12 +137,7 @@ class EGNNEquiHNNS(nn.Module):
 
     def forward(self, data, taps=None, head=None):
         index = HyperIndex.from_batch(data)
-        x = self.atom_encoder(data.x)
-        if taps is not None:
-            taps["atom_encoder"] = x
-        x = self.egnn_layer(x, data.pos, index)
-        if taps is not None:
-            taps["front_end"] = x
+        x = self._apply_front(data, index, taps)
         x0 = x
         res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
         fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
@@ -77,147 +145,30 @@ class EGNNEquiHNNS(nn.Module):
         return readout(self.mlp_out, self.dropout(x), index, taps, head)
 
 
-@registry.register_model("mhnnm")
-class MHNNM(nn.Module):
-    """mhnn.py:144-218: L unshared MHNNConv layers + BatchNorm1d on node rows.  The host-side
-    per-molecule ``.item()`` loop of mhnn.py:196-199 builds a tensor the model never uses; it is
-    not reproduced (it costs B device syncs per step)."""
+class _PairedBase(_Wrapper):
+    """The paired tail: ONE shared MHNNConv applied L times on (x, e); nodes and hyperedges of order > 2 are pooled per
+    molecule and concatenated.  The reference sizes the hyperedge pool by ``he_batch.max()+1`` and fails in ``torch.cat``
+    when the last molecules of a batch have no such hyperedge; here they get a zero row."""
+
+    front_leads = False   # the front-end is the FIRST sub-module (equihnn_egnn.py:12-95 only); the others append theirs
 
     def __init__(self, num_target, args):
-        super().__init__()
-        self.act = _ACT[args.activation]()
-        self.dropout = nn.Dropout(args.dropout)
-        self.mlp1_layers = args.MLP1_num_layers
-        self.mlp2_layers = args.MLP2_num_layers
-        self.mlp3_layers = args.MLP3_num_layers
+        super().__init__(args)
         self.mlp4_layers = args.MLP4_num_layers
-        self.nlayer = args.All_num_layers
+        if self.front_leads:
+            self._build_front(args)
         self.atom_encoder = AtomEncoder(emb_dim=args.MLP_hidden)
         self.bond_encoder = BondEncoder(6, args.MLP_hidden)
-        self.layers = nn.ModuleList()
-        self.batch_norms = nn.ModuleList()
-        for _ in range(self.nlayer):
-            self.layers.append(MHNNConv(args.MLP_hidden, mlp1_layers=self.mlp1_layers,
-                                        mlp2_layers=self.mlp2_layers, mlp3_layers=self.mlp3_layers,
-                                        mlp4_layers=self.mlp4_layers, aggr=args.aggregate,
-                                        dropout=args.dropout, normalization=args.normalization))
-            self.batch_norms.append(nn.BatchNorm1d(args.MLP_hidden))
-        self.mlp_out = MLP(in_channels=args.MLP_hidden, hidden_channels=args.output_hidden,
-                           out_channels=num_target, num_layers=args.output_num_layers,
-                           dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
+        self.conv = _mhnn_conv(args)
+        self.mlp_out = _head(num_target, args, width=2)
+        if not self._embeds:
+            del self.atom_encoder   # never used, but its random draws come before those of every module after it
+        if not self.front_leads:
+            self._build_front(args)
 
     def forward(self, data, taps=None, head=None):
         index = HyperIndex.from_batch(data)
-        x = self.atom_encoder(data.x)
-        e = self.bond_encoder(data.edge_attr)
-        if taps is not None:
-            taps["atom_encoder"] = x
-        mask = real_row_mask(data, x)   # padded batch: BatchNorm statistics over the real atoms only
-        with _merged_scope(self.layers, x, e):      # the layers' weight-level products in one launch each way
-            for i, layer in enumerate(self.layers):
-                x, e = layer(x, e, index)
-                # (the ReLU behind the normalisation rides its launches, unless the pre-activation value is tapped)
-                fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
-                x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
-                if taps is not None:
-                    taps[f"bn{i}"] = x
-                if i != self.nlayer - 1:  # no activation after the last layer, mhnn.py:208-214
-                    x, e = (x if fuse else self.act(x)), self.act(e)
-                x, e = self.dropout(x), self.dropout(e)
-        return readout(self.mlp_out, x, index, taps, head)
-
-
-def _merged_scope(convs, x, e):
-    """ops.merged_scope on the GPU (the panel path of MHNNConv); a no-op context elsewhere."""
-    import contextlib
-    if x.is_cuda:
-        from . import ops
-        return ops.merged_scope(convs, x, e)
-    return contextlib.nullcontext()
-
-
-@registry.register_model("equiformer_equihnns")
-class EquiformerEquiHNNS(nn.Module):
-    """equihnn_equiformer.py:12-93: AtomEncoder -> Equiformer (once, type-0 output) -> shared
-    MHNNSConv x L -> pool -> head.  The reference keeps a leading batch dim of 1 through the conv /
-    pool / head (equihnn_equiformer.py:82-85) and flattens at the end; values are identical."""
-
-    def __init__(self, num_target, args):
-        super().__init__()
-        self.act = _ACT[args.activation]()
-        self.dropout = nn.Dropout(args.dropout)
-        self.mlp1_layers = args.MLP1_num_layers
-        self.mlp2_layers = args.MLP2_num_layers
-        self.mlp3_layers = args.MLP3_num_layers
-        self.nlayer = args.All_num_layers
-        self.atom_encoder = AtomEncoder(emb_dim=args.MLP_hidden)
-        self.equiformer_layer = Equiformer(dim=args.MLP_hidden, dim_head=48, num_neighbors=16,
-                                           valid_radius=5.0)
-        self.conv = MHNNSConv(args.MLP_hidden, mlp1_layers=self.mlp1_layers,
-                              mlp2_layers=self.mlp2_layers, mlp3_layers=self.mlp3_layers,
-                              aggr=args.aggregate, dropout=args.dropout,
-                              normalization=args.normalization)
-        self.mlp_out = MLP(in_channels=args.MLP_hidden, hidden_channels=args.output_hidden,
-                           out_channels=num_target, num_layers=args.output_num_layers,
-                           dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
-
-    def reset_parameters(self):
-        self.conv.reset_parameters()
-        self.mlp_out.reset_parameters()
-
-    def forward(self, data, taps=None, head=None):
-        index = HyperIndex.from_batch(data)
-        x = self.atom_encoder(data.x)
-        if taps is not None:
-            taps["atom_encoder"] = x
-        x = self.equiformer_layer(x, data.pos, index)
-        if taps is not None:
-            taps["front_end"] = x
-        x0 = x
-        res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
-        fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
-        x = _conv_layers(self, x, index, x0, res, fuse_act, taps)
-        return readout(self.mlp_out, self.dropout(x), index, taps, head)
-
-
-class _PairedBase(nn.Module):
-    """``mhnn`` (mhnn.py:11-81) and ``egnn_equihnn`` (equihnn_egnn.py:12-95): ONE shared MHNNConv
-    applied L times; nodes and hyperedges of order > 2 are pooled per molecule and concatenated.
-    The reference sizes the hyperedge pool by ``he_batch.max()+1`` and fails in ``torch.cat`` when the
-    last molecules of a batch have no such hyperedge; here they get a zero row."""
-
-    def __init__(self, num_target, args, with_egnn: bool):
-        super().__init__()
-        self.act = _ACT[args.activation]()
-        self.dropout = nn.Dropout(args.dropout)
-        self.mlp1_layers = args.MLP1_num_layers
-        self.mlp2_layers = args.MLP2_num_layers
-        self.mlp3_layers = args.MLP3_num_layers
-        self.mlp4_layers = args.MLP4_num_layers
-        self.nlayer = args.All_num_layers
-        if with_egnn:
-            self.egnn_layer = EGNN(dim=args.MLP_hidden, num_nearest_neighbors=16)
-        self.atom_encoder = AtomEncoder(emb_dim=args.MLP_hidden)
-        self.bond_encoder = BondEncoder(6, args.MLP_hidden)
-        self.conv = MHNNConv(args.MLP_hidden, mlp1_layers=self.mlp1_layers, mlp2_layers=self.mlp2_layers,
-                             mlp3_layers=self.mlp3_layers, mlp4_layers=self.mlp4_layers,
-                             aggr=args.aggregate, dropout=args.dropout, normalization=args.normalization)
-        self.mlp_out = MLP(in_channels=args.MLP_hidden * 2, hidden_channels=args.output_hidden * 2,
-                           out_channels=num_target, num_layers=args.output_num_layers,
-                           dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
-        self.with_egnn = with_egnn
-
-    def _front(self, data, index, taps):
-        x = self.atom_encoder(data.x)
-        if self.with_egnn:
-            x = self.egnn_layer(x, data.pos, index)
-            if taps is not None:
-                taps["front_end"] = x
-        return x
-
-    def forward(self, data, taps=None, head=None):
-        index = HyperIndex.from_batch(data)
-        x = self._front(data, index, taps)
+        x = self._apply_front(data, index, taps)
         e = self.bond_encoder(data.edge_attr)
         with _merged_scope([self.conv], x, e):      # the shared layer's weight-level products once per step
             for i in range(self.nlayer):
@@ -234,7 +185,6 @@ class _PairedBase(nn.Module):
 
     def _pool(self, x, e, index, data):
         """[B, 2C]: node rows and hyperedge rows of order > 2 summed per molecule, side by side (mhnn.py:58,72)."""
-        from . import ops
         if self.fused_pool:
             return ops.pool_pair(x, e, index, data.n_e, data.e_order)
         xp = pool_sum(x, index)
@@ -244,134 +194,94 @@ class _PairedBase(nn.Module):
         return torch.cat((xp, ep), -1)
 
 
+class _MTail(_Wrapper):
+    """The M tail: L unshared MHNNConv layers + BatchNorm1d on node rows -> pool -> head.  The host-side per-molecule
+    ``.item()`` loop of mhnn.py:196-199 builds a tensor the model never uses; it is not reproduced (it costs B device syncs
+    per step)."""
+
+    # Whether the layer loop runs inside ops.merged_scope (all layers' weight-level products in one launch each way).
+    # True on ``mhnnm`` alone: the three methods with a front-end have never opened it, and that was inherited from the
+    # order the code was written in, not measured.  Turning it on for them changes their launch sequence and needs a
+    # number behind it (DESIGN.md section 7.3).
+    merged_layers = False
+
+    def __init__(self, num_target, args):
+        super().__init__(args)
+        self.mlp4_layers = args.MLP4_num_layers
+        self.atom_encoder = AtomEncoder(emb_dim=args.MLP_hidden)
+        self.bond_encoder = BondEncoder(6, args.MLP_hidden)
+        self.layers = nn.ModuleList()
+        self.batch_norms = nn.ModuleList()
+        for _ in range(self.nlayer):
+            self.layers.append(_mhnn_conv(args))
+            self.batch_norms.append(nn.BatchNorm1d(args.MLP_hidden))
+        self.mlp_out = _head(num_target, args)
+        if not self._embeds:
+            del self.atom_encoder   # never used, but its random draws come before those of every module after it
+        self._build_front(args)
+
+    def forward(self, data, taps=None, head=None):
+        index = HyperIndex.from_batch(data)
+        x = self._apply_front(data, index, taps)
+        e = self.bond_encoder(data.edge_attr)
+        mask = real_row_mask(data, x)   # padded batch: BatchNorm statistics over the real atoms only
+        with _merged_scope(self.layers, x, e) if self.merged_layers else contextlib.nullcontext():
+            for i, layer in enumerate(self.layers):
+                x, e = layer(x, e, index)
+                # (the ReLU behind the normalisation rides its launches, unless the pre-activation value is tapped)
+                fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
+                x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
+                if taps is not None:
+                    taps[f"bn{i}"] = x
+                if i != self.nlayer - 1:  # no activation after the last layer, mhnn.py:208-214
+                    x, e = (x if fuse else self.act(x)), self.act(e)
+                x, e = self.dropout(x), self.dropout(e)
+        return readout(self.mlp_out, x, index, taps, head)
+
+
+@registry.register_model("mhnns")
+class MHNNS(_STail):
+    """mhnn.py:84-141: shared MHNNSConv x L on atom embeddings (no geometric front-end)."""
+
+
+@registry.register_model("egnn_equihnns")
+class EGNNEquiHNNS(_STail):
+    """equihnn_egnn.py:98-169: AtomEncoder -> EGNN (once) -> shared MHNNSConv x L -> pool -> head."""
+    front = _EGNN
+
+
+@registry.register_model("equiformer_equihnns")
+class EquiformerEquiHNNS(_STail):
+    """equihnn_equiformer.py:12-93: AtomEncoder -> Equiformer (once, type-0 output) -> shared
+    MHNNSConv x L -> pool -> head.  The reference keeps a leading batch dim of 1 through the conv /
+    pool / head (equihnn_equiformer.py:82-85) and flattens at the end; values are identical."""
+    front = _EQUIFORMER
+
+
+@registry.register_model("faformer_equihnns")
+class FAFormerEquiHNNS(_STail):
+    """equihnn_fa_former.py:105-184: AtomEncoder -> FAFormer (once) -> shared MHNNSConv x L -> pool
+    -> head.  Note the reference keeps proj_drop = attn_drop = 0.1 inside FAFormer in training mode
+    (fa_former_layer.py:20-21), whatever ``--dropout`` says."""
+    front = _FAFORMER
+
+
+@registry.register_model("visnet_equihnns")
+class VisNetEquiHNNS(_STail):
+    """equihnn_visnet.py:92-158: ViSNet (once) -> shared MHNNSConv x L -> pool -> head."""
+    front = _VISNET
+
+
 @registry.register_model("mhnn")
 class MHNN(_PairedBase):
-    def __init__(self, num_target, args):
-        super().__init__(num_target, args, with_egnn=False)
+    """mhnn.py:11-81: AtomEncoder -> shared MHNNConv x L on (x, e) -> node and order > 2 hyperedge pools -> head."""
 
 
 @registry.register_model("egnn_equihnn")
 class EGNNEquiHNN(_PairedBase):
-    def __init__(self, num_target, args):
-        super().__init__(num_target, args, with_egnn=True)
-
-
-@registry.register_model("mhnns")
-class MHNNS(nn.Module):
-    """mhnn.py:84-141: shared MHNNSConv x L on atom embeddings (no geometric front-end)."""
-
-    def __init__(self, num_target, args):
-        super().__init__()
-        self.act = _ACT[args.activation]()
-        self.dropout = nn.Dropout(args.dropout)
-        self.mlp1_layers = args.MLP1_num_layers
-        self.mlp2_layers = args.MLP2_num_layers
-        self.mlp3_layers = args.MLP3_num_layers
-        self.nlayer = args.All_num_layers
-        self.atom_encoder = AtomEncoder(emb_dim=args.MLP_hidden)
-        self.conv = MHNNSConv(args.MLP_hidden, mlp1_layers=self.mlp1_layers, mlp2_layers=self.mlp2_layers,
-                              mlp3_layers=self.mlp3_layers, aggr=args.aggregate, dropout=args.dropout,
-                              normalization=args.normalization)
-        self.mlp_out = MLP(in_channels=args.MLP_hidden, hidden_channels=args.output_hidden,
-                           out_channels=num_target, num_layers=args.output_num_layers,
-                           dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
-
-    def reset_parameters(self):
-        self.conv.reset_parameters()
-        self.mlp_out.reset_parameters()
-
-    def forward(self, data, taps=None, head=None):
-        index = HyperIndex.from_batch(data)
-        x = self.atom_encoder(data.x)
-        x0 = x
-        res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
-        fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
-        x = _conv_layers(self, x, index, x0, res, fuse_act, taps)
-        return readout(self.mlp_out, self.dropout(x), index, taps, head)
-
-
-@registry.register_model("egnn_equihnnm")
-class EGNNEquiHNNM(MHNNM):
-    """equihnn_egnn.py:172-261: mhnnm with the EGNN front-end applied once to the atom embeddings."""
-
-    def __init__(self, num_target, args):
-        super().__init__(num_target, args)
-        self.egnn_layer = EGNN(dim=args.MLP_hidden, num_nearest_neighbors=16)
-
-    def forward(self, data, taps=None, head=None):
-        index = HyperIndex.from_batch(data)
-        x = self.egnn_layer(self.atom_encoder(data.x), data.pos, index)
-        if taps is not None:
-            taps["front_end"] = x
-        e = self.bond_encoder(data.edge_attr)
-        mask = real_row_mask(data, x)   # padded batch: BatchNorm statistics over the real atoms only
-        for i, layer in enumerate(self.layers):
-            x, e = layer(x, e, index)
-            fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
-            x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
-            if taps is not None:
-                taps[f"bn{i}"] = x
-            if i != self.nlayer - 1:
-                x, e = (x if fuse else self.act(x)), self.act(e)
-            x, e = self.dropout(x), self.dropout(e)
-        return readout(self.mlp_out, x, index, taps, head)
-
-
-@registry.register_model("faformer_equihnns")
-class FAFormerEquiHNNS(nn.Module):
-    """equihnn_fa_former.py:105-184: AtomEncoder -> FAFormer (once) -> shared MHNNSConv x L -> pool
-    -> head.  Note the reference keeps proj_drop = attn_drop = 0.1 inside FAFormer in training mode
-    (fa_former_layer.py:20-21), whatever ``--dropout`` says."""
-
-    def __init__(self, num_target, args):
-        super().__init__()
-        self.act = _ACT[args.activation]()
-        self.dropout = nn.Dropout(args.dropout)
-        self.mlp1_layers = args.MLP1_num_layers
-        self.mlp2_layers = args.MLP2_num_layers
-        self.mlp3_layers = args.MLP3_num_layers
-        self.nlayer = args.All_num_layers
-        self.atom_encoder = AtomEncoder(emb_dim=args.MLP_hidden)
-        self.fa_former = FAFormer(args.MLP_hidden, n_layers=2, n_heads=2, n_neighbors=16, valid_radius=5.0)
-        self.conv = MHNNSConv(args.MLP_hidden, mlp1_layers=self.mlp1_layers, mlp2_layers=self.mlp2_layers,
-                              mlp3_layers=self.mlp3_layers, aggr=args.aggregate, dropout=args.dropout,
-                              normalization=args.normalization)
-        self.mlp_out = MLP(in_channels=args.MLP_hidden, hidden_channels=args.output_hidden,
-                           out_channels=num_target, num_layers=args.output_num_layers,
-                           dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
-
-    def reset_parameters(self):
-        self.conv.reset_parameters()
-        self.mlp_out.reset_parameters()
-
-    def forward(self, data, taps=None, head=None):
-        index = HyperIndex.from_batch(data)
-        x = self.atom_encoder(data.x)
-        if taps is not None:
-            taps["atom_encoder"] = x
-        x = self.fa_former(x, data.pos, index, real_row_mask(data, x))
-        if taps is not None:
-            taps["front_end"] = x
-        x0 = x
-        res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
-        fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
-        x = _conv_layers(self, x, index, x0, res, fuse_act, taps)
-        return readout(self.mlp_out, self.dropout(x), index, taps, head)
-
-
-def _faformer(args):
-    """The wrappers' FAFormer (equihnn_fa_former.py:36-49,130-143,210-223)."""
-    return FAFormer(args.MLP_hidden, n_layers=2, n_heads=2, n_neighbors=16, valid_radius=5.0)
-
-
-def _faformer_front(model, data, index, taps):
-    x = model.atom_encoder(data.x)
-    if taps is not None:
-        taps["atom_encoder"] = x
-    x = model.fa_former(x, data.pos, index, real_row_mask(data, x))
-    if taps is not None:
-        taps["front_end"] = x
-    return x
+    """equihnn_egnn.py:12-95: mhnn with the EGNN front-end applied once to the atom embeddings."""
+    front = _EGNN
+    front_leads = True
 
 
 @registry.register_model("faformer_equihnn")
@@ -381,134 +291,42 @@ class FAFormerEquiHNN(_PairedBase):
     of order > 2 gets a zero row in the hyperedge pool; the reference sizes that pool by ``he_batch.max() + 1`` and fails in
     ``torch.cat`` (:101) when the LAST molecules of a batch have none.  The reference keeps proj_drop = attn_drop = 0.1
     inside FAFormer in training mode (fa_former_layer.py:20-21), whatever ``--dropout`` says."""
-
+    front = _FAFORMER
     fused_pool = True
-
-    def __init__(self, num_target, args):
-        super().__init__(num_target, args, with_egnn=False)
-        self.fa_former = _faformer(args)
-
-    def _front(self, data, index, taps):
-        return _faformer_front(self, data, index, taps)
-
-
-@registry.register_model("faformer_equihnnm")
-class FAFormerEquiHNNM(MHNNM):
-    """equihnn_fa_former.py:187-283: mhnnm with the FAFormer front-end applied once to the atom embeddings.  FAFormer keeps
-    its own proj_drop = attn_drop = 0.1 in training mode (fa_former_layer.py:20-21), whatever ``--dropout`` says."""
-
-    def __init__(self, num_target, args):
-        super().__init__(num_target, args)
-        self.fa_former = _faformer(args)
-
-    def forward(self, data, taps=None, head=None):
-        index = HyperIndex.from_batch(data)
-        x = _faformer_front(self, data, index, taps)
-        e = self.bond_encoder(data.edge_attr)
-        mask = real_row_mask(data, x)   # padded batch: BatchNorm statistics over the real atoms only
-        for i, layer in enumerate(self.layers):
-            x, e = layer(x, e, index)
-            fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
-            x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
-            if taps is not None:
-                taps[f"bn{i}"] = x
-            if i != self.nlayer - 1:
-                x, e = (x if fuse else self.act(x)), self.act(e)
-            x, e = self.dropout(x), self.dropout(e)
-        return readout(self.mlp_out, x, index, taps, head)
-
-
-def _visnet(args):
-    """The wrappers' ViSNet (equihnn_visnet.py:35-37,114-118,183-185)."""
-    return ViSNet(hidden_channels=args.MLP_hidden, lmax=2, max_num_neighbors=16)
-
-
-def _visnet_front(model, data, index, taps):
-    x = model.visnet_layer(data.x, data.pos, index)
-    if taps is not None:
-        taps["front_end"] = x
-    return x
 
 
 @registry.register_model("visnet_equihnn")
 class VisNetEquiHNN(_PairedBase):
     """equihnn_visnet.py:11-89: ViSNet (its own two AtomEncoders) -> shared MHNNConv x L -> node and order > 2 hyperedge
     pools -> head.  No AtomEncoder of its own."""
-
-    def __init__(self, num_target, args):
-        super().__init__(num_target, args, with_egnn=False)
-        del self.atom_encoder
-        self.visnet_layer = _visnet(args)
-
-    def _front(self, data, index, taps):
-        return _visnet_front(self, data, index, taps)
+    front = _VISNET
 
 
-@registry.register_model("visnet_equihnns")
-class VisNetEquiHNNS(nn.Module):
-    """equihnn_visnet.py:92-158: ViSNet (once) -> shared MHNNSConv x L -> pool -> head."""
+@registry.register_model("mhnnm")
+class MHNNM(_MTail):
+    """mhnn.py:144-218: L unshared MHNNConv layers + BatchNorm1d on atom embeddings (no geometric front-end)."""
+    merged_layers = True    # 1.30 -> 1.28 ms when the scope came in
 
-    def __init__(self, num_target, args):
-        super().__init__()
-        self.act = _ACT[args.activation]()
-        self.dropout = nn.Dropout(args.dropout)
-        self.mlp1_layers = args.MLP1_num_layers
-        self.mlp2_layers = args.MLP2_num_layers
-        self.mlp3_layers = args.MLP3_num_layers
-        self.nlayer = args.All_num_layers
-        self.visnet_layer = _visnet(args)
-        self.conv = MHNNSConv(args.MLP_hidden, mlp1_layers=self.mlp1_layers, mlp2_layers=self.mlp2_layers,
-                              mlp3_layers=self.mlp3_layers, aggr=args.aggregate, dropout=args.dropout,
-                              normalization=args.normalization)
-        self.mlp_out = MLP(in_channels=args.MLP_hidden, hidden_channels=args.output_hidden,
-                           out_channels=num_target, num_layers=args.output_num_layers,
-                           dropout=args.dropout, Normalization=args.normalization, InputNorm=False)
 
-    def reset_parameters(self):
-        self.conv.reset_parameters()
-        self.mlp_out.reset_parameters()
+@registry.register_model("egnn_equihnnm")
+class EGNNEquiHNNM(_MTail):
+    """equihnn_egnn.py:172-261: mhnnm with the EGNN front-end applied once to the atom embeddings."""
+    front = _EGNN
 
-    def forward(self, data, taps=None, head=None):
-        index = HyperIndex.from_batch(data)
-        x = _visnet_front(self, data, index, taps)
-        x0 = x
-        res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
-        fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
-        x = _conv_layers(self, x, index, x0, res, fuse_act, taps)
-        return readout(self.mlp_out, self.dropout(x), index, taps, head)
+
+@registry.register_model("faformer_equihnnm")
+class FAFormerEquiHNNM(_MTail):
+    """equihnn_fa_former.py:187-283: mhnnm with the FAFormer front-end applied once to the atom embeddings.  FAFormer keeps
+    its own proj_drop = attn_drop = 0.1 in training mode (fa_former_layer.py:20-21), whatever ``--dropout`` says."""
+    front = _FAFORMER
 
 
 @registry.register_model("visnet_equihnnm")
-class VisNetEquiHNNM(MHNNM):
+class VisNetEquiHNNM(_MTail):
     """equihnn_visnet.py:161-243: mhnnm with ViSNet in place of the AtomEncoder."""
-
-    def __init__(self, num_target, args):
-        super().__init__(num_target, args)
-        del self.atom_encoder
-        self.visnet_layer = _visnet(args)
-
-    def forward(self, data, taps=None, head=None):
-        index = HyperIndex.from_batch(data)
-        x = _visnet_front(self, data, index, taps)
-        e = self.bond_encoder(data.edge_attr)
-        mask = real_row_mask(data, x)   # padded batch: BatchNorm statistics over the real atoms only
-        for i, layer in enumerate(self.layers):
-            x, e = layer(x, e, index)
-            fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
-            x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
-            if taps is not None:
-                taps[f"bn{i}"] = x
-            if i != self.nlayer - 1:
-                x, e = (x if fuse else self.act(x)), self.act(e)
-            x, e = self.dropout(x), self.dropout(e)
-        return readout(self.mlp_out, x, index, taps, head)
+    front = _VISNET
 
 
-from .baseline_2d import GNN_2D  # noqa: E402  (registers gin / gcn; constructed as GNN_2D(1, gnn_type=...))
+from .baseline_2d import GNN_2D  # noqa: E402, F401  (registers gin / gcn; constructed as GNN_2D(1, gnn_type=...))
 
-MODELS = {"egnn_equihnns": EGNNEquiHNNS, "mhnnm": MHNNM, "equiformer_equihnns": EquiformerEquiHNNS,
-          "faformer_equihnns": FAFormerEquiHNNS,
-          "mhnn": MHNN, "mhnns": MHNNS, "egnn_equihnn": EGNNEquiHNN, "egnn_equihnnm": EGNNEquiHNNM,
-          "gin": GNN_2D, "gcn": GNN_2D,
-          "visnet_equihnn": VisNetEquiHNN, "visnet_equihnns": VisNetEquiHNNS, "visnet_equihnnm": VisNetEquiHNNM,
-          "faformer_equihnn": FAFormerEquiHNN, "faformer_equihnnm": FAFormerEquiHNNM}
+MODELS = dict(registry.mapping["model_name_mapping"])   # the thirteen above plus gin / gcn
