@@ -1,6 +1,8 @@
 """equihgnn_amd: the MI355X-native training hot path of HySonLab/EquiHGNN."""
 import os
 
+from .precision import get_float32_matmul_precision, set_float32_matmul_precision  # noqa: F401
+
 
 def enable_tuned_gemms(tuning: bool = False) -> bool:
     """Let PyTorch's TunableOp use the GEMM selections committed for gfx950 (``tuned/tunableop_gfx950.csv``): the library's

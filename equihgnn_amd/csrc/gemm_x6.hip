@@ -32,6 +32,10 @@
 // columns of one output row, so the epilogue reads the addend / bias and stores the result as float4.
 //
 // Results are bitwise reproducible (fixed k order, no atomics, no split-K).  Up to 8 problems share a launch.
+//
+// This file is compiled three times, so that the instantiations of the three precision modes build side by side: as itself
+// (GX_PLANES undefined: the six-product kernels and the whole host side) and through gemm_bf16_high.hip / gemm_bf16_medium.hip
+// (GX_PLANES = 2 / 1: the kernels of that mode and their launch function gx_launch_planes2 / 1, nothing else).
 #include <cstdlib>
 #include <type_traits>
 
@@ -151,7 +155,8 @@ struct LoadKC {
             r.v[i] = ok ? x : f4_zero();
         }
     }
-    static __device__ __forceinline__ void store(const Regs& r, uint4* __restrict__ s) {
+    template <int NPL>
+    static __device__ __forceinline__ void store(const Regs& r, uint4* __restrict__ s) {   // the first NPL planes (the others' arithmetic is dead code)
         const int t = threadIdx.x & 255, k4 = t & 7;
         uint2* d = reinterpret_cast<uint2*>(s);
 #pragma unroll
@@ -161,8 +166,8 @@ struct LoadKC {
             split_pair(r.v[i].x, r.v[i].y, a0, a1, a2);
             split_pair(r.v[i].z, r.v[i].w, b0, b1, b2);
             d[slot_index<R>(0, row, k4) * 2 + (k4 & 1)] = make_uint2(a0, b0);
-            d[slot_index<R>(1, row, k4) * 2 + (k4 & 1)] = make_uint2(a1, b1);
-            d[slot_index<R>(2, row, k4) * 2 + (k4 & 1)] = make_uint2(a2, b2);
+            if constexpr (NPL > 1) d[slot_index<R>(1, row, k4) * 2 + (k4 & 1)] = make_uint2(a1, b1);
+            if constexpr (NPL > 2) d[slot_index<R>(2, row, k4) * 2 + (k4 & 1)] = make_uint2(a2, b2);
         }
     }
 };
@@ -204,6 +209,7 @@ struct LoadKS {
                 r.v[i][kk] = ok ? x : make_float2(0.f, 0.f);
             }
     }
+    template <int NPL>
     static __device__ __forceinline__ void store(const Regs& r, uint4* __restrict__ s) {
         const int t = threadIdx.x & 255, k4 = t >> 5;
         uint2* d = reinterpret_cast<uint2*>(s);
@@ -214,13 +220,13 @@ struct LoadKS {
             split_pair(r.v[i][0].x, r.v[i][1].x, a0, a1, a2);
             split_pair(r.v[i][2].x, r.v[i][3].x, b0, b1, b2);
             d[slot_index<R>(0, row, k4) * 2 + (k4 & 1)] = make_uint2(a0, b0);
-            d[slot_index<R>(1, row, k4) * 2 + (k4 & 1)] = make_uint2(a1, b1);
-            d[slot_index<R>(2, row, k4) * 2 + (k4 & 1)] = make_uint2(a2, b2);
+            if constexpr (NPL > 1) d[slot_index<R>(1, row, k4) * 2 + (k4 & 1)] = make_uint2(a1, b1);
+            if constexpr (NPL > 2) d[slot_index<R>(2, row, k4) * 2 + (k4 & 1)] = make_uint2(a2, b2);
             split_pair(r.v[i][0].y, r.v[i][1].y, a0, a1, a2);
             split_pair(r.v[i][2].y, r.v[i][3].y, b0, b1, b2);
             d[slot_index<R>(0, row + 1, k4) * 2 + (k4 & 1)] = make_uint2(a0, b0);
-            d[slot_index<R>(1, row + 1, k4) * 2 + (k4 & 1)] = make_uint2(a1, b1);
-            d[slot_index<R>(2, row + 1, k4) * 2 + (k4 & 1)] = make_uint2(a2, b2);
+            if constexpr (NPL > 1) d[slot_index<R>(1, row + 1, k4) * 2 + (k4 & 1)] = make_uint2(a1, b1);
+            if constexpr (NPL > 2) d[slot_index<R>(2, row + 1, k4) * 2 + (k4 & 1)] = make_uint2(a2, b2);
         }
     }
 };
@@ -313,15 +319,27 @@ __device__ __forceinline__ int xcd_remap(int b, int n) {
 // against 19.5-19.6 ms.  (EQH_X6_TILES_PER_WG=n caps a workgroup's tiles for A/B runs: 1 is the old launch; 4 loses to both --
 // 304 workgroups of 4 tiles on 256 CUs are two rounds.)  The two-per-CU configurations keep one tile per workgroup: their CU
 // partner covers the prologue.
-template <int MT, int NT, int S, int MINW, bool A_KS, bool B_KS, int WR = 2, int WC = 2, bool B_PRE = false>
+//
+// NPL: the bf16 planes kept per operand (the matmul precision modes of hg_gemm_bf16_batch).  3: the six products above, fp32 grade.
+// 2 ("high"): planes 0 and 1, the three products a0b1, a1b0, a0b0 -- every dropped term is below 2^-14 |a||b|.  1 ("medium"): plane 0
+// alone, one product -- a bf16 x bf16 product with truncated operands, |a - a0| < 2^-7 |a|.  The stagers compute and store NPL planes
+// (split_pair's unused planes are dead code), a stage is NPL / 3 of the full one, the multipliers read NPL fragments per operand.
+template <int MT, int NT, int S, int MINW, bool A_KS, bool B_KS, int WR = 2, int WC = 2, bool B_PRE = false, int NPL = 3>
 __global__ void __launch_bounds__(64 * WR * WC + GX_STAGERS, MINW)
 k_gemm_x6(const GxBatch batch) {
+    static_assert(NPL >= 1 && NPL <= 3 && (!B_PRE || NPL == 3), "one to three planes; a pre-split image is read whole");
     constexpr int BM = 32 * WR * MT, BN = 32 * WC * NT;
     constexpr int NMT = 64 * WR * WC;                                              // multiplying threads
-    constexpr int SA = 3 * (BM / 32) * 2 * 64, SB = 3 * (BN / 32) * 2 * 64;       // uint4 per stage
+    constexpr int SA = NPL * (BM / 32) * 2 * 64, SB = NPL * (BN / 32) * 2 * 64;   // uint4 per stage
     constexpr bool PERSIST = MINW <= 4;
     constexpr int RING = S * (SA + SB);
-    __shared__ uint4 s_mem[RING];                                                  // ring of stages, each [A | B]
+    // the epilogue's pieces start in the last ring stage (below); where a stage of fewer planes is too small for them they run on
+    // into EP_EXTRA, which no stager writes (none with three planes: the layout of the six-product kernel is unchanged)
+    constexpr int EP_LD = 36;                                                      // floats per staged row (32 + 4: conflict-free b128 writes)
+    constexpr int EP_U4 = (NMT / 64) * 32 * EP_LD / 4;
+    constexpr int EP_EXTRA = EP_U4 > SA + SB ? EP_U4 - (SA + SB) : 0;
+    static_assert(NPL < 3 || EP_EXTRA == 0, "the epilogue pieces of the six-product kernel fit one ring stage");
+    __shared__ uint4 s_mem[RING + EP_EXTRA];                                       // ring of stages, each [A | B]
 
     // Two roles, one barrier per K step (and one before a tile's first).  During step k the four MULTIPLIERS (wavefronts 0-3)
     // read the fragments of tile k from ring stage k % S and issue its MFMAs; the STAGERS (wavefronts 4-11, two groups of four)
@@ -375,11 +393,11 @@ k_gemm_x6(const GxBatch batch) {
                 // requested BEFORE the A tile is split, stored behind it
                 typename LB::Regs tb;
                 lb.fetch(tb, kt0 + w);
-                LA::store(ra, st);
+                LA::template store<NPL>(ra, st);
                 lb.store(tb, st + SA);
             } else {
-                LA::store(ra, st);
-                LB::store(rb, st + SA);
+                LA::template store<NPL>(ra, st);
+                LB::template store<NPL>(rb, st + SA);
             }
         };
         // tiles 0 .. S-2 before the first barrier (even tiles by group 0, odd ones by group 1), and the request for
@@ -425,14 +443,14 @@ k_gemm_x6(const GxBatch batch) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
 
-    // one K step from ring stage k % S is two 16-deep halves, each 3 x (MT + NT) fragment reads and 6 x MT x NT MFMAs (smallest
-    // terms first).  (Measured and not kept, round 6: with two multiplying wavefronts per SIMD, the second one running half a step
+    // one K step from ring stage k % S is two 16-deep halves, each NPL x (MT + NT) fragment reads and 6 / 3 / 1 x MT x NT MFMAs (the
+    // products with i + j < NPL, smallest terms first).  (Measured and not kept, round 6: with two multiplying wavefronts per SIMD, the second one running half a step
     // late -- a step's second-half fragments held in registers across the barrier and multiplied while the first one reads:
     // [246 k x 256].[256 x 256] 232 against 205 us; the two in step, reading together and multiplying together, are the faster form.)
-    bf16x8 fa[3][MT], fb[3][NT];
+    bf16x8 fa[NPL][MT], fb[NPL][NT];
     auto rd = [&](const uint4* __restrict__ sa, const uint4* __restrict__ sb, int off) {
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
+        for (int p = 0; p < NPL; ++p) {
 #pragma unroll
             for (int m = 0; m < MT; ++m)
                 fa[p][m] = __builtin_bit_cast(bf16x8, sa[(p * (BM / 32) + wm * MT + m) * 128 + off]);
@@ -447,9 +465,11 @@ k_gemm_x6(const GxBatch batch) {
             acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[PB][n], fa[PA][m], acc[m][n], 0, 0, 0);
     auto mm = [&]() {
 #ifndef GX_ABLATE_MFMA
-        GX_MM(1, 1) GX_MM(0, 2) GX_MM(2, 0) GX_MM(0, 1) GX_MM(1, 0) GX_MM(0, 0)
+        if constexpr (NPL == 3) { GX_MM(1, 1) GX_MM(0, 2) GX_MM(2, 0) GX_MM(0, 1) GX_MM(1, 0) GX_MM(0, 0) }
+        else if constexpr (NPL == 2) { GX_MM(0, 1) GX_MM(1, 0) GX_MM(0, 0) }
+        else { GX_MM(0, 0) }
 #else
-        _Pragma("unroll") for (int p = 0; p < 3; ++p) {
+        _Pragma("unroll") for (int p = 0; p < NPL; ++p) {
             _Pragma("unroll") for (int m = 0; m < MT; ++m) { asm volatile("" :: "v"(fa[p][m])); }
             _Pragma("unroll") for (int n = 0; n < NT; ++n) { asm volatile("" :: "v"(fb[p][n])); }
         }
@@ -485,8 +505,6 @@ k_gemm_x6(const GxBatch batch) {
     const float* __restrict__ bias = P.bias;
     // The pieces lie in ring stage S - 1: the stagers, who after a tile's last barrier go on to the next tile of the workgroup, write
     // its first S - 1 stages (0 .. S - 2) before the barrier that the multipliers reach only after this epilogue.
-    constexpr int EP_LD = 36;                                  // floats per staged row (32 + 4: conflict-free b128 writes)
-    static_assert((NMT / 64) * 32 * EP_LD * 4 <= (SA + SB) * 16, "the epilogue pieces fit one ring stage");
     float* ep = reinterpret_cast<float*>(s_mem + (S - 1) * (SA + SB)) + wave * (32 * EP_LD);
     int le = lane;
     if constexpr (PERSIST) asm volatile("" : "+v"(le));       // (the epilogue's lane arithmetic stays in the epilogue: hoisted out of the
@@ -609,7 +627,7 @@ k_gemm_x6(const GxBatch batch) {
     GX_STAMP_CLOCK(36);
 }
 
-template <int MT, int NT, int S, int MINW, int WR = 2, int WC = 2>
+template <int MT, int NT, int S, int MINW, int WR = 2, int WC = 2, int NPL = 3>
 int launch(const GxBatch& b, bool a_ks, bool b_ks, hipStream_t stream, bool b_pre = false) {
     // the one-per-CU configurations: one workgroup per CU walks its share of the tiles (a multiple of 8 workgroups: a workgroup's
     // tiles stay on its XCD's L2)
@@ -626,20 +644,61 @@ int launch(const GxBatch& b, bool a_ks, bool b_ks, hipStream_t stream, bool b_pr
     }
     const dim3 grid(n_wg), block(64 * WR * WC + GX_STAGERS);
     if (b_pre) {
-        if (a_ks) return EQH_ERR_ARG;
-        hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, false, false, WR, WC, true>), grid, block, 0, stream, b);
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
+        if constexpr (NPL == 3) {
+            if (a_ks) return EQH_ERR_ARG;
+            hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, false, false, WR, WC, true>), grid, block, 0, stream, b);
+            EQH_CHECK_LAUNCH();
+            return EQH_OK;
+        } else {
+            return EQH_ERR_ARG;          // (a pre-split image goes with all six products only)
+        }
     }
-    if (!a_ks && !b_ks) hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, false, false, WR, WC>), grid, block, 0, stream, b);
-    else if (!a_ks && b_ks) hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, false, true, WR, WC>), grid, block, 0, stream, b);
-    else if (a_ks && b_ks) hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, true, true, WR, WC>), grid, block, 0, stream, b);
-    else hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, true, false, WR, WC>), grid, block, 0, stream, b);
+    if (!a_ks && !b_ks) hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, false, false, WR, WC, false, NPL>), grid, block, 0, stream, b);
+    else if (!a_ks && b_ks) hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, false, true, WR, WC, false, NPL>), grid, block, 0, stream, b);
+    else if (a_ks && b_ks) hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, true, true, WR, WC, false, NPL>), grid, block, 0, stream, b);
+    else hipLaunchKernelGGL((k_gemm_x6<MT, NT, S, MINW, true, false, WR, WC, false, NPL>), grid, block, 0, stream, b);
     EQH_CHECK_LAUNCH();
     return EQH_OK;
 }
 
+// the launch of tile `id` with NPL planes.  Ring depth: three planes as before (two stages on the one-per-CU tiles).  With fewer planes
+// the same two stages, a ring of 2/3 or 1/3 the bytes: EQH_BF16_RING=deep (read at every call: same-process A/B runs) spends the
+// freed LDS on a deeper ring instead -- three stages with two planes, four with one -- on the one-per-CU tiles.
+template <int NPL>
+int launch_tile(int id, const GxBatch& b, bool a_ks, bool b_ks, hipStream_t stream, bool b_pre) {
+    if constexpr (NPL == 3) {
+        if (id == 512) return launch<2, 2, 2, 4, 2, 4>(b, a_ks, b_ks, stream, b_pre);
+        if (id == 513) return launch<2, 2, 2, 4, 4, 2>(b, a_ks, b_ks, stream, b_pre);
+        if (id == 256) {
+            static const bool deep = [] { const char* e = getenv("EQH_X6_DEEP"); return e && e[0] == '1'; }();   // three ring stages (A/B runs)
+            return deep ? launch<2, 2, 3, 3>(b, a_ks, b_ks, stream, b_pre) : launch<2, 2, 2, 3>(b, a_ks, b_ks, stream, b_pre);
+        }
+        if (id == 128) return launch<2, 1, 2, 6>(b, a_ks, b_ks, stream, b_pre);   // 6 waves / SIMD = 2 blocks / CU
+        return launch<1, 1, 3, 6>(b, a_ks, b_ks, stream, b_pre);
+    } else {
+        constexpr int SD = NPL == 2 ? 3 : 4;
+        const char* e = getenv("EQH_BF16_RING");
+        const bool deep = e && e[0] == 'd';
+        if (id == 512) return deep ? launch<2, 2, SD, 4, 2, 4, NPL>(b, a_ks, b_ks, stream, b_pre) : launch<2, 2, 2, 4, 2, 4, NPL>(b, a_ks, b_ks, stream, b_pre);
+        if (id == 513) return deep ? launch<2, 2, SD, 4, 4, 2, NPL>(b, a_ks, b_ks, stream, b_pre) : launch<2, 2, 2, 4, 4, 2, NPL>(b, a_ks, b_ks, stream, b_pre);
+        if (id == 256) return deep ? launch<2, 2, SD, 3, 2, 2, NPL>(b, a_ks, b_ks, stream, b_pre) : launch<2, 2, 2, 3, 2, 2, NPL>(b, a_ks, b_ks, stream, b_pre);
+        if (id == 128) return launch<2, 1, 2, 6, 2, 2, NPL>(b, a_ks, b_ks, stream, b_pre);
+        return launch<1, 1, 3, 6, 2, 2, NPL>(b, a_ks, b_ks, stream, b_pre);
+    }
+}
+
 }  // namespace
+
+#ifdef GX_PLANES
+// (the batch goes by address: GxBatch lives in each translation unit's own unnamed namespace, the same layout in all three)
+#define GX_CAT_(a, b) a##b
+#define GX_CAT(a, b) GX_CAT_(a, b)
+int GX_CAT(gx_launch_planes, GX_PLANES)(int id, const void* batch, bool a_ks, bool b_ks, hipStream_t stream) {
+    return launch_tile<GX_PLANES>(id, *static_cast<const GxBatch*>(batch), a_ks, b_ks, stream, false);
+}
+#else
+int gx_launch_planes2(int id, const void* batch, bool a_ks, bool b_ks, hipStream_t stream);   // gemm_bf16_high.hip
+int gx_launch_planes1(int id, const void* batch, bool a_ks, bool b_ks, hipStream_t stream);   // gemm_bf16_medium.hip
 
 #ifdef GX_STAMPS
 extern "C" int hg_gemm_x6_debug_stamps(void* buf) {
@@ -752,8 +811,9 @@ extern "C" size_t hg_gemm_x6_workspace_bytes(int32_t n_problems, const HgGemmPro
     return total;
 }
 
-extern "C" int hg_gemm_x6_batch(int32_t n_problems, const HgGemmProblem* pr, int32_t tile, void* workspace, size_t workspace_bytes,
-                                void* stream_) {
+// the launch behind hg_gemm_x6_batch (planes = 3) and hg_gemm_bf16_batch (planes = 3, 2, 1 for 6, 3, 1 products)
+static int gx_batch(int32_t n_problems, const HgGemmProblem* pr, int32_t tile, int planes, void* workspace, size_t workspace_bytes,
+                    void* stream_) {
     if (n_problems <= 0 || n_problems > GX_MAXP || !pr) return EQH_ERR_ARG;
     GxBatch b;
     b.n = n_problems;
@@ -763,6 +823,7 @@ extern "C" int hg_gemm_x6_batch(int32_t n_problems, const HgGemmProblem* pr, int
         const HgGemmProblem& q = pr[i];
         if (q.m < 0 || q.n <= 0 || q.k <= 0 || !q.a || (!q.b && !q.b_packed) || !q.c) return EQH_ERR_ARG;
         if ((q.b_packed != nullptr) != b_pre) return EQH_ERR_ARG;                       // one B form per launch
+        if (b_pre && planes != 3) return EQH_ERR_ARG;                                   // a pre-split image: all six products only
         if (b_pre && ((q.k & 31) || q.trans_a || !eqh_aligned16(q.b_packed))) return EQH_ERR_ARG;   // whole K steps of 32
         if ((q.trans_a != 0) != a_ks || (q.trans_b == 0) != b_ks) return EQH_ERR_ARG;   // one operand layout per launch
         if (q.m >= (1ll << 31) - 256) return EQH_ERR_RANGE;
@@ -827,15 +888,8 @@ extern "C" int hg_gemm_x6_batch(int32_t n_problems, const HgGemmProblem* pr, int
     for (int i = n_problems; i < GX_MAXP; ++i) b.p[i] = b.p[0], b.p[i].first_tile = 0x7fffffff;
     b.total_tiles = (int)first;
     if (first == 0) return EQH_OK;
-    int rc;
-    if (id == 512) rc = launch<2, 2, 2, 4, 2, 4>(b, a_ks, b_ks, stream, b_pre);
-    else if (id == 513) rc = launch<2, 2, 2, 4, 4, 2>(b, a_ks, b_ks, stream, b_pre);
-    else if (id == 256) {
-        static const bool deep = [] { const char* e = getenv("EQH_X6_DEEP"); return e && e[0] == '1'; }();   // three ring stages (A/B runs)
-        rc = deep ? launch<2, 2, 3, 3>(b, a_ks, b_ks, stream, b_pre) : launch<2, 2, 2, 3>(b, a_ks, b_ks, stream, b_pre);
-    }
-    else if (id == 128) rc = launch<2, 1, 2, 6>(b, a_ks, b_ks, stream, b_pre);   // 6 waves / SIMD = 2 blocks / CU
-    else rc = launch<1, 1, 3, 6>(b, a_ks, b_ks, stream, b_pre);
+    int rc = planes == 3 ? launch_tile<3>(id, b, a_ks, b_ks, stream, b_pre)
+             : planes == 2 ? gx_launch_planes2(id, &b, a_ks, b_ks, stream) : gx_launch_planes1(id, &b, a_ks, b_ks, stream);
     if (rc) return rc;
     // split-K problems: c = beta * d + sum of the slabs, in slab order (bitwise reproducible); beta * d with d == c and
     // beta == 1 is the accumulating form the weight gradients use
@@ -849,3 +903,15 @@ extern "C" int hg_gemm_x6_batch(int32_t n_problems, const HgGemmProblem* pr, int
     }
     return EQH_OK;
 }
+
+extern "C" int hg_gemm_x6_batch(int32_t n_problems, const HgGemmProblem* pr, int32_t tile, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    return gx_batch(n_problems, pr, tile, 3, workspace, workspace_bytes, stream);
+}
+
+extern "C" int hg_gemm_bf16_batch(int32_t n_problems, const HgGemmProblem* pr, int32_t tile, int32_t products, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    if (products != 6 && products != 3 && products != 1) return EQH_ERR_ARG;     // before anything is looked at or launched
+    return gx_batch(n_problems, pr, tile, products == 6 ? 3 : products == 3 ? 2 : 1, workspace, workspace_bytes, stream);
+}
+#endif  // !GX_PLANES

@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from .. import hip
+from .. import hip, precision
 from ._base import (_f32c, _ptr, _row_view, _stream, _workspace, timed)
 
 
@@ -21,7 +21,7 @@ from ._base import (_f32c, _ptr, _row_view, _stream, _workspace, timed)
 # ------------------------------------------------------------------------------------------------------------------
 @dataclass
 class GemmProblem:
-    """c = act(alpha * op(a) @ op(b) + beta * d + bias); see hg_gemm_x6_batch in include/equihgnn_hip.h.
+    """c = act(alpha * op(a) @ op(b) + beta * d + bias); see hg_gemm_x6_batch / hg_gemm_bf16_batch in include/equihgnn_hip.h.
     ``trans_a``: a is stored [K, M]; ``trans_b``: b is stored [N, K] (an nn.Linear weight).  ``d`` may be ``out``."""
 
     a: torch.Tensor
@@ -128,8 +128,11 @@ def gemm_batch(problems):
     L = hip.lib()
     ws_bytes = L.hg_gemm_x6_workspace_bytes(n, arr, GEMM_TILE)
     ws = _workspace(ws_bytes, dev) if ws_bytes else None
-    timed("k_gemm_x6", flops, lambda: hip.check(L.hg_gemm_x6_batch(n, arr, GEMM_TILE, _ptr(ws), ws_bytes, _stream(dev)),
-                                               "hg_gemm_x6_batch"))
+    # the matmul precision mode, read at call time: 6, 3 or 1 bf16 products per fp32 product (6 is hg_gemm_x6_batch bit for bit;
+    # a pre-split image holds three planes and keeps all six)
+    products = 6 if pre_all else precision.products()
+    timed("k_gemm_x6", flops, lambda: hip.check(L.hg_gemm_bf16_batch(n, arr, GEMM_TILE, products, _ptr(ws), ws_bytes, _stream(dev)),
+                                               "hg_gemm_bf16_batch"))
     return outs
 
 
@@ -173,7 +176,9 @@ def gemm(a, b, trans_a=False, trans_b=True, bias=None, d=None, alpha=1.0, beta=1
 # tools/gemm_bench.py -> profiles/r03_gemm_bench.txt): from ~4 M output elements per launch it is 7-37 % faster
 # ([15 k x 256].[256 x 256] 18.6 against 20.0 us, [15 k x 512].[512 x 1024] 84 against 133 us, 150-215 against 105-135
 # TFLOP/s at the Molecule3D / PCQM / Equiformer sizes); below that -- the [4.7 k x 256] x [256 x 256] products of a QM9
-# batch, one workgroup per CU and eight K steps -- the tuned library is 10-15 % ahead.
+# batch, one workgroup per CU and eight K steps -- the tuned library is 10-15 % ahead.  (The same threshold under the matmul
+# precision modes "high" / "medium": they are faster than six products at every shape measured above it --
+# profiles/matmul_precision_bench.json -- and the crossover below it was not measured again.)
 X6_MIN_OUTPUTS = int(os.environ.get("EQH_X6_MIN_OUTPUTS", 3_500_000))
 X6_MAX_K = 8192
 X6_DEEP_ROWS = 32768        # weight gradients dY^T X over at least this many rows: the split-K form of the x6 kernel

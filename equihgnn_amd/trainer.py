@@ -18,6 +18,8 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .precision import get_float32_matmul_precision
+
 
 def _world() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -309,9 +311,11 @@ class GraphedTrainStep:
 
     @staticmethod
     def _key(b):
+        # (the matmul precision mode is part of the key: a graph replays the arithmetic it was captured under)
+        mode = get_float32_matmul_precision()
         if not hasattr(b, "edge_index0"):       # a 2-D batch (batch.GBatch): atoms, edges, molecules
-            return (b.x.shape[0], b.edge_index.shape[1], b.y.shape[0])
-        return (b.x.shape[0], b.edge_attr.shape[0], b.edge_index0.shape[0], b.y.shape[0])
+            return (b.x.shape[0], b.edge_index.shape[1], b.y.shape[0], mode)
+        return (b.x.shape[0], b.edge_attr.shape[0], b.edge_index0.shape[0], b.y.shape[0], mode)
 
     def _loss(self, data):
         nb = getattr(data, "num_real_graphs", None) or data.y.shape[0]

@@ -113,6 +113,20 @@ size_t hg_gemm_x6_workspace_bytes(int32_t n_problems, const HgGemmProblem* probl
 int32_t hg_gemm_x6_choose_tile(int32_t n_problems, const HgGemmProblem* problems, int32_t with_workspace);
 int hg_gemm_x6_batch(int32_t n_problems, const HgGemmProblem* problems, int32_t tile, void* workspace, size_t workspace_bytes,
                      void* stream);
+/* The same GEMM at a chosen matmul precision (torch.set_float32_matmul_precision's grades): `products` = how many of the bf16 x bf16
+ * partial products of the split a = a0 + a1 + a2, b = b0 + b1 + b2 (each plane a truncation to the top 16 bits of what is left) are
+ * accumulated -- the ones with i + j < P, smallest first, in fp32:
+ *   6 (P = 3, "highest"): hg_gemm_x6_batch itself, bit for bit;
+ *   3 (P = 2, "high"):    a0b1 + a1b0 + a0b0;   |c - a.b| <= 3 * 2^-14 * sum_k |a||b|  (+ the fp32 accumulation error)
+ *   1 (P = 1, "medium"):  a0b0;                 |c - a.b| <= (2 * 2^-7 + 2^-14) * sum_k |a||b|  (+ the same)
+ * Any other value: EQH_ERR_ARG, nothing launched.  Operands and results stay fp32 in memory; the stagers compute and stage only P
+ * planes (a stage of P / 3 the LDS), the multiplying wavefronts issue P (P + 1) / 2 MFMAs per tile and K step.  Epilogues, split-K,
+ * batching, transposition and bitwise reproducibility as above.  A pre-split image (b_packed) holds three planes and goes with
+ * products == 6 only: EQH_ERR_ARG otherwise.  hg_gemm_x6_choose_tile and hg_gemm_x6_workspace_bytes hold for every mode: the
+ * split-K plan and the tile do not depend on `products`.  Not covered (fp32 grade under every mode): the panel kernels, the EGNN
+ * edge kernel's second Linear, the batched weight-gradient kernels. */
+int hg_gemm_bf16_batch(int32_t n_problems, const HgGemmProblem* problems, int32_t tile, int32_t products, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched small matrix products with riders (csrc/small_mm.hip), one launch for up to 8 problems:

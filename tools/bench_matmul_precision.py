@@ -1,0 +1,188 @@
+#!/usr/bin/env python3
+"""What the matmul precision modes give back (not part of bench.py).  Prints ONE JSON line and writes it to ``--out`` (default
+profiles/matmul_precision_bench.json).  Everything is timed in ONE process, "highest" beside the reduced modes:
+
+* three dense products through ``ops.gemm`` -- FAFormer's [246 k x 256].[256 x 256] (x W^T), the Equiformer's
+  [2432 x 256].[256 x 16384] (x W^T) and a K = 2052 input gradient dY W, [36864 x 2052].[2052 x 256] -- per mode and, for the
+  reduced modes, per ring depth (EQH_BF16_RING=deep: the LDS that fewer planes free spent on a deeper ring).  Each variant is
+  captured as a hipGraph of ``REPS`` launches; after a warm-up the graphs are replayed in interleaved blocks (variant 1, 2, ..,
+  1, 2, ..) between device events.  Per variant: the median block in microseconds per launch, ``spread`` = (max - min) / median
+  of its blocks, and ``vs_highest`` = its median / the median of "highest";
+* the replayed training step (GraphedTrainStep) of ``equiformer_equihnns`` (QM9-like, batch 128) and ``faformer_equihnns``
+  (PCQM-like, batch 512) per mode: one trainer, the mode switched between interleaved blocks (the trainer keys its graphs by
+  the mode, so each mode replays its own capture).
+
+``verdict`` says, per shape and mode, whether the mode is faster than "highest" by more than the two spreads.
+
+    python tools/bench_matmul_precision.py [--blocks 7] [--steps 10] [--warmup 5] [--skip-steps]
+"""
+from __future__ import annotations
+
+import argparse
+import gc
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+REPS = 10
+MODES = ("highest", "high", "medium")
+SHAPES = {"faformer_246k_256_256": (245760, 256, 256, True), "equiformer_2432_256_16384": (2432, 16384, 256, True),
+          "dyW_36864_2052_256": (36864, 256, 2052, False)}
+
+
+def _stat(ts):
+    med = statistics.median(ts)
+    return med, (max(ts) - min(ts)) / med
+
+
+def gemm_times(a, dev):
+    import equihgnn_amd
+    from equihgnn_amd import hip, ops
+    res = {}
+    for name, (M, N, K, tb) in SHAPES.items():
+        g = torch.Generator().manual_seed(0)
+        x = torch.randn(M, K, generator=g).to(dev)
+        w = torch.randn((N, K) if tb else (K, N), generator=g).to(dev)
+        out = torch.empty(M, N, device=dev)
+        graphs = {}
+        for mode in MODES:
+            for ring in (("base",) if mode == "highest" else ("base", "deep")):
+                equihgnn_amd.set_float32_matmul_precision(mode)
+                os.environ["EQH_BF16_RING"] = ring
+                for _ in range(3):
+                    ops.gemm(x, w, trans_b=tb, out=out)
+                torch.cuda.synchronize()
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr):
+                    for _ in range(REPS):
+                        ops.gemm(x, w, trans_b=tb, out=out)
+                graphs[mode if ring == "base" else mode + "_deep_ring"] = gr
+        equihgnn_amd.set_float32_matmul_precision("highest")
+        os.environ.pop("EQH_BF16_RING", None)
+        for gr in graphs.values():
+            for _ in range(3):
+                gr.replay()
+        torch.cuda.synchronize()
+        times = {k: [] for k in graphs}
+        for _ in range(a.blocks):
+            for k, gr in graphs.items():
+                s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(a.inner):
+                    gr.replay()
+                t.record()
+                torch.cuda.synchronize()
+                times[k].append(s.elapsed_time(t) * 1e3 / (a.inner * REPS))
+        pr = (hip.HgGemmProblem * 1)()
+        pr[0].m, pr[0].n, pr[0].k, pr[0].trans_b = M, N, K, int(tb)
+        entry = {"m": M, "n": N, "k": K, "b_is_n_by_k": tb, "tile": int(hip.lib().hg_gemm_x6_choose_tile(1, pr, 1))}
+        base, base_sp = _stat(times["highest"])
+        for k, ts in times.items():
+            med, sp = _stat(ts)
+            entry[k] = {"us": round(med, 2), "spread": round(sp, 4), "vs_highest": round(med / base, 4),
+                        "tflops_fp32_equivalent": round(2.0 * M * N * K / med / 1e6, 1),
+                        "faster_than_highest_beyond_spread": bool(med * (1 + sp) < base * (1 - base_sp))}
+        res[name] = entry
+        del graphs, x, w, out
+        gc.collect()
+        torch.cuda.empty_cache()
+    return res
+
+
+def step_times(method, batch, flavour, seed0, a, dev):
+    import equihgnn_amd
+    from equihgnn_amd.batch import bucket_sizes, pad_batch, synth_batch
+    from equihgnn_amd.models import MODELS
+    from equihgnn_amd.registry import default_args
+    from equihgnn_amd.trainer import GraphedTrainStep
+    pool = 4
+    ns = default_args(method=method, batch_size=batch)
+    host = [synth_batch(batch, seed0 + i, flavour) for i in range(pool)]
+    torch.manual_seed(0)
+    model = MODELS[method](1, ns).to(dev).train()
+    ext = [bucket_sizes(b.num_nodes, b.num_hyperedges, b.nnz) for b in host]
+    tgt = tuple(max(e[i] for e in ext) for i in range(3))
+    batches = [pad_batch(b, *tgt).packed().to(dev) for b in host]
+    for b in batches:
+        b.num_real_graphs = batch
+    tr = GraphedTrainStep(model, lr=ns.lr, weight_decay=ns.wd)
+    n = [0]
+
+    def step():
+        tr.step(batches[n[0] % pool], batches[(n[0] + 1) % pool])
+        n[0] += 1
+
+    for _ in range(2):
+        step()
+    while getattr(tr, "calibrating", False):          # the trainer settles the form of its index build under "highest"
+        step()
+    for mode in MODES:                                # each mode's capture and warm-up
+        equihgnn_amd.set_float32_matmul_precision(mode)
+        for _ in range(1 + a.warmup):
+            step()
+    times = {m: [] for m in MODES}
+    for _ in range(a.blocks):
+        for mode in MODES:
+            equihgnn_amd.set_float32_matmul_precision(mode)
+            step()                                    # (the first step after a switch is not timed)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                step()
+            torch.cuda.synchronize()
+            times[mode].append((time.perf_counter() - t0) / a.steps * 1e3)
+    equihgnn_amd.set_float32_matmul_precision("highest")
+    out = {"molecules": batch, "flavour": flavour, "hidden": ns.MLP_hidden, "graphs": len(tr.slots)}
+    base, base_sp = _stat(times["highest"])
+    for mode, ts in times.items():
+        med, sp = _stat(ts)
+        out[mode] = {"ms": round(med, 4), "spread": round(sp, 4), "vs_highest": round(med / base, 4),
+                     "faster_than_highest_beyond_spread": bool(med * (1 + sp) < base * (1 - base_sp))}
+    tr.close()
+    del tr, model, batches
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=7)
+    ap.add_argument("--inner", type=int, default=3, help="graph replays (of REPS launches) per timed block of a product")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--skip-steps", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "matmul_precision_bench.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_matmul_precision: no GPU (there is no CPU path to time)")
+    dev = torch.device("cuda:0")
+    result = {"bench": "matmul_precision", "device": torch.cuda.get_device_name(0),
+              "timing": f"products: hipGraphs of {REPS} launches, {a.blocks} interleaved blocks of {a.inner} replays between device events; "
+                        f"steps: {a.blocks} interleaved blocks of {a.steps} replayed steps on a host clock; median block, "
+                        "spread = (max - min) / median",
+              "products": gemm_times(a, dev), "steps": {}}
+    if not a.skip_steps:
+        result["steps"]["c3_equiformer_equihnns_b128"] = step_times("equiformer_equihnns", 128, "qm9", 3000, a, dev)
+        result["steps"]["c5_faformer_equihnns_b512"] = step_times("faformer_equihnns", 512, "pcqm", 5000, a, dev)
+    result["verdict"] = {
+        **{f"{s}/{m}": ("faster" if e[m]["faster_than_highest_beyond_spread"] else "not faster beyond the spread: six products would do")
+           for s, e in result["products"].items() for m in e if isinstance(e[m], dict) and m != "highest"},
+        **{f"{s}/{m}": ("faster" if e[m]["faster_than_highest_beyond_spread"] else "not faster beyond the spread")
+           for s, e in result["steps"].items() for m in ("high", "medium")}}
+    line = json.dumps(result)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()

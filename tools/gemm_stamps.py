@@ -20,7 +20,7 @@ def main():
     ta = int(sys.argv[5]) if len(sys.argv) > 5 else 0
     tb = int(sys.argv[6]) if len(sys.argv) > 6 else 1
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libgemm_stamps.so")
-    build.compile_variant(["gemm_x6.hip", "api.hip"], ["GX_STAMPS", *os.environ.get("GX_DEFS", "").split()], so)
+    build.compile_variant(["gemm_x6.hip", "gemm_bf16_high.hip", "gemm_bf16_medium.hip", "api.hip"], ["GX_STAMPS", *os.environ.get("GX_DEFS", "").split()], so)
     L = hip.load(so, partial=True)
     dev = "cuda:0"
     g = torch.Generator(device=dev).manual_seed(0)
