@@ -1,7 +1,8 @@
 """equihgnn_amd: the MI355X-native training hot path of HySonLab/EquiHGNN."""
 import os
 
-from .precision import get_float32_matmul_precision, set_float32_matmul_precision  # noqa: F401
+from .precision import (get_float32_matmul_precision, get_float32_matmul_precision_panels,  # noqa: F401
+                        set_float32_matmul_precision)
 
 
 def enable_tuned_gemms(tuning: bool = False) -> bool:

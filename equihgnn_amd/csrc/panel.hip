@@ -12,7 +12,8 @@
 //   * the panel's rows are produced by a row PROLOGUE (plain rows, a gathered mean over a CSR row, the per-incidence hidden
 //     layer + mean of conv.py:175-177, a LayerNorm backward of a gathered sum), split (bf16x3.h) and laid into LDS as the A
 //     image; they are 48 KB for all of K = 256, shared by the workgroup's wavefronts;
-//   * products are the six bf16 MFMAs of gemm_x6.hip (fp32-grade results, tests compare with float64);
+//   * products are the six bf16 MFMAs of gemm_x6.hip (fp32-grade results, tests compare with float64) -- or, per launch, its
+//     three or one (NP below: matmul precision "high" / "medium" extended to these kernels);
 //   * the accumulators go through an fp32 LDS staging tile into ROW TILES (below), where the row EPILOGUE runs (scale, addend,
 //     bias, ReLU, LayerNorm and its backward, SiLU), stores whole row segments, and -- in the chained forms -- lays the next
 //     product's A image without leaving the workgroup.
@@ -42,6 +43,17 @@ constexpr int PN_ROWS = 32;        // rows per panel = one MFMA row tile
 constexpr int PN_STG_LD = 260;     // floats per staged row: 256 + 4 keeps the accumulators' 16-byte stores conflict-free
 constexpr int PN_PF = 3;           // K steps (of 16) of weight fragments in flight per wavefront
 
+// The matmul precision of a product: NP = 6, 3 or 1 partial products per fp32 product -- the template parameter of everything
+// below that multiplies, chosen per launch (`products` of the C ABI).  An operand is cut to pn_planes(NP) = 3, 2 or 1 of its
+// bf16 planes and the products a_i b_j with i + j < planes are summed, smallest first (gemm_x6.hip's term sets):
+//   6: a1b1 a0b2 a2b0 a0b1 a1b0 a0b0   (fp32 grade; the code of rounds 4-6, instantiated unchanged)
+//   3: a0b1 a1b0 a0b0                  (|error| <= 3 2^-14 sum |a||b|)
+//   1: a0b0                            (|error| <= (2 2^-7 + 2^-14) sum |a||b|)
+// What shrinks with NP: the MFMAs (192 / 96 / 32 per SIMD at C = 256), the A image in LDS (48 / 32 / 16 KB at K = 256: only the
+// planes that are read are split off and laid down), and the weight stream (384 / 256 / 128 KB: a wavefront fetches the planes it
+// multiplies and no others; hg_panel_pack with `planes` < 3 leaves the others out of the image altogether).
+constexpr int pn_planes(int NP) { return NP == 6 ? 3 : (NP == 3 ? 2 : 1); }
+
 // Geometry of a workgroup of NW wavefronts.  Matrix work: wavefront w multiplies the column tiles w, w + NW, ...  Row work
 // runs on ROW TILES: a wavefront holds RPW = 32 / NW rows of the panel at once, LPR = 64 / RPW lanes per row -- lane
 // (r = lane / LPR, c = lane % LPR) has the float4 at columns 4 (LPR j + c), j < C / (4 LPR) -- so a LayerNorm statistic is a
@@ -66,6 +78,7 @@ __device__ unsigned long long* pn_stamp_buf = nullptr;
 // ---- weights in MFMA operand order ------------------------------------------------------------------------------------------
 // image[tile = n / 32][kstep = k / 16][plane 3][lane 64] x 16 bytes: lane (fh = lane >> 5, fr = lane & 31) holds the eight bf16
 // B[16 kstep + 8 fh + 0..7][32 tile + fr] of one plane.  Several weights may be stacked along K in one image (kstep0).
+// An image of `planes` = 2 or 1 holds the leading planes only ([plane 2] / [plane 1]: two thirds / one third of the bytes).
 struct PackItem {
     const float* w;      // trans: B[k][n] = w[n * ld + k]  (an nn.Linear weight used as x W^T);  else B[k][n] = w[k * ld + n]
     int64_t ld;
@@ -73,6 +86,7 @@ struct PackItem {
     int K, N, trans, kstep0, ksteps_total;
     int n_valid;         // columns n >= n_valid of B are zero (N padded up to a multiple of 32)
     int k_major;         // image[k / 32][tile][k half][plane][lane] (gemm_x6.hip's pre-split B: a K step of ALL tiles contiguous)
+    int planes;          // planes the image holds (3, 2, 1; k_major: 3)
 };
 constexpr int PN_MAXPACK = 32;
 struct PackBatch {
@@ -111,14 +125,14 @@ __global__ void __launch_bounds__(256) k_panel_pack(const PackBatch b) {
     split_pair(v[6], v[7], p0.w, p1.w, p2.w);
     const int kg = it.kstep0 + kstep;
     uint4* d = it.k_major ? it.dst + ((int64_t)(((kg >> 1) * (it.N >> 5) + tile) * 2 + (kg & 1)) * 3) * 64 + lane
-                          : it.dst + ((int64_t)(tile * it.ksteps_total + kg) * 3) * 64 + lane;
+                          : it.dst + ((int64_t)(tile * it.ksteps_total + kg) * it.planes) * 64 + lane;
     d[0] = p0;
-    d[64] = p1;
-    d[128] = p2;
+    if (it.planes > 1) d[64] = p1;
+    if (it.planes > 2) d[128] = p2;
 }
 
 // ---- the A image: a panel's rows as bf16 planes in LDS ---------------------------------------------------------------------
-// [plane 3][kstep KS][slot 64] x 16 bytes; the fragment of (plane, kstep) is 1 KB, lane (fh, fr) reads slot
+// [plane pn_planes(NP)][kstep KS][slot 64] x 16 bytes; the fragment of (plane, kstep) is 1 KB, lane (fh, fr) reads slot
 // fh * 32 + (fr ^ swz), swz = ((kstep & 3) << 1) | fh: the xor keeps the 8-byte row-wise writes below (sixteen lanes of a row
 // tile cover four K steps x two halves of ONE row) on 32 distinct banks, and a ds_read_b128 of a fragment stays a permutation of
 // its 64 slots inside each hardware lane group.
@@ -127,8 +141,8 @@ __device__ __forceinline__ int a_slot(int kstep, int fh, int row) {
     return kstep * 64 + fh * 32 + (row ^ (((kstep & 3) << 1) | fh));
 }
 
-// a lane with v = row[4 k4 .. 4 k4 + 3]: its 8 bytes of each plane
-template <int KS>
+// a lane with v = row[4 k4 .. 4 k4 + 3]: its 8 bytes of each plane that NP products read
+template <int KS, int NP>
 __device__ __forceinline__ void a_put(uint4* __restrict__ img, int row, int k4, const float4& v) {
     const int kstep = k4 >> 2, fh = (k4 >> 1) & 1, half = k4 & 1;
     uint32_t a0, a1, a2, b0, b1, b2;
@@ -136,29 +150,38 @@ __device__ __forceinline__ void a_put(uint4* __restrict__ img, int row, int k4, 
     split_pair(v.z, v.w, b0, b1, b2);
     uint2* d = reinterpret_cast<uint2*>(img) + a_slot<KS>(kstep, fh, row) * 2 + half;
     d[0] = make_uint2(a0, b0);
-    d[KS * 64 * 2] = make_uint2(a1, b1);
-    d[KS * 64 * 4] = make_uint2(a2, b2);
+    if constexpr (pn_planes(NP) > 1) d[KS * 64 * 2] = make_uint2(a1, b1);
+    if constexpr (pn_planes(NP) > 2) d[KS * 64 * 4] = make_uint2(a2, b2);
 }
 
 // ---- the product: acc[g][j] (+)= A image . W image g for the column tiles wave + NW j --------------------------------------
 // NG products share the A image (conv.py:172,176: X feeds W1's first Linear and the node half of W2's); the weight stream
 // runs on across them, PN_PF K steps ahead of the MFMAs.
-template <int KS, int NTW, int NG, int NW>
+// NP = 6: the image holds three planes (a compile-time stride).  NP < 6: PL = pn_planes(NP) planes are fetched from an image
+// of `ip` >= PL planes (the launch's `planes`: a three-plane image serves every mode, a smaller one is a shorter stream).
+template <int KS, int NTW, int NG, int NW, int NP>
 struct WStream {
-    uint4 q[PN_PF][NTW][3];
+    static constexpr int PL = pn_planes(NP);
+    uint4 q[PN_PF][NTW][PL];
     const uint4* base[NG][NTW];
+    int ip;
+    __device__ __forceinline__ explicit WStream(int image_planes) : ip(image_planes) {}
+    __device__ __forceinline__ int stride() const {
+        if constexpr (NP == 6) return 3;
+        else return ip;
+    }
     __device__ __forceinline__ void init(int g, const uint4* __restrict__ w, int wave, int lane, int n_tiles = 1 << 30) {
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {       // (a tile past the image re-reads tile 0; its product is not staged)
             const int tile = wave + NW * j < n_tiles ? wave + NW * j : 0;
-            base[g][j] = w + (int64_t)(tile * KS) * 3 * 64 + lane;
+            base[g][j] = w + (int64_t)(tile * KS) * stride() * 64 + lane;
         }
     }
     __device__ __forceinline__ void fetch(int slot, int kk) {      // kk = product * KS + kstep (compile-time after unrolling)
 #pragma unroll
         for (int j = 0; j < NTW; ++j)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) q[slot][j][p] = base[kk / KS][j][((kk % KS) * 3 + p) * 64];
+            for (int p = 0; p < PL; ++p) q[slot][j][p] = base[kk / KS][j][((kk % KS) * stride() + p) * 64];
     }
     __device__ __forceinline__ void prime() {
 #pragma unroll
@@ -167,37 +190,45 @@ struct WStream {
     }
 };
 
-template <int KS, int NTW, int NG, int NW>
-__device__ __forceinline__ void panel_mma(const uint4* __restrict__ img, WStream<KS, NTW, NG, NW>& ws, f32x16 (&acc)[NG][NTW], int lane) {
+// the NP partial products of one K step of one column tile: A fragments a[plane], weight fragments b[plane]
+template <int NP>
+__device__ __forceinline__ void pn_terms(const uint4 (&a)[pn_planes(NP)], const uint4 (&b)[pn_planes(NP)], f32x16& acc) {
+    const bf16x8 a0 = __builtin_bit_cast(bf16x8, a[0]), b0 = __builtin_bit_cast(bf16x8, b[0]);
+    if constexpr (NP == 6) {
+        const bf16x8 a1 = __builtin_bit_cast(bf16x8, a[1]), a2 = __builtin_bit_cast(bf16x8, a[2]);
+        const bf16x8 b1 = __builtin_bit_cast(bf16x8, b[1]), b2 = __builtin_bit_cast(bf16x8, b[2]);
+        // smallest terms first, as gemm_x6.hip: a1 b1, a0 b2, a2 b0, a0 b1, a1 b0, a0 b0
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, a0, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a2, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc, 0, 0, 0);
+    } else if constexpr (NP == 3) {
+        const bf16x8 a1 = __builtin_bit_cast(bf16x8, a[1]), b1 = __builtin_bit_cast(bf16x8, b[1]);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc, 0, 0, 0);
+    }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc, 0, 0, 0);
+}
+
+template <int KS, int NTW, int NG, int NW, int NP>
+__device__ __forceinline__ void panel_mma(const uint4* __restrict__ img, WStream<KS, NTW, NG, NW, NP>& ws, f32x16 (&acc)[NG][NTW], int lane) {
+    constexpr int PL = pn_planes(NP);
     const int fh = lane >> 5, fr = lane & 31;
-    uint4 af[2][3];            // the A fragments of a K step are requested during the step before
+    uint4 af[2][PL];           // the A fragments of a K step are requested during the step before
     auto a_read = [&](int kk) {
         const uint4* ap = img + a_slot<KS>(kk % KS, fh, fr);
         af[kk & 1][0] = ap[0];
-        af[kk & 1][1] = ap[KS * 64];
-        af[kk & 1][2] = ap[KS * 128];
+        if constexpr (PL > 1) af[kk & 1][1] = ap[KS * 64];
+        if constexpr (PL > 2) af[kk & 1][2] = ap[KS * 128];
     };
     a_read(0);
 #pragma unroll
     for (int kk = 0; kk < KS * NG; ++kk) {
         const int slot = kk % PN_PF, g = kk / KS;
         if (kk + 1 < KS * NG) a_read(kk + 1);
-        const bf16x8 a0 = __builtin_bit_cast(bf16x8, af[kk & 1][0]);
-        const bf16x8 a1 = __builtin_bit_cast(bf16x8, af[kk & 1][1]);
-        const bf16x8 a2 = __builtin_bit_cast(bf16x8, af[kk & 1][2]);
 #pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-            const bf16x8 b0 = __builtin_bit_cast(bf16x8, ws.q[slot][j][0]);
-            const bf16x8 b1 = __builtin_bit_cast(bf16x8, ws.q[slot][j][1]);
-            const bf16x8 b2 = __builtin_bit_cast(bf16x8, ws.q[slot][j][2]);
-            // smallest terms first, as gemm_x6.hip: a1 b1, a0 b2, a2 b0, a0 b1, a1 b0, a0 b0
-            acc[g][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc[g][j], 0, 0, 0);
-            acc[g][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, a0, acc[g][j], 0, 0, 0);
-            acc[g][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a2, acc[g][j], 0, 0, 0);
-            acc[g][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc[g][j], 0, 0, 0);
-            acc[g][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc[g][j], 0, 0, 0);
-            acc[g][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc[g][j], 0, 0, 0);
-        }
+        for (int j = 0; j < NTW; ++j) pn_terms<NP>(af[kk & 1], ws.q[slot][j], acc[g][j]);
         if (kk + PN_PF < KS * NG) ws.fetch(slot, kk + PN_PF);
         // (the scheduler otherwise sinks the fetches next to their uses -- registers it thinks it saves -- and the stream
         // runs one load deep)
@@ -208,36 +239,24 @@ __device__ __forceinline__ void panel_mma(const uint4* __restrict__ img, WStream
 // accumulators (C^T layout: lane (fh, fr) holds row fr, columns 8 g + 4 fh .. + 3 of its tiles) -> the fp32 staging tile
 // Product G of a SUM of products over different A images (k_panel_sum): K steps [G KS, (G + 1) KS) of the weight stream, which
 // runs on across the products as in panel_mma, against the image of product G; every product adds into the same accumulators.
-template <int KS, int NTW, int NG, int NW, int G>
-__device__ __forceinline__ void panel_mma_part(const uint4* __restrict__ img, WStream<KS, NTW, NG, NW>& ws, f32x16 (&acc)[1][NTW], int lane) {
+template <int KS, int NTW, int NG, int NW, int NP, int G>
+__device__ __forceinline__ void panel_mma_part(const uint4* __restrict__ img, WStream<KS, NTW, NG, NW, NP>& ws, f32x16 (&acc)[1][NTW], int lane) {
+    constexpr int PL = pn_planes(NP);
     const int fh = lane >> 5, fr = lane & 31;
-    uint4 af[2][3];
+    uint4 af[2][PL];
     auto a_read = [&](int ks) {
         const uint4* ap = img + a_slot<KS>(ks, fh, fr);
         af[ks & 1][0] = ap[0];
-        af[ks & 1][1] = ap[KS * 64];
-        af[ks & 1][2] = ap[KS * 128];
+        if constexpr (PL > 1) af[ks & 1][1] = ap[KS * 64];
+        if constexpr (PL > 2) af[ks & 1][2] = ap[KS * 128];
     };
     a_read(0);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         const int kk = G * KS + ks, slot = kk % PN_PF;
         if (ks + 1 < KS) a_read(ks + 1);
-        const bf16x8 a0 = __builtin_bit_cast(bf16x8, af[ks & 1][0]);
-        const bf16x8 a1 = __builtin_bit_cast(bf16x8, af[ks & 1][1]);
-        const bf16x8 a2 = __builtin_bit_cast(bf16x8, af[ks & 1][2]);
 #pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-            const bf16x8 b0 = __builtin_bit_cast(bf16x8, ws.q[slot][j][0]);
-            const bf16x8 b1 = __builtin_bit_cast(bf16x8, ws.q[slot][j][1]);
-            const bf16x8 b2 = __builtin_bit_cast(bf16x8, ws.q[slot][j][2]);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc[0][j], 0, 0, 0);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, a0, acc[0][j], 0, 0, 0);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a2, acc[0][j], 0, 0, 0);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc[0][j], 0, 0, 0);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc[0][j], 0, 0, 0);
-            acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc[0][j], 0, 0, 0);
-        }
+        for (int j = 0; j < NTW; ++j) pn_terms<NP>(af[ks & 1], ws.q[slot][j], acc[0][j]);
         if (kk + PN_PF < KS * NG) ws.fetch(slot, kk + PN_PF);
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -319,10 +338,10 @@ __device__ __forceinline__ void rt_load_vec(RowTile<C, NW>& t, const float* __re
     for (int j = 0; j < PnShape<C, NW>::NJ; ++j) t.v[j] = *reinterpret_cast<const float4*>(vec + 4 * Geo<NW>::LPR * j + c4);
 }
 // the tile's rows -> the A image (K offset kb4 = k / 4 of the tile's first column)
-template <int C, int NW, int KS>
+template <int C, int NW, int KS, int NP>
 __device__ __forceinline__ void rt_a_put(const RowTile<C, NW>& t, uint4* __restrict__ img, int lrow, int c, int kb4 = 0) {
 #pragma unroll
-    for (int j = 0; j < PnShape<C, NW>::NJ; ++j) a_put<KS>(img, lrow, kb4 + Geo<NW>::LPR * j + c, t.v[j]);
+    for (int j = 0; j < PnShape<C, NW>::NJ; ++j) a_put<KS, NP>(img, lrow, kb4 + Geo<NW>::LPR * j + c, t.v[j]);
 }
 template <int C, int NW>
 __device__ __forceinline__ void rt_zero(RowTile<C, NW>& t) {
@@ -630,14 +649,15 @@ struct PanelPlain {
     int relu;
     float* Cout;
     int64_t ldc;
+    int wplanes;         // planes of the weight image (>= pn_planes(NP); read by the NP < 6 kernels)
 };
 
 #define PN_KERNEL(NW_) __global__ void __launch_bounds__(64 * NW_) __attribute__((amdgpu_waves_per_eu(NW_ / 4, NW_ / 4)))
 
-template <int C, int NW>
+template <int C, int NW, int NP>
 PN_KERNEL(NW) k_panel_plain(const PanelPlain p) {
     using S = PnShape<C, NW>;
-    __shared__ uint4 s_img[3 * S::KS * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
@@ -645,20 +665,20 @@ PN_KERNEL(NW) k_panel_plain(const PanelPlain p) {
     PN_STAMP(0);
     RowTile<C, NW> x, d;
     rt_load<C, NW>(x, p.A, p.lda, P.rowc, P.c4);
-    WStream<S::KS, S::NTW, 1, NW> ws;
+    WStream<S::KS, S::NTW, 1, NW, NP> ws(p.wplanes);
     ws.init(0, p.W, mul ? wave : 0, lane);
     ws.prime();          // unconditional: loads inside a branch make every later wait conservative (idle waves re-read tile 0)
     if (p.D) rt_load<C, NW>(d, p.D, p.ldd, P.rowc, P.c4);
     else rt_zero<C, NW>(d);
     __builtin_amdgcn_sched_barrier(0);
-    rt_a_put<C, NW, S::KS>(x, s_img, P.lrow, P.c);
+    rt_a_put<C, NW, S::KS, NP>(x, s_img, P.lrow, P.c);
     PN_STAMP(1);
     __syncthreads();
     PN_STAMP(2);
     f32x16 acc[1][S::NTW];
     acc_zero<1, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, 1, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, 1, NW, NP>(s_img, ws, acc, lane);
         PN_STAMP(3);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     }
@@ -711,11 +731,11 @@ __device__ int pn_debug_flags = 0;     // diagnostic build only: 1 = no result s
 #else
 #define PS_STAMP(slot) do { } while (0)
 #endif
-template <int K, int N>
+template <int K, int N, int NP>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) k_panel_stream(const PanelPlain p, int n_panels) {
     constexpr int NW = 8, KS = K / 16, NT = N / 32, LDS_LD = N + 4;
     static_assert(NT >= 1 && NT <= NW && K % 64 == 0 && N % 64 == 0, "one column tile per multiplying wavefront; whole row-tile quads");
-    __shared__ uint4 s_img[2][3 * KS * 64];
+    __shared__ uint4 s_img[2][pn_planes(NP) * KS * 64];
     __shared__ float s_stg[PN_ROWS * LDS_LD];
     const int lane = threadIdx.x & 63, wave_all = threadIdx.x >> 6;
     const bool row_role = wave_all >= NW;                 // wavefront-uniform
@@ -770,7 +790,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)
         RowTile<K, NW> xa, xb;                            // rows of the panels at distance 1 and 2
         rt_load<K, NW>(xa, p.A, p.lda, rowc(first), L.c4);
         rt_load<K, NW>(xb, p.A, p.lda, rowc(first + step), L.c4);
-        rt_a_put<K, NW, KS>(xa, s_img[0], L.lrow, L.c);
+        rt_a_put<K, NW, KS, NP>(xa, s_img[0], L.lrow, L.c);
         xa = xb;
         rt_load<K, NW>(xb, p.A, p.lda, rowc(first + 2 * step), L.c4);
         __syncthreads();                                  // (A) image of the first panel is in place
@@ -785,7 +805,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)
             asm volatile("" : "+v"(ln));
             const RtPos<NW> L(0, PN_ROWS, wave, ln);
             // while the multipliers work on panel pnl: the NEXT panel's image, then the PREVIOUS panel's epilogue
-            if (pnl + step < n_panels) rt_a_put<K, NW, KS>(xa, s_img[cur ^ 1], L.lrow, L.c);
+            if (pnl + step < n_panels) rt_a_put<K, NW, KS, NP>(xa, s_img[cur ^ 1], L.lrow, L.c);
             PS_STAMP(1);
             xa = xb;
             rt_load<K, NW>(xb, p.A, p.lda, rowc(pnl + 3 * step), L.c4);
@@ -803,7 +823,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)
     }
     // ---- multiplying wavefronts
     const bool mul = wave < NT;
-    WStream<KS, 1, 1, NW> ws;
+    WStream<KS, 1, 1, NW, NP> ws(p.wplanes);
     ws.init(0, p.W, mul ? wave : 0, lane);
     __syncthreads();                                      // (A)
     int cur = 0;
@@ -821,7 +841,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc[1][1];
         acc_zero<1, 1>(acc);
-        if (mul) panel_mma<KS, 1, 1, NW>(s_img[cur], ws, acc, ln);
+        if (mul) panel_mma<KS, 1, 1, NW, NP>(s_img[cur], ws, acc, ln);
         PS_STAMP(2);
         __syncthreads();                                  // (B)
         PS_STAMP(3);
@@ -838,25 +858,25 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)
 // 256), so the row prologue -- load, split into bf16 planes, LDS image -- is done twice, by half as many wavefronts each.
 template <int C>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) k_panel_plain_pair(const PanelPlain p) {
-    constexpr int NW = 4;
+    constexpr int NW = 4, NP = 6;          // (a measurement aid at six products)
     using S = PnShape<C, NW>;
     constexpr int HT = S::NT / 2;          // column tiles per half (4 at C = 256): one per wavefront
     static_assert(HT == NW, "one column tile per wavefront");
-    __shared__ uint4 s_img[3 * S::KS * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * (C / 2 + 4)];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = blockIdx.y;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
     RowTile<C, NW> x;
     rt_load<C, NW>(x, p.A, p.lda, P.rowc, P.c4);
-    WStream<S::KS, 1, 1, NW> ws;
+    WStream<S::KS, 1, 1, NW, NP> ws(p.wplanes);
     ws.init(0, p.W + (int64_t)(half * HT * S::KS) * 3 * 64, wave, lane);
     ws.prime();
     __builtin_amdgcn_sched_barrier(0);
-    rt_a_put<C, NW, S::KS>(x, s_img, P.lrow, P.c);
+    rt_a_put<C, NW, S::KS, NP>(x, s_img, P.lrow, P.c);
     __syncthreads();
     f32x16 acc[1][1];
     acc_zero<1, 1>(acc);
-    panel_mma<S::KS, 1, 1, NW>(s_img, ws, acc, lane);
+    panel_mma<S::KS, 1, 1, NW, NP>(s_img, ws, acc, lane);
     acc_to_staging<1, NW, C / 2 + 4>(s_stg, acc[0], wave, lane);
     __syncthreads();
     // epilogue on this half's 32 x 128 block: 8 lanes per row, four float4 each
@@ -894,29 +914,30 @@ struct PanelMulti {
     int64_t ldd[3];
     float* out[3];
     int64_t ldo[3];
+    int wplanes;
 };
 
-template <int C, int NW, int NG>
+template <int C, int NW, int NG, int NP>
 PN_KERNEL(NW) k_panel_multi(const PanelMulti p) {
     using S = PnShape<C, NW>;
-    __shared__ uint4 s_img[3 * S::KS * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[NG][PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
     const bool mul = wave < S::NT;
     RowTile<C, NW> x;
     rt_load<C, NW>(x, p.A, p.lda, P.rowc, P.c4);
-    WStream<S::KS, S::NTW, NG, NW> ws;
+    WStream<S::KS, S::NTW, NG, NW, NP> ws(p.wplanes);
 #pragma unroll
     for (int g = 0; g < NG; ++g) ws.init(g, p.W[g], mul ? wave : 0, lane);
     ws.prime();
     __builtin_amdgcn_sched_barrier(0);
-    rt_a_put<C, NW, S::KS>(x, s_img, P.lrow, P.c);
+    rt_a_put<C, NW, S::KS, NP>(x, s_img, P.lrow, P.c);
     __syncthreads();
     f32x16 acc[NG][S::NTW];
     acc_zero<NG, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, NG, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, NG, NW, NP>(s_img, ws, acc, lane);
 #pragma unroll
         for (int g = 0; g < NG; ++g) acc_to_staging<S::NTW, NW>(s_stg[g], acc[g], wave, lane);
     }
@@ -971,17 +992,18 @@ struct ConvPanelArgs {
     float* slab; float* slab2;
     float* acc_out;
     int* signal;                    // F2: a device counter the first thread of the launch bumps (eqh_signal_post folded in), or null
+    int wplanes;                    // planes of every weight image of the launch
 };
 
 // ---- F1: X -> h1 (raw), h1n = LN1(relu(h1 + b1a)), pa -------------------------------------------------------------------------
 // the A image holds X's panel; w_a = W1a image (x W^T), w_b = W2v image
-template <int C, int NW>
+template <int C, int NW, int NP>
 __device__ __forceinline__ void stage_f1(const ConvPanelArgs& p, uint4* __restrict__ s_img, float* __restrict__ s_stg,
                                          float* __restrict__ s_stg2, const uint4* w_a, const uint4* w_b, const float* b1a,
                                          const float* g1, const float* be1, float* h1, float* h1n, float* pa, const RtPos<NW>& P, int wave,
                                          int lane, bool mul) {
     using S = PnShape<C, NW>;
-    WStream<S::KS, S::NTW, 2, NW> ws;
+    WStream<S::KS, S::NTW, 2, NW, NP> ws(p.wplanes);
     ws.init(0, w_a, mul ? wave : 0, lane);
     ws.init(1, w_b, mul ? wave : 0, lane);
     ws.prime();
@@ -989,7 +1011,7 @@ __device__ __forceinline__ void stage_f1(const ConvPanelArgs& p, uint4* __restri
     f32x16 acc[2][S::NTW];
     acc_zero<2, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, 2, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, 2, NW, NP>(s_img, ws, acc, lane);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
         acc_to_staging<S::NTW, NW>(s_stg2, acc[1], wave, lane);
     }
@@ -1008,10 +1030,10 @@ __device__ __forceinline__ void stage_f1(const ConvPanelArgs& p, uint4* __restri
     if (P.live) rt_store<C, NW>(y, h1n, C, P.row, P.c4);
 }
 
-template <int C, int NW>
+template <int C, int NW, int NP>
 PN_KERNEL(NW) k_conv_f1(const ConvPanelArgs p) {
     using S = PnShape<C, NW>;
-    __shared__ uint4 s_img[3 * S::KS * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
     __shared__ float s_stg2[PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1019,17 +1041,17 @@ PN_KERNEL(NW) k_conv_f1(const ConvPanelArgs p) {
     const bool mul = wave < S::NT;
     RowTile<C, NW> x;
     rt_load<C, NW>(x, p.in0, p.ld0, P.rowc, P.c4);
-    rt_a_put<C, NW, S::KS>(x, s_img, P.lrow, P.c);
+    rt_a_put<C, NW, S::KS, NP>(x, s_img, P.lrow, P.c);
     __syncthreads();
-    stage_f1<C, NW>(p, s_img, s_stg, s_stg2, p.w0, p.w1, p.b0, p.g0, p.be0, p.out0, p.out1, p.out2, P, wave, lane, mul);
+    stage_f1<C, NW, NP>(p, s_img, s_stg, s_stg2, p.w0, p.w1, p.b0, p.g0, p.be0, p.out0, p.out1, p.out2, P, wave, lane, mul);
 }
 
 // ---- F2: hbar[e] = mean over the hyperedge's nodes of h1n, qb = hbar w12^T + b12 ---------------------------------------------
 // in0 = h1n [N, C], rowptr / col = the incidence CSR by hyperedge, w0 = w12 image, bias_out = b12; out0 = hbar, out1 = qb
-template <int C, int NW>
+template <int C, int NW, int NP>
 PN_KERNEL(NW) k_conv_f2(const ConvPanelArgs p) {
     using S = PnShape<C, NW>;
-    __shared__ uint4 s_img[3 * S::KS * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
@@ -1038,7 +1060,7 @@ PN_KERNEL(NW) k_conv_f2(const ConvPanelArgs p) {
     // (round 6) the post that releases the next batch's index build on the trainer's side stream, folded into this launch: one
     // launch slot (~4.7 us in a replayed graph) less than a one-thread kernel of its own
     if (p.signal && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_fetch_add(p.signal, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    WStream<S::KS, S::NTW, 1, NW> ws;
+    WStream<S::KS, S::NTW, 1, NW, NP> ws(p.wplanes);
     ws.init(0, p.w0, mul ? wave : 0, lane);
     ws.prime();
     __builtin_amdgcn_sched_barrier(0);
@@ -1049,14 +1071,14 @@ PN_KERNEL(NW) k_conv_f2(const ConvPanelArgs p) {
 #pragma unroll
     for (int j = 0; j < S::NJ; ++j) { m.v[j].x /= den; m.v[j].y /= den; m.v[j].z /= den; m.v[j].w /= den; }
     if (P.live) rt_store<C, NW>(m, p.out0, C, P.row, P.c4);
-    rt_a_put<C, NW, S::KS>(m, s_img, P.lrow, P.c);        // (rows past the end of the matrix: zeros for the MFMA)
+    rt_a_put<C, NW, S::KS, NP>(m, s_img, P.lrow, P.c);        // (rows past the end of the matrix: zeros for the MFMA)
     PN_STAMP(1);
     __syncthreads();
     PN_STAMP(2);
     f32x16 acc[1][S::NTW];
     acc_zero<1, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, 1, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, 1, NW, NP>(s_img, ws, acc, lane);
         PN_STAMP(3);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     }
@@ -1076,17 +1098,17 @@ PN_KERNEL(NW) k_conv_f2(const ConvPanelArgs p) {
 // incidence LayerNorm, out6 = s (written); in1 = cw, w0 = w23 image, b0/g0/be0 = b3a, gamma3, beta3, w1 = W3b image,
 // bias_out = b3b, relu; out0 = u, out1 = x3, out2 = Xn;
 // tail: w2 = W1a image, w3 = W2v image, b1/g1/be1 = b1a, gamma1, beta1, out3 = h1, out4 = h1n, out5 = pa
-template <int C, int NW>
+template <int C, int NW, int NP>
 PN_KERNEL(NW) k_conv_f3(const ConvPanelArgs p) {
     using S = PnShape<C, NW>;
-    __shared__ uint4 s_img[3 * S::KS * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
     __shared__ float s_stg2[PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
     const bool mul = wave < S::NT;
     PN_STAMP(0);
-    WStream<S::KS, S::NTW, 1, NW> ws;
+    WStream<S::KS, S::NTW, 1, NW, NP> ws(p.wplanes);
     ws.init(0, p.w0, mul ? wave : 0, lane);
     ws.prime();
     RowTile<C, NW> t, cw;
@@ -1098,14 +1120,14 @@ PN_KERNEL(NW) k_conv_f3(const ConvPanelArgs p) {
     } else {
         rt_load<C, NW>(t, p.in0, C, P.rowc, P.c4);
     }
-    rt_a_put<C, NW, S::KS>(t, s_img, P.lrow, P.c);
+    rt_a_put<C, NW, S::KS, NP>(t, s_img, P.lrow, P.c);
     PN_STAMP(1);
     __syncthreads();
     PN_STAMP(2);
     f32x16 acc[1][S::NTW];
     acc_zero<1, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, 1, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, 1, NW, NP>(s_img, ws, acc, lane);
         PN_STAMP(3);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     }
@@ -1130,14 +1152,14 @@ PN_KERNEL(NW) k_conv_f3(const ConvPanelArgs p) {
             rt_store<C, NW>(t, p.out0, C, P.row, P.c4);
             rt_store<C, NW>(x3, p.out1, C, P.row, P.c4);
         }
-        rt_a_put<C, NW, S::KS>(x3, s_img, P.lrow, P.c);       // (every wavefront has left the MFMA loop: barrier above)
+        rt_a_put<C, NW, S::KS, NP>(x3, s_img, P.lrow, P.c);       // (every wavefront has left the MFMA loop: barrier above)
     }
     PN_STAMP(5);
     __syncthreads();
     PN_STAMP(6);
     acc_zero<1, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, 1, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, 1, NW, NP>(s_img, ws, acc, lane);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     }
     PN_STAMP(7);
@@ -1152,26 +1174,26 @@ PN_KERNEL(NW) k_conv_f3(const ConvPanelArgs p) {
             if (p.relu) { t.v[j].x = fmaxf(t.v[j].x, 0.f); t.v[j].y = fmaxf(t.v[j].y, 0.f); t.v[j].z = fmaxf(t.v[j].z, 0.f); t.v[j].w = fmaxf(t.v[j].w, 0.f); }
         }
         if (P.live) rt_store<C, NW>(t, p.out2, C, P.row, P.c4);
-        if (p.tail) rt_a_put<C, NW, S::KS>(t, s_img, P.lrow, P.c);
+        if (p.tail) rt_a_put<C, NW, S::KS, NP>(t, s_img, P.lrow, P.c);
     }
     PN_STAMP(8);
     if (!p.tail) return;
     __syncthreads();
-    stage_f1<C, NW>(p, s_img, s_stg, s_stg2, p.w2, p.w3, p.b1, p.g1, p.be1, p.out3, p.out4, p.out5, P, wave, lane, mul);
+    stage_f1<C, NW, NP>(p, s_img, s_stg, s_stg2, p.w2, p.w3, p.b1, p.g1, p.be1, p.out3, p.out4, p.out5, P, wave, lane, mul);
     PN_STAMP(9);
 }
 
 // ---- B3: dXn -> g = dXn * [Xn > 0], dx3 = g W3b, dpre = LN3bwd(u + b3a; dx3), ds = scale * dpre w23 --------------------------
 // Shared by k_conv_b3 (rows from memory) and the tail of k_conv_b1 (rows = the dX it has just formed, in registers).
 // w_a = W3b image (dy W), w_b = w23 image (dy W); slab = [d b3a | d gamma3 | d beta3] of this workgroup; acc_out += dpre
-template <int C, int NW>
+template <int C, int NW, int NP>
 __device__ __forceinline__ void stage_b3(const ConvPanelArgs& p, uint4* __restrict__ s_img, float* __restrict__ s_stg, RowTile<C, NW>& t,
                                          const float* xmask, const uint4* w_a, const uint4* w_b, const float* u_pre, const float* b3a,
                                          const float* g3, float* g_out, float* dpre_out, float* ds_out, float* slab, float* acc_out,
                                          int acc_first, const RtPos<NW>& P, int wave, int lane, bool mul) {
     using S = PnShape<C, NW>;
     RowTile<C, NW> upre;
-    WStream<S::KS, S::NTW, 1, NW> ws;
+    WStream<S::KS, S::NTW, 1, NW, NP> ws(p.wplanes);
     ws.init(0, w_a, mul ? wave : 0, lane);
     ws.prime();
     rt_load<C, NW>(upre, u_pre, C, P.rowc, P.c4);
@@ -1187,13 +1209,13 @@ __device__ __forceinline__ void stage_b3(const ConvPanelArgs& p, uint4* __restri
     __builtin_amdgcn_sched_barrier(0);
     if (g_out && P.live) rt_store<C, NW>(t, g_out, C, P.row, P.c4);
     // (the A image was last read before the barriers of the caller's slab reduction)
-    rt_a_put<C, NW, S::KS>(t, s_img, P.lrow, P.c);
+    rt_a_put<C, NW, S::KS, NP>(t, s_img, P.lrow, P.c);
     PN_STAMP(8);
     __syncthreads();
     f32x16 acc[1][S::NTW];
     acc_zero<1, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, 1, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, 1, NW, NP>(s_img, ws, acc, lane);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     }
     PN_STAMP(9);
@@ -1224,13 +1246,13 @@ __device__ __forceinline__ void stage_b3(const ConvPanelArgs& p, uint4* __restri
                 }
             }
         }
-        rt_a_put<C, NW, S::KS>(dpre, s_img, P.lrow, P.c);
+        rt_a_put<C, NW, S::KS, NP>(dpre, s_img, P.lrow, P.c);
     }
     PN_STAMP(11);
     __syncthreads();
     acc_zero<1, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, 1, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, 1, NW, NP>(s_img, ws, acc, lane);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     }
     PN_STAMP(12);
@@ -1245,17 +1267,17 @@ __device__ __forceinline__ void stage_b3(const ConvPanelArgs& p, uint4* __restri
 
 // in0 = dXn (ld0), in1 = Xn or null, w0 = W3b image, w1 = w23 image, in2 = u, b0/g0 = b3a, gamma3;
 // out0 = g (when in1), out1 = dpre, out2 = ds, slab, acc_out (+= dpre; overwritten when acc_first)
-template <int C, int NW>
+template <int C, int NW, int NP>
 PN_KERNEL(NW) k_conv_b3(const ConvPanelArgs p) {
     using S = PnShape<C, NW>;
-    __shared__ uint4 s_img[3 * S::KS * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
     const bool mul = wave < S::NT;
     RowTile<C, NW> t;
     rt_load<C, NW>(t, p.in0, p.ld0, P.rowc, P.c4);
-    stage_b3<C, NW>(p, s_img, s_stg, t, p.in1, p.w0, p.w1, p.in2, p.b0, p.g0, p.out0, p.out1, p.out2, p.slab, p.acc_out, p.acc_first, P,
+    stage_b3<C, NW, NP>(p, s_img, s_stg, t, p.in1, p.w0, p.w1, p.in2, p.b0, p.g0, p.out0, p.out1, p.out2, p.slab, p.acc_out, p.acc_first, P,
                     wave, lane, mul);
 }
 
@@ -1265,11 +1287,11 @@ PN_KERNEL(NW) k_conv_b3(const ConvPanelArgs p) {
 // slab = [d b1a | d gamma1 | d beta1];
 // tail: in3 = X of this application = Xn of the one before (mask), w1 = W3b image, w2 = w23 image, out5 = its u (read),
 //       b1/g1 = b3a, gamma3; out2 = g, out3 = dpre, out4 = ds, slab2, acc_out
-template <int C, int NW>
+template <int C, int NW, int NP>
 PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
     using S = PnShape<C, NW>;
     constexpr int KS2 = 2 * S::KS;
-    __shared__ uint4 s_img[3 * KS2 * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * KS2 * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
@@ -1277,7 +1299,7 @@ PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
     // w3 != null: B2 folded in -- in0 is dqb and the gathered sums are multiplied by w12 here (the gathered mean is linear:
     // sum_e w_e (dqb[e] w12) = (sum_e w_e dqb[e]) w12), so dhbar never exists and its launch is gone
     PN_STAMP(0);
-    WStream<S::KS, S::NTW, 1, NW> ws12;
+    WStream<S::KS, S::NTW, 1, NW, NP> ws12(p.wplanes);
     if (p.w3) {
         ws12.init(0, p.w3, mul ? wave : 0, lane);
         ws12.prime();
@@ -1291,19 +1313,19 @@ PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
     else rt_gather_sum<C, NW, false>(p.in0, p.rowptr, p.col, nullptr, P, dsum, deg);
     PN_STAMP(1);
     if (p.w3) {
-        rt_a_put<C, NW, S::KS>(dsum, s_img, P.lrow, P.c);
+        rt_a_put<C, NW, S::KS, NP>(dsum, s_img, P.lrow, P.c);
         __syncthreads();
         f32x16 acc12[1][S::NTW];
         acc_zero<1, S::NTW>(acc12);
         if (mul) {
-            panel_mma<S::KS, S::NTW, 1, NW>(s_img, ws12, acc12, lane);
+            panel_mma<S::KS, S::NTW, 1, NW, NP>(s_img, ws12, acc12, lane);
             acc_to_staging<S::NTW, NW>(s_stg, acc12[0], wave, lane);
         }
         __syncthreads();
         rt_load<C, NW>(dsum, s_stg, PN_STG_LD, P.lrow, P.c4);
     }
     PN_STAMP(2);
-    WStream<KS2, S::NTW, 1, NW> ws;
+    WStream<KS2, S::NTW, 1, NW, NP> ws(p.wplanes);
     ws.init(0, p.w0, mul ? wave : 0, lane);
     ws.prime();
     __builtin_amdgcn_sched_barrier(0);
@@ -1316,15 +1338,15 @@ PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
         rt_ln_bwd<C, NW>(h, bv, gv, dsum, p.eps, P.live, dh, a_db, a_dg, a_dbeta);
         if (P.live) rt_store<C, NW>(dh, p.out0, C, P.row, P.c4);
         // (every wavefront is past the barrier behind the w12 product: its image may be overwritten, in the K = 2 C layout)
-        rt_a_put<C, NW, KS2>(dh, s_img, P.lrow, P.c, 0);
-        rt_a_put<C, NW, KS2>(dpa, s_img, P.lrow, P.c, C / 4);
+        rt_a_put<C, NW, KS2, NP>(dh, s_img, P.lrow, P.c, 0);
+        rt_a_put<C, NW, KS2, NP>(dpa, s_img, P.lrow, P.c, C / 4);
     }
     PN_STAMP(3);
     __syncthreads();
     f32x16 acc[1][S::NTW];
     acc_zero<1, S::NTW>(acc);
     if (mul) {
-        panel_mma<KS2, S::NTW, 1, NW>(s_img, ws, acc, lane);
+        panel_mma<KS2, S::NTW, 1, NW, NP>(s_img, ws, acc, lane);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     }
     PN_STAMP(4);
@@ -1335,7 +1357,7 @@ PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
     write_slab<C, NW>(s_stg, p.slab + (int64_t)blockIdx.x * 3 * C, a_db, a_dg, a_dbeta, wave, lane);
     PN_STAMP(5);
     if (!p.tail) return;
-    stage_b3<C, NW>(p, s_img, s_stg, dx, p.in3, p.w1, p.w2, p.out5, p.b1, p.g1, p.out2, p.out3, p.out4, p.slab2, p.acc_out, p.acc_first, P,
+    stage_b3<C, NW, NP>(p, s_img, s_stg, dx, p.in3, p.w1, p.w2, p.out5, p.b1, p.g1, p.out2, p.out3, p.out4, p.slab2, p.acc_out, p.acc_first, P,
                     wave, lane, mul);
     PN_STAMP(6);
 }
@@ -1360,11 +1382,11 @@ __device__ __forceinline__ float silu_grad_f(float x) {
 // out0 = node_in [N, C + 16], out1 = hpre [N, 2 C], out2 = hid [N, 2 C], out3 = out [N, C].
 // g0 != null (round 6): in0 = feats and normed = LayerNorm(feats; g0, be0, eps) is formed HERE (node_norm, egnn_layer.py:192,360:
 // it was a launch of its own each way), the residual is in0 itself (in2 unused)
-template <int C, int NW>
+template <int C, int NW, int NP>
 PN_KERNEL(NW) k_node_f(const ConvPanelArgs p) {
     using S = PnShape<C, NW>;
     constexpr int KS1 = C / 16 + 1, KS2 = C / 8;
-    __shared__ uint4 s_img[3 * KS2 * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * KS2 * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
@@ -1372,7 +1394,7 @@ PN_KERNEL(NW) k_node_f(const ConvPanelArgs p) {
     RowTile<C, NW> x, res;
     rt_load<C, NW>(x, p.in0, C, P.rowc, P.c4);
     const float4 mi = P.c < 4 ? *reinterpret_cast<const float4*>(p.in1 + (int64_t)P.rowc * 16 + P.c4) : f4_zero();
-    WStream<KS1, S::NTW, 2, NW> ws;
+    WStream<KS1, S::NTW, 2, NW, NP> ws(p.wplanes);
     ws.init(0, p.w0, mul ? wave : 0, lane);
     ws.init(1, p.w1, mul ? wave : 0, lane);
     ws.prime();
@@ -1392,8 +1414,8 @@ PN_KERNEL(NW) k_node_f(const ConvPanelArgs p) {
         rt_load<C, NW>(res, p.in2, C, P.rowc, P.c4);
     }
     __builtin_amdgcn_sched_barrier(0);
-    rt_a_put<C, NW, KS1>(x, s_img, P.lrow, P.c);
-    if (P.c < 4) a_put<KS1>(s_img, P.lrow, C / 4 + P.c, mi);
+    rt_a_put<C, NW, KS1, NP>(x, s_img, P.lrow, P.c);
+    if (P.c < 4) a_put<KS1, NP>(s_img, P.lrow, C / 4 + P.c, mi);
     if (P.live) {
         rt_store<C, NW>(x, p.out0, C + 16, P.row, P.c4);
         if (P.c < 4) *reinterpret_cast<float4*>(p.out0 + (int64_t)P.row * (C + 16) + C + P.c4) = mi;
@@ -1402,10 +1424,10 @@ PN_KERNEL(NW) k_node_f(const ConvPanelArgs p) {
     f32x16 acc[2][S::NTW];
     acc_zero<2, S::NTW>(acc);
     if (mul) {
-        panel_mma<KS1, S::NTW, 2, NW>(s_img, ws, acc, lane);
+        panel_mma<KS1, S::NTW, 2, NW, NP>(s_img, ws, acc, lane);
         acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     }
-    WStream<KS2, S::NTW, 1, NW> ws2;
+    WStream<KS2, S::NTW, 1, NW, NP> ws2(p.wplanes);
     ws2.init(0, p.w2, mul ? wave : 0, lane);
     ws2.prime();
     __builtin_amdgcn_sched_barrier(0);
@@ -1422,7 +1444,7 @@ PN_KERNEL(NW) k_node_f(const ConvPanelArgs p) {
         for (int j = 0; j < S::NJ; ++j)
             t.v[j] = make_float4(silu_div(t.v[j].x), silu_div(t.v[j].y), silu_div(t.v[j].z), silu_div(t.v[j].w));
         if (P.live) rt_store<C, NW>(t, p.out2 + half * C, 2 * C, P.row, P.c4);
-        rt_a_put<C, NW, KS2>(t, s_img, P.lrow, P.c, half * (C / 4));
+        rt_a_put<C, NW, KS2, NP>(t, s_img, P.lrow, P.c, half * (C / 4));
         if (half == 0) {
             __syncthreads();                   // the staging tile's rows have been read: second half of the product
             if (mul) acc_to_staging<S::NTW, NW>(s_stg, acc[1], wave, lane);
@@ -1432,7 +1454,7 @@ PN_KERNEL(NW) k_node_f(const ConvPanelArgs p) {
     f32x16 acc2[1][S::NTW];
     acc_zero<1, S::NTW>(acc2);
     if (mul) {
-        panel_mma<KS2, S::NTW, 1, NW>(s_img, ws2, acc2, lane);
+        panel_mma<KS2, S::NTW, 1, NW, NP>(s_img, ws2, acc2, lane);
         acc_to_staging<S::NTW, NW>(s_stg, acc2[0], wave, lane);
     }
     __syncthreads();
@@ -1448,34 +1470,34 @@ PN_KERNEL(NW) k_node_f(const ConvPanelArgs p) {
 // w2 = W0 N image (K = 2 C, N = C + 16 zero-padded to C + 32); out0 = dpre [N, 2 C], out1 = dnode_in [N, C + 16].
 // g0 != null (round 6, with k_node_f's LayerNorm): in3 = feats; out1 = d feats [N, C] = LNbwd(d normed) + dout (the residual's
 // gradient rides along), out2 = d m_i [N, 16], slab = [unused | d gamma | d beta] partial sums of this workgroup
-template <int C, int NW>
+template <int C, int NW, int NP>
 PN_KERNEL(NW) k_node_b(const ConvPanelArgs p) {
     using S = PnShape<C, NW>;
     constexpr int KS2 = C / 8, NT2 = C / 32 + 1, NTW2 = (NT2 + NW - 1) / NW, LD2 = C + 32 + 4;
-    __shared__ uint4 s_img[3 * KS2 * 64];
+    __shared__ uint4 s_img[pn_planes(NP) * KS2 * 64];
     __shared__ float s_stg[PN_ROWS * LD2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
     const bool mul = wave < S::NT;
     RowTile<C, NW> d, hp[2];
     rt_load<C, NW>(d, p.in0, p.ld0, P.rowc, P.c4);
-    WStream<S::KS, S::NTW, 2, NW> ws;
+    WStream<S::KS, S::NTW, 2, NW, NP> ws(p.wplanes);
     ws.init(0, p.w0, mul ? wave : 0, lane);
     ws.init(1, p.w1, mul ? wave : 0, lane);
     ws.prime();
     rt_load<C, NW>(hp[0], p.in1, 2 * C, P.rowc, P.c4);
     rt_load<C, NW>(hp[1], p.in1 + C, 2 * C, P.rowc, P.c4);
     __builtin_amdgcn_sched_barrier(0);
-    rt_a_put<C, NW, S::KS>(d, s_img, P.lrow, P.c);
+    rt_a_put<C, NW, S::KS, NP>(d, s_img, P.lrow, P.c);
     __syncthreads();
     f32x16 acc[2][S::NTW];
     acc_zero<2, S::NTW>(acc);
     if (mul) {
-        panel_mma<S::KS, S::NTW, 2, NW>(s_img, ws, acc, lane);
+        panel_mma<S::KS, S::NTW, 2, NW, NP>(s_img, ws, acc, lane);
         acc_to_staging<S::NTW, NW, LD2>(s_stg, acc[0], wave, lane);
     }
     const bool mul2 = wave < NT2;
-    WStream<KS2, NTW2, 1, NW> ws2;
+    WStream<KS2, NTW2, 1, NW, NP> ws2(p.wplanes);
     ws2.init(0, p.w2, mul2 ? wave : 0, lane, NT2);
     ws2.prime();
     __builtin_amdgcn_sched_barrier(0);
@@ -1490,7 +1512,7 @@ PN_KERNEL(NW) k_node_b(const ConvPanelArgs p) {
             t.v[j].x *= silu_grad_f(h.x); t.v[j].y *= silu_grad_f(h.y); t.v[j].z *= silu_grad_f(h.z); t.v[j].w *= silu_grad_f(h.w);
         }
         if (P.live) rt_store<C, NW>(t, p.out0 + half * C, 2 * C, P.row, P.c4);
-        rt_a_put<C, NW, KS2>(t, s_img, P.lrow, P.c, half * (C / 4));
+        rt_a_put<C, NW, KS2, NP>(t, s_img, P.lrow, P.c, half * (C / 4));
         if (half == 0) {
             __syncthreads();
             if (mul) acc_to_staging<S::NTW, NW, LD2>(s_stg, acc[1], wave, lane);
@@ -1500,7 +1522,7 @@ PN_KERNEL(NW) k_node_b(const ConvPanelArgs p) {
     f32x16 acc2[1][NTW2];
     acc_zero<1, NTW2>(acc2);
     if (mul2) {
-        panel_mma<KS2, NTW2, 1, NW>(s_img, ws2, acc2, lane);
+        panel_mma<KS2, NTW2, 1, NW, NP>(s_img, ws2, acc2, lane);
         acc_to_staging<NTW2, NW, LD2>(s_stg, acc2[0], wave, lane, NT2);
     }
     __syncthreads();
@@ -1532,14 +1554,34 @@ PN_KERNEL(NW) k_node_b(const ConvPanelArgs p) {
 
 inline bool pn_width_ok(int C) { return C == 64 || C == 128 || C == 256; }
 
-// wavefronts per panel: 8 (default); EQH_PANEL_WAVES=4 selects round 4's geometry for same-box A/B runs
-inline int pn_waves() {
+// wavefronts per panel: 8 (default); EQH_PANEL_WAVES=4 selects round 4's geometry for same-box A/B runs -- of the six-product
+// kernels: the three- and one-product kernels exist with eight wavefronts only
+inline int pn_waves(int np = 6) {
     static const int nw = [] {
         const char* e = std::getenv("EQH_PANEL_WAVES");
         return (e && e[0] == '4') ? 4 : 8;
     }();
-    return nw;
+    return np == 6 ? nw : 8;
 }
+
+// `products` / `planes` of an entry point -> (NP, planes of the weight images): 0 stands for 6 products / a three-plane image;
+// false: not one of 6, 3, 1 / 3, 2, 1, or an image with fewer planes than the products read
+inline bool pn_mode(int32_t products, int32_t planes, int& np, int& ip) {
+    np = products ? products : 6;
+    ip = planes ? planes : 3;
+    if (np != 6 && np != 3 && np != 1) return false;
+    return ip >= pn_planes(np) && ip <= 3;
+}
+
+// X(NW, NP) for the (wavefronts, products) of a launch
+#define PN_BY_MODE(X)                  \
+    do {                               \
+        if (np == 6) {                 \
+            if (nw == 8) X(8, 6);      \
+            else X(4, 6);              \
+        } else if (np == 3) X(8, 3);   \
+        else X(8, 1);                  \
+    } while (0)
 
 }  // namespace
 
@@ -1551,7 +1593,8 @@ extern "C" size_t hg_conv_panel_slab_bytes(int64_t rows, int32_t C) {
 extern "C" int hg_conv_panel(int32_t stage, const HgConvPanel* q, void* stream_) {
     if (!q) return EQH_ERR_ARG;
     const int C = q->C;
-    if (!pn_width_ok(C) || q->rows < 0) return EQH_ERR_ARG;
+    int np, ip;
+    if (!pn_width_ok(C) || q->rows < 0 || !pn_mode(q->products, q->planes, np, ip)) return EQH_ERR_ARG;
     if (q->rows >= ((int64_t)1 << 31) - 64) return EQH_ERR_RANGE;
     if (q->rows == 0) return EQH_OK;
     const void* ptrs[] = {q->in0, q->in1, q->in2, q->in3, q->w0, q->w1, q->w2, q->w3, q->b0, q->g0, q->be0, q->b1, q->g1, q->be1,
@@ -1571,25 +1614,29 @@ extern "C" int hg_conv_panel(int32_t stage, const HgConvPanel* q, void* stream_)
     a.out0 = q->out0; a.out1 = q->out1; a.out2 = q->out2; a.out3 = q->out3; a.out4 = q->out4; a.out5 = q->out5; a.out6 = q->out6;
     a.slab = q->slab; a.slab2 = q->slab2; a.acc_out = q->acc_out;
     a.signal = stage == HG_CONV_F2 ? q->signal : nullptr;
+    a.wplanes = ip;
     if (a.ld0 & 3) return EQH_ERR_ALIGN;
     const int blocks = (int)((q->rows + PN_ROWS - 1) / PN_ROWS);
-    const int nw = pn_waves();
+    const int nw = pn_waves(np);
     const dim3 grid(blocks), block(64 * nw);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     auto need = [](std::initializer_list<const void*> l) { for (const void* x : l) if (!x) return false; return true; };
     auto f1_ok = [&](const void* wa, const void* wb, const void* b, const void* g, const void* be, const void* o0, const void* o1, const void* o2) {
         return need({wa, wb, b, g, be, o0, o1, o2});
     };
-#define PN_LAUNCH_W(K, NW_)                                                                               \
+#define PN_LAUNCH_W(K, NW_, NP_)                                                                          \
     do {                                                                                                  \
-        if (C == 256) hipLaunchKernelGGL((K<256, NW_>), grid, block, 0, stream, a);                       \
-        else if (C == 128) hipLaunchKernelGGL((K<128, NW_>), grid, block, 0, stream, a);                  \
-        else hipLaunchKernelGGL((K<64, NW_>), grid, block, 0, stream, a);                                 \
+        if (C == 256) hipLaunchKernelGGL((K<256, NW_, NP_>), grid, block, 0, stream, a);                  \
+        else if (C == 128) hipLaunchKernelGGL((K<128, NW_, NP_>), grid, block, 0, stream, a);             \
+        else hipLaunchKernelGGL((K<64, NW_, NP_>), grid, block, 0, stream, a);                            \
     } while (0)
 #define PN_LAUNCH(K)                                                                                      \
     do {                                                                                                  \
-        if (nw == 8) PN_LAUNCH_W(K, 8);                                                                   \
-        else PN_LAUNCH_W(K, 4);                                                                           \
+        if (np == 6) {                                                                                    \
+            if (nw == 8) PN_LAUNCH_W(K, 8, 6);                                                            \
+            else PN_LAUNCH_W(K, 4, 6);                                                                    \
+        } else if (np == 3) PN_LAUNCH_W(K, 8, 3);                                                         \
+        else PN_LAUNCH_W(K, 8, 1);                                                                        \
         EQH_CHECK_LAUNCH();                                                                               \
     } while (0)
     switch (stage) {
@@ -1659,39 +1706,40 @@ struct PanelSum {
     int64_t ldd;
     float* out;
     int64_t ldo;
+    int wplanes;
 };
 
-template <int C, int NW, int NG>
+template <int C, int NW, int NG, int NP>
 PN_KERNEL(NW) k_panel_sum(const PanelSum p) {
     using S = PnShape<C, NW>;
-    __shared__ uint4 s_img[2][3 * S::KS * 64];
+    __shared__ uint4 s_img[2][pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RtPos<NW> P((int)blockIdx.x * PN_ROWS, p.rows, wave, lane);
     const bool mul = wave < S::NT;
     RowTile<C, NW> x;
     rt_load<C, NW>(x, p.A[0], p.lda[0], P.rowc, P.c4);
-    WStream<S::KS, S::NTW, NG, NW> ws;
+    WStream<S::KS, S::NTW, NG, NW, NP> ws(p.wplanes);
 #pragma unroll
     for (int g = 0; g < NG; ++g) ws.init(g, p.W[g], mul ? wave : 0, lane);
     ws.prime();
     __builtin_amdgcn_sched_barrier(0);
-    rt_a_put<C, NW, S::KS>(x, s_img[0], P.lrow, P.c);
+    rt_a_put<C, NW, S::KS, NP>(x, s_img[0], P.lrow, P.c);
     if (NG > 1) rt_load<C, NW>(x, p.A[1], p.lda[1], P.rowc, P.c4);        // (in flight during product 0)
     __syncthreads();
     f32x16 acc[1][S::NTW];
     acc_zero<1, S::NTW>(acc);
-    if (mul) panel_mma_part<S::KS, S::NTW, NG, NW, 0>(s_img[0], ws, acc, lane);
+    if (mul) panel_mma_part<S::KS, S::NTW, NG, NW, NP, 0>(s_img[0], ws, acc, lane);
     if (NG > 1) {
-        rt_a_put<C, NW, S::KS>(x, s_img[1], P.lrow, P.c);                  // (nobody reads image 1 yet)
+        rt_a_put<C, NW, S::KS, NP>(x, s_img[1], P.lrow, P.c);                  // (nobody reads image 1 yet)
         if (NG > 2) rt_load<C, NW>(x, p.A[2], p.lda[2], P.rowc, P.c4);
         __syncthreads();                                                   // image 1 complete; image 0 free
-        if (mul) panel_mma_part<S::KS, S::NTW, NG, NW, (NG > 1 ? 1 : 0)>(s_img[1], ws, acc, lane);
+        if (mul) panel_mma_part<S::KS, S::NTW, NG, NW, NP, (NG > 1 ? 1 : 0)>(s_img[1], ws, acc, lane);
     }
     if (NG > 2) {
-        rt_a_put<C, NW, S::KS>(x, s_img[0], P.lrow, P.c);
+        rt_a_put<C, NW, S::KS, NP>(x, s_img[0], P.lrow, P.c);
         __syncthreads();
-        if (mul) panel_mma_part<S::KS, S::NTW, NG, NW, (NG > 2 ? 2 : 0)>(s_img[0], ws, acc, lane);
+        if (mul) panel_mma_part<S::KS, S::NTW, NG, NW, NP, (NG > 2 ? 2 : 0)>(s_img[0], ws, acc, lane);
     }
     if (mul) acc_to_staging<S::NTW, NW>(s_stg, acc[0], wave, lane);
     __syncthreads();
@@ -1710,35 +1758,36 @@ PN_KERNEL(NW) k_panel_sum(const PanelSum p) {
 extern "C" int hg_panel_sum(const HgPanelSum* q, void* stream_) {
     if (!q || q->rows < 0 || q->n < 1 || q->n > 3 || !q->out) return EQH_ERR_ARG;
     const int C = q->C;
-    if (!pn_width_ok(C)) return EQH_ERR_ARG;
+    int np, ip;
+    if (!pn_width_ok(C) || !pn_mode(q->products, q->planes, np, ip)) return EQH_ERR_ARG;
     if (q->rows >= ((int64_t)1 << 31) - 64) return EQH_ERR_RANGE;
     if (!eqh_aligned16(q->out) || (q->ldo & 3) || !eqh_aligned16(q->d) || (q->d && (q->ldd & 3))) return EQH_ERR_ALIGN;
     PanelSum p{};
-    p.rows = (int)q->rows; p.D = q->d; p.ldd = q->ldd; p.out = q->out; p.ldo = q->ldo;
+    p.rows = (int)q->rows; p.D = q->d; p.ldd = q->ldd; p.out = q->out; p.ldo = q->ldo; p.wplanes = ip;
     for (int g = 0; g < q->n; ++g) {
         if (!q->a[g] || !q->w[g]) return EQH_ERR_ARG;
         if (!eqh_aligned16(q->a[g]) || (q->lda[g] & 3) || !eqh_aligned16(q->w[g])) return EQH_ERR_ALIGN;
         p.A[g] = q->a[g]; p.lda[g] = q->lda[g]; p.W[g] = static_cast<const uint4*>(q->w[g]);
     }
     if (q->rows == 0) return EQH_OK;
-    const int nw = pn_waves();
+    const int nw = pn_waves(np);
     const dim3 grid((unsigned)((q->rows + PN_ROWS - 1) / PN_ROWS)), block(64 * nw);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define PN_SUM_C(NW_, NG_)                                                                                     \
+#define PN_SUM_C(NW_, NP_, NG_)                                                                                \
     do {                                                                                                       \
-        if (C == 256) hipLaunchKernelGGL((k_panel_sum<256, NW_, NG_>), grid, block, 0, stream, p);             \
-        else if (C == 128) hipLaunchKernelGGL((k_panel_sum<128, NW_, NG_>), grid, block, 0, stream, p);        \
-        else hipLaunchKernelGGL((k_panel_sum<64, NW_, NG_>), grid, block, 0, stream, p);                       \
+        if (C == 256) hipLaunchKernelGGL((k_panel_sum<256, NW_, NG_, NP_>), grid, block, 0, stream, p);        \
+        else if (C == 128) hipLaunchKernelGGL((k_panel_sum<128, NW_, NG_, NP_>), grid, block, 0, stream, p);   \
+        else hipLaunchKernelGGL((k_panel_sum<64, NW_, NG_, NP_>), grid, block, 0, stream, p);                  \
     } while (0)
-#define PN_SUM(NG_)                                                                                            \
-    do {                                                                                                       \
-        if (nw == 8) PN_SUM_C(8, NG_);                                                                         \
-        else PN_SUM_C(4, NG_);                                                                                 \
-    } while (0)
-    if (q->n == 1) PN_SUM(1);
-    else if (q->n == 2) PN_SUM(2);
-    else PN_SUM(3);
-#undef PN_SUM
+#define PN_SUM1(NW_, NP_) PN_SUM_C(NW_, NP_, 1)
+#define PN_SUM2(NW_, NP_) PN_SUM_C(NW_, NP_, 2)
+#define PN_SUM3(NW_, NP_) PN_SUM_C(NW_, NP_, 3)
+    if (q->n == 1) PN_BY_MODE(PN_SUM1);
+    else if (q->n == 2) PN_BY_MODE(PN_SUM2);
+    else PN_BY_MODE(PN_SUM3);
+#undef PN_SUM1
+#undef PN_SUM2
+#undef PN_SUM3
 #undef PN_SUM_C
     EQH_CHECK_LAUNCH();
     return EQH_OK;
@@ -1747,11 +1796,12 @@ extern "C" int hg_panel_sum(const HgPanelSum* q, void* stream_) {
 extern "C" int hg_panel_multi(const HgPanelMulti* q, void* stream_) {
     if (!q || q->rows < 0 || !q->a || q->n < 1 || q->n > 3) return EQH_ERR_ARG;
     const int C = q->C;
-    if (!pn_width_ok(C)) return EQH_ERR_ARG;
+    int np, ip;
+    if (!pn_width_ok(C) || !pn_mode(q->products, q->planes, np, ip)) return EQH_ERR_ARG;
     if (q->rows >= ((int64_t)1 << 31) - 64) return EQH_ERR_RANGE;
     if ((q->lda & 3) || !eqh_aligned16(q->a)) return EQH_ERR_ALIGN;
     PanelMulti p{};
-    p.A = q->a; p.lda = q->lda; p.rows = (int)q->rows;
+    p.A = q->a; p.lda = q->lda; p.rows = (int)q->rows; p.wplanes = ip;
     for (int g = 0; g < q->n; ++g) {
         if (!q->w[g] || !q->out[g]) return EQH_ERR_ARG;
         if (!eqh_aligned16(q->w[g]) || !eqh_aligned16(q->out[g]) || !eqh_aligned16(q->bias[g]) || !eqh_aligned16(q->d[g]) ||
@@ -1761,24 +1811,24 @@ extern "C" int hg_panel_multi(const HgPanelMulti* q, void* stream_) {
         p.ldd[g] = q->ldd[g]; p.out[g] = q->out[g]; p.ldo[g] = q->ldo[g];
     }
     if (q->rows == 0) return EQH_OK;
-    const int nw = pn_waves();
+    const int nw = pn_waves(np);
     const dim3 grid((unsigned)((q->rows + PN_ROWS - 1) / PN_ROWS)), block(64 * nw);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define PN_MULTI_C(NW_, NG_)                                                                                   \
+#define PN_MULTI_C(NW_, NP_, NG_)                                                                              \
     do {                                                                                                       \
-        if (C == 256) hipLaunchKernelGGL((k_panel_multi<256, NW_, NG_>), grid, block, 0, stream, p);           \
-        else if (C == 128) hipLaunchKernelGGL((k_panel_multi<128, NW_, NG_>), grid, block, 0, stream, p);      \
-        else hipLaunchKernelGGL((k_panel_multi<64, NW_, NG_>), grid, block, 0, stream, p);                     \
+        if (C == 256) hipLaunchKernelGGL((k_panel_multi<256, NW_, NG_, NP_>), grid, block, 0, stream, p);      \
+        else if (C == 128) hipLaunchKernelGGL((k_panel_multi<128, NW_, NG_, NP_>), grid, block, 0, stream, p); \
+        else hipLaunchKernelGGL((k_panel_multi<64, NW_, NG_, NP_>), grid, block, 0, stream, p);                \
     } while (0)
-#define PN_MULTI(NG_)                                                                                          \
-    do {                                                                                                       \
-        if (nw == 8) PN_MULTI_C(8, NG_);                                                                       \
-        else PN_MULTI_C(4, NG_);                                                                               \
-    } while (0)
-    if (q->n == 1) PN_MULTI(1);
-    else if (q->n == 2) PN_MULTI(2);
-    else PN_MULTI(3);
-#undef PN_MULTI
+#define PN_MULTI1(NW_, NP_) PN_MULTI_C(NW_, NP_, 1)
+#define PN_MULTI2(NW_, NP_) PN_MULTI_C(NW_, NP_, 2)
+#define PN_MULTI3(NW_, NP_) PN_MULTI_C(NW_, NP_, 3)
+    if (q->n == 1) PN_BY_MODE(PN_MULTI1);
+    else if (q->n == 2) PN_BY_MODE(PN_MULTI2);
+    else PN_BY_MODE(PN_MULTI3);
+#undef PN_MULTI1
+#undef PN_MULTI2
+#undef PN_MULTI3
 #undef PN_MULTI_C
     EQH_CHECK_LAUNCH();
     return EQH_OK;
@@ -1796,10 +1846,12 @@ extern "C" int hg_panel_debug_flags(int flags) {
 }
 #endif
 
-extern "C" size_t hg_panel_pack_bytes(int32_t K, int32_t N) {
-    if (K <= 0 || N <= 0 || (K & 15) || (N & 31)) return 0;
-    return (size_t)K * (size_t)N * 6;
+extern "C" size_t hg_panel_pack_bytes_p(int32_t K, int32_t N, int32_t planes) {
+    if (K <= 0 || N <= 0 || (K & 15) || (N & 31) || planes < 1 || planes > 3) return 0;
+    return (size_t)K * (size_t)N * 2 * (size_t)planes;
 }
+
+extern "C" size_t hg_panel_pack_bytes(int32_t K, int32_t N) { return hg_panel_pack_bytes_p(K, N, 3); }
 
 extern "C" int hg_panel_pack(int32_t n_items, const HgPanelPack* items, void* stream_) {
     if (n_items <= 0 || !items) return EQH_ERR_ARG;
@@ -1811,11 +1863,13 @@ extern "C" int hg_panel_pack(int32_t n_items, const HgPanelPack* items, void* st
         for (int i = 0; i < b.n; ++i) {
             const HgPanelPack& q = items[i0 + i];
             if (!q.w || !q.dst || q.K <= 0 || q.N <= 0 || q.kstep0 < 0) return EQH_ERR_ARG;
+            const int planes = q.planes ? q.planes : 3;
+            if (planes < 1 || planes > 3 || (q.k_major && planes != 3)) return EQH_ERR_ARG;
             if ((q.K & 15) || (q.N & 31) || (q.ld & 3) || !eqh_aligned16(q.w) || !eqh_aligned16(q.dst)) return EQH_ERR_ALIGN;
             const int total = q.ksteps_total > 0 ? q.ksteps_total : q.K / 16;
             if (q.kstep0 + q.K / 16 > total) return EQH_ERR_ARG;
             const int n_valid = (q.n_valid > 0 && q.n_valid < q.N) ? q.n_valid : q.N;
-            b.it[i] = PackItem{q.w, q.ld, static_cast<uint4*>(q.dst), q.K, q.N, q.trans ? 1 : 0, q.kstep0, total, n_valid, q.k_major ? 1 : 0};
+            b.it[i] = PackItem{q.w, q.ld, static_cast<uint4*>(q.dst), q.K, q.N, q.trans ? 1 : 0, q.kstep0, total, n_valid, q.k_major ? 1 : 0, planes};
             b.first[i + 1] = b.first[i] + (q.K / 16) * (q.N / 32);
         }
         for (int i = b.n; i < PN_MAXPACK; ++i) { b.it[i] = b.it[0]; b.first[i + 1] = b.first[b.n]; }
@@ -1830,17 +1884,18 @@ extern "C" int hg_panel_stream_supported(int32_t K, int32_t N) {
     return (K == 64 || K == 128 || K == 256) && (N == 128 || N == 256);
 }
 
-extern "C" int hg_panel_stream_gemm_f32(const float* a, int64_t lda, int64_t rows, int32_t K, int32_t N, const void* wpack, float alpha,
-                                        const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
-                                        void* stream_) {
-    if (rows < 0 || !a || !wpack || !c) return EQH_ERR_ARG;
+extern "C" int hg_panel_stream_gemm_f32_p(const float* a, int64_t lda, int64_t rows, int32_t K, int32_t N, const void* wpack, float alpha,
+                                          const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
+                                          int32_t products, int32_t planes, void* stream_) {
+    int np, ip;
+    if (rows < 0 || !a || !wpack || !c || !pn_mode(products, planes, np, ip)) return EQH_ERR_ARG;
     if (!hg_panel_stream_supported(K, N)) return EQH_ERR_ARG;
     if ((lda & 3) || (ldc & 3) || (d && (ldd & 3)) || !eqh_aligned16(a) || !eqh_aligned16(c) || !eqh_aligned16(d) ||
         !eqh_aligned16(bias) || !eqh_aligned16(wpack))
         return EQH_ERR_ALIGN;
     if (rows >= ((int64_t)1 << 31) - 64) return EQH_ERR_RANGE;
     if (rows == 0) return EQH_OK;
-    PanelPlain p{a, lda, (int)rows, static_cast<const uint4*>(wpack), alpha, beta, d, ldd, bias, relu, c, ldc};
+    PanelPlain p{a, lda, (int)rows, static_cast<const uint4*>(wpack), alpha, beta, d, ldd, bias, relu, c, ldc, ip};
     const int n_panels = (int)((rows + PN_ROWS - 1) / PN_ROWS);
     static const int n_cu = [] {
         int dev = 0, n = 0;
@@ -1849,10 +1904,54 @@ extern "C" int hg_panel_stream_gemm_f32(const float* a, int64_t lda, int64_t row
     }();
     const dim3 grid((unsigned)(n_panels < n_cu ? n_panels : n_cu)), block(1024);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define PN_STREAM(K_, N_) if (K == K_ && N == N_) hipLaunchKernelGGL((k_panel_stream<K_, N_>), grid, block, 0, stream, p, n_panels)
-    PN_STREAM(256, 256); else PN_STREAM(128, 256); else PN_STREAM(64, 256);
-    else PN_STREAM(256, 128); else PN_STREAM(128, 128); else PN_STREAM(64, 128);
+#define PN_STREAM(K_, N_)                                                                                                \
+    if (K == K_ && N == N_) {                                                                                            \
+        if (np == 6) hipLaunchKernelGGL((k_panel_stream<K_, N_, 6>), grid, block, 0, stream, p, n_panels);               \
+        else if (np == 3) hipLaunchKernelGGL((k_panel_stream<K_, N_, 3>), grid, block, 0, stream, p, n_panels);          \
+        else hipLaunchKernelGGL((k_panel_stream<K_, N_, 1>), grid, block, 0, stream, p, n_panels);                       \
+    }
+    PN_STREAM(256, 256) else PN_STREAM(128, 256) else PN_STREAM(64, 256)
+    else PN_STREAM(256, 128) else PN_STREAM(128, 128) else PN_STREAM(64, 128)
 #undef PN_STREAM
+    EQH_CHECK_LAUNCH();
+    return EQH_OK;
+}
+
+extern "C" int hg_panel_stream_gemm_f32(const float* a, int64_t lda, int64_t rows, int32_t K, int32_t N, const void* wpack, float alpha,
+                                        const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
+                                        void* stream_) {
+    return hg_panel_stream_gemm_f32_p(a, lda, rows, K, N, wpack, alpha, d, ldd, beta, bias, relu, c, ldc, 6, 3, stream_);
+}
+
+extern "C" int hg_panel_gemm_f32_p(const float* a, int64_t lda, int64_t rows, int32_t C, const void* wpack, float alpha,
+                                   const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
+                                   int32_t products, int32_t planes, void* stream_) {
+    int np, ip;
+    if (rows < 0 || !a || !wpack || !c || !pn_mode(products, planes, np, ip)) return EQH_ERR_ARG;
+    if (!pn_width_ok(C)) return EQH_ERR_ARG;
+    if ((lda & 3) || (ldc & 3) || (d && (ldd & 3)) || !eqh_aligned16(a) || !eqh_aligned16(c) || !eqh_aligned16(d) ||
+        !eqh_aligned16(bias) || !eqh_aligned16(wpack))
+        return EQH_ERR_ALIGN;
+    if (rows >= ((int64_t)1 << 31) - 64) return EQH_ERR_RANGE;
+    if (rows == 0) return EQH_OK;
+    PanelPlain p{a, lda, (int)rows, static_cast<const uint4*>(wpack), alpha, beta, d, ldd, bias, relu, c, ldc, ip};
+    const int nw = pn_waves(np);
+    const dim3 grid((unsigned)((rows + PN_ROWS - 1) / PN_ROWS)), block(64 * nw);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    static const bool pair = [] { const char* e = getenv("EQH_PANEL_PAIR"); return e && e[0] == '1'; }();
+    if (pair && C == 256 && np == 6) {      // measurement aid: see k_panel_plain_pair
+        hipLaunchKernelGGL((k_panel_plain_pair<256>), dim3(grid.x, 2), dim3(256), 0, stream, p);
+        EQH_CHECK_LAUNCH();
+        return EQH_OK;
+    }
+#define PN_PLAIN(NW_, NP_)                                                                                  \
+    do {                                                                                                    \
+        if (C == 256) hipLaunchKernelGGL((k_panel_plain<256, NW_, NP_>), grid, block, 0, stream, p);       \
+        else if (C == 128) hipLaunchKernelGGL((k_panel_plain<128, NW_, NP_>), grid, block, 0, stream, p);  \
+        else hipLaunchKernelGGL((k_panel_plain<64, NW_, NP_>), grid, block, 0, stream, p);                 \
+    } while (0)
+    PN_BY_MODE(PN_PLAIN);
+#undef PN_PLAIN
     EQH_CHECK_LAUNCH();
     return EQH_OK;
 }
@@ -1860,32 +1959,5 @@ extern "C" int hg_panel_stream_gemm_f32(const float* a, int64_t lda, int64_t row
 extern "C" int hg_panel_gemm_f32(const float* a, int64_t lda, int64_t rows, int32_t C, const void* wpack, float alpha,
                                  const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
                                  void* stream_) {
-    if (rows < 0 || !a || !wpack || !c) return EQH_ERR_ARG;
-    if (!pn_width_ok(C)) return EQH_ERR_ARG;
-    if ((lda & 3) || (ldc & 3) || (d && (ldd & 3)) || !eqh_aligned16(a) || !eqh_aligned16(c) || !eqh_aligned16(d) ||
-        !eqh_aligned16(bias) || !eqh_aligned16(wpack))
-        return EQH_ERR_ALIGN;
-    if (rows >= ((int64_t)1 << 31) - 64) return EQH_ERR_RANGE;
-    if (rows == 0) return EQH_OK;
-    PanelPlain p{a, lda, (int)rows, static_cast<const uint4*>(wpack), alpha, beta, d, ldd, bias, relu, c, ldc};
-    const int nw = pn_waves();
-    const dim3 grid((unsigned)((rows + PN_ROWS - 1) / PN_ROWS)), block(64 * nw);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    static const bool pair = [] { const char* e = getenv("EQH_PANEL_PAIR"); return e && e[0] == '1'; }();
-    if (pair && C == 256) {      // measurement aid: see k_panel_plain_pair
-        hipLaunchKernelGGL((k_panel_plain_pair<256>), dim3(grid.x, 2), dim3(256), 0, stream, p);
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
-    }
-#define PN_PLAIN(NW_)                                                                                       \
-    do {                                                                                                    \
-        if (C == 256) hipLaunchKernelGGL((k_panel_plain<256, NW_>), grid, block, 0, stream, p);            \
-        else if (C == 128) hipLaunchKernelGGL((k_panel_plain<128, NW_>), grid, block, 0, stream, p);       \
-        else hipLaunchKernelGGL((k_panel_plain<64, NW_>), grid, block, 0, stream, p);                      \
-    } while (0)
-    if (nw == 8) PN_PLAIN(8);
-    else PN_PLAIN(4);
-#undef PN_PLAIN
-    EQH_CHECK_LAUNCH();
-    return EQH_OK;
+    return hg_panel_gemm_f32_p(a, lda, rows, C, wpack, alpha, d, ldd, beta, bias, relu, c, ldc, 6, 3, stream_);
 }

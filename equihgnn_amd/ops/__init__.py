@@ -41,7 +41,7 @@ from .products import (  # noqa: F401
     X6_MIN_OUTPUTS, X6_MAX_K, X6_DEEP_ROWS, X6_WGRAD_OUTPUTS, X6_WGRAD_ROWS, USE_X6, _x6_ok, mm_nt, mm_nn, small_mm_batch,
 )
 from .panel import (  # noqa: F401
-    PANEL_WIDTHS, panel_supported, panel_pack, panel_pack_bytes, panel_gemm, panel_stream_gemm, panel_stream_supported,
+    PANEL_WIDTHS, panel_supported, panel_pack, panel_pack_bytes, panel_planes, panel_gemm, panel_stream_gemm, panel_stream_supported,
     conv_panel, conv_panel_slab,
 )
 from .grads import (  # noqa: F401

@@ -16,7 +16,8 @@ from ._base import (LINEAR_PARAMS, _acc_target, _f32c, _note_acc, _ptr, _require
 from .aggregate import entry_weights
 from .grads import (_linear_weight_grad, _wgrad_deferred, colsum)
 from .rows import inc_fwd_col_bytes
-from .panel import (conv_panel, conv_panel_slab, panel_gemm, panel_pack, panel_supported)
+from .panel import (_products, backward_as_forward, conv_panel, conv_panel_slab, panel_gemm, panel_pack, panel_planes,
+                    panel_supported)
 
 FOLD_B2 = not os.environ.get("EQH_NO_B2_FOLD")     # dhbar = dqb w12 inside B1 (after its gather) instead of a launch of its own
 FOLD_INC = not os.environ.get("EQH_NO_INC_FOLD")   # the incidence aggregation (k_inc_fwd_col) as the prologue of F3 instead of a launch
@@ -52,11 +53,12 @@ class _MergedConvStack(torch.autograd.Function):
         dev = X.device
         M = ix.by_e.n_rows
         need_grad = any(ctx.needs_input_grad)
+        ctx.products = _products()       # (the panel products' matmul precision, read once: the backward pass multiplies alike)
         W2v = W2a[:, :C]
         items = [(W1a, True), (W2v, True), (w12, True), (w23, True), (W3b, True)]
         if need_grad:
             items += [(W3b, False), (w23, False), (w12, False), [(W1a, False), (W2v, False)]]
-        imgs = panel_pack(items)
+        imgs = panel_pack(items, planes=panel_planes())
         iW1a, iW2v, iw12, iw23, iW3b = imgs[:5]
         new = lambda r: torch.empty((r, C), dtype=torch.float32, device=dev)
         flops = lambda rows, n: 2 * rows * C * C * n
@@ -109,6 +111,7 @@ class _MergedConvStack(torch.autograd.Function):
         return xn.view_as(xn)
 
     @staticmethod
+    @backward_as_forward
     def backward(ctx, dout):
         W1a, b1a, g1, W2a, g2, w12, w23, b3a, g3, W3b = ctx.saved_tensors
         ix, L, scale, eps, relu_out = ctx.meta

@@ -15,6 +15,7 @@ from ._base import (
 from .aggregate import (CSR)
 from .products import (USE_X6, X6_WGRAD_ROWS, gemm, gemm_supported, mm_nn, mm_nt)
 from .grads import (_merged_acc, _wgrad_deferred, colsum)
+from .panel import backward_as_forward
 
 
 class _EgnnEdge(torch.autograd.Function):
@@ -258,8 +259,9 @@ class _EgnnNodeMlp(torch.autograd.Function):
     def forward(ctx, normed, m_i, res, w0, b0, w3, b3, gamma=None, beta=None, eps=0.0):
         """``gamma`` given (round 6): ``normed`` is the RAW feature rows, LayerNorm(gamma, beta, eps) is formed inside the
         launch (and its backward inside the backward launch), ``res`` is ignored (the residual is the same rows)."""
-        from .panel import conv_panel, panel_pack
+        from .panel import _products, conv_panel, panel_pack, panel_planes
         _require_gpu(normed, "egnn_node_mlp")
+        ctx.products = _products()       # (the panel products' matmul precision, read once: the backward pass multiplies alike)
         ctx.fold = gamma is not None
         normed, m_i = _f32c(normed), _f32c(m_i)
         res = normed if ctx.fold else _f32c(res)
@@ -269,7 +271,7 @@ class _EgnnNodeMlp(torch.autograd.Function):
         items = [(w0[:C], True), (w0[C:], True), (w3, True)]
         if need_grad:
             items += [(w3[:, :C], False), (w3[:, C:], False), (w0, False, C + 32)]
-        imgs = panel_pack(items)
+        imgs = panel_pack(items, planes=panel_planes())
         node_in = torch.empty((N, C + 16), dtype=torch.float32, device=dev)
         hpre = torch.empty((N, 2 * C), dtype=torch.float32, device=dev)
         hid = torch.empty_like(hpre)
@@ -288,6 +290,7 @@ class _EgnnNodeMlp(torch.autograd.Function):
         return out
 
     @staticmethod
+    @backward_as_forward
     def backward(ctx, dout):
         from .panel import conv_panel, conv_panel_slab
         from .grads import _linear_weight_grad

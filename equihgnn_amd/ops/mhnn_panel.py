@@ -32,18 +32,20 @@ from .. import hip
 from ._base import (LINEAR_PARAMS, _acc_target, _f32c, _note_acc, _ptr, _require_gpu, _stream, _workspace, timed)
 from .grads import (_linear_weight_grad, colsum)
 from .conv_stack import (_sum_opt, _wgrad_scaled)
-from .panel import (conv_panel, conv_panel_slab, panel_pack, panel_supported)
+from .panel import (_image_planes, _products, backward_as_forward, conv_panel, conv_panel_slab, panel_pack, panel_planes,
+                    panel_supported)
 from .rows import inc_fwd_col_bytes
 
 USE_MHNN_PANEL = not os.environ.get("EQH_NO_MHNN_PANEL")     # tests / A-B runs switch the panel path of MHNNConv off
 
 
-def panel_multi(a, C, items, rows=None):
+def panel_multi(a, C, items, rows=None, products=None):
     """out[g] = a @ B_g + rw_g[:, None] * bias_g + d_g for up to three packed [C x C] images sharing the A rows (hg_panel_multi).
     ``items``: [(image, bias or None, rw or None, d or None, out)]."""
     a = _f32c(a)
     q = hip.HgPanelMulti()
     q.a, q.lda, q.rows, q.C, q.n = a.data_ptr(), a.stride(0), a.shape[0] if rows is None else rows, C, len(items)
+    q.products, q.planes = _products(products), _image_planes("panel_multi", *((it[0], C, C) for it in items))
     for g, (img, bias, rw, d, out) in enumerate(items):
         q.w[g], q.out[g], q.ldo[g] = img.data_ptr(), out.data_ptr(), out.stride(0)
         q.bias[g] = bias.data_ptr() if bias is not None else None
@@ -56,7 +58,7 @@ def panel_multi(a, C, items, rows=None):
 PANEL_SUM = not os.environ.get("EQH_NO_PANEL_SUM")      # (off: the chained single-product launches of rounds 4-5, for A/B runs)
 
 
-def panel_sum(items, C, out, d=None, rows=None):
+def panel_sum(items, C, out, d=None, rows=None, products=None):
     """out = sum_g a_g @ B_g + d for up to three (a_g [rows, C], packed [C x C] image) pairs over the same rows, one launch
     (hg_panel_sum)."""
     q = hip.HgPanelSum()
@@ -66,6 +68,7 @@ def panel_sum(items, C, out, d=None, rows=None):
         keep.append(a)
         q.a[g], q.lda[g], q.w[g] = a.data_ptr(), a.stride(0), img.data_ptr()
     q.rows, q.C, q.n = (keep[0].shape[0] if rows is None else rows), C, len(items)
+    q.products, q.planes = _products(products), _image_planes("panel_sum", *((it[1], C, C) for it in items))
     q.d, q.ldd = (d.data_ptr(), d.stride(0)) if d is not None else (None, 0)
     q.out, q.ldo = out.data_ptr(), out.stride(0)
     hip.check(hip.lib().hg_panel_sum(ctypes.byref(q), _stream(out.device)), "hg_panel_sum")
@@ -106,12 +109,13 @@ class _MHNNConvPanel(torch.autograd.Function):
         M = E.shape[0]
         dev = X.device
         need_grad = any(ctx.needs_input_grad)
+        ctx.products = _products()       # (the panel products' matmul precision, read once: the backward pass multiplies alike)
         # (`packed`: the images of this application, packed with those of the model's other layers in ONE launch by the
         # merged_scope around them -- with or without the backward ones, as the scope saw fit)
         if packed is not None and len(packed) >= (20 if need_grad else 10):
             imgs = packed
         else:
-            imgs = panel_pack(_pack_items(C, W1a, W2a, W2b, W3a, W4a, W4b, w12, w34, need_grad))
+            imgs = panel_pack(_pack_items(C, W1a, W2a, W2b, W3a, W4a, W4b, w12, w34, need_grad), planes=panel_planes())
         iW1x, iW3x, iW4x, iW1e, iW2e, iw12, iW2b, iW3e, iw34, iW4b = imgs[:10]
         new = lambda r: torch.empty((r, C), dtype=torch.float32, device=dev)
         flops = lambda rows, n: 2 * rows * C * C * n
@@ -146,6 +150,7 @@ class _MHNNConvPanel(torch.autograd.Function):
         return Xn, En
 
     @staticmethod
+    @backward_as_forward
     def backward(ctx, dXn, dEn):
         X, E, W1a, W2a, W2b, W3a, W4a, W4b, w12, w34, g1, g3, b2a, g2, b4a, g4, En = ctx.saved_tensors
         pa1, pa3, qb1, qb3, s_e, u_e, x3_e, s_v, u_v, x3_v = ctx.rows
@@ -296,7 +301,7 @@ class merged_scope:
                 (w12, _), (w34, _) = self.merged[id(c)]
                 lists.append(_pack_items(self.C, c.W1.lins[0].weight, c.W2.lins[0].weight, c.W2.lins[1].weight, c.W3.lins[0].weight,
                                          c.W4.lins[0].weight, c.W4.lins[1].weight, w12, w34, need_grad))
-            imgs = panel_pack([it for lst in lists for it in lst]) if lists else []
+            imgs = panel_pack([it for lst in lists for it in lst], planes=panel_planes()) if lists else []
             off = 0
             for c, lst in zip(self.convs_packed, lists):
                 self.packed[id(c)] = imgs[off:off + len(lst)]

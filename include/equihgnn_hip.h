@@ -123,8 +123,9 @@ int hg_gemm_x6_batch(int32_t n_problems, const HgGemmProblem* problems, int32_t 
  * planes (a stage of P / 3 the LDS), the multiplying wavefronts issue P (P + 1) / 2 MFMAs per tile and K step.  Epilogues, split-K,
  * batching, transposition and bitwise reproducibility as above.  A pre-split image (b_packed) holds three planes and goes with
  * products == 6 only: EQH_ERR_ARG otherwise.  hg_gemm_x6_choose_tile and hg_gemm_x6_workspace_bytes hold for every mode: the
- * split-K plan and the tile do not depend on `products`.  Not covered (fp32 grade under every mode): the panel kernels, the EGNN
- * edge kernel's second Linear, the batched weight-gradient kernels. */
+ * split-K plan and the tile do not depend on `products`.  Not covered here: the panel kernels take a product count of their own
+ * (below: `products` / `planes` of their entry points); the EGNN edge kernel's second Linear and the batched weight-gradient
+ * kernels stay at fp32 grade under every mode. */
 int hg_gemm_bf16_batch(int32_t n_problems, const HgGemmProblem* problems, int32_t tile, int32_t products, void* workspace,
                        size_t workspace_bytes, void* stream);
 
@@ -162,7 +163,19 @@ int hg_small_mm_batch(int32_t n_problems, const HgSmallMM* problems, void* strea
  * or B[k][n] = w[k * ld + n] (trans == 0: the same weight used as dY W), K x N (K % 16 == 0, N % 32 == 0), into the image
  * at dst, hg_panel_pack_bytes(K_total, N) bytes; kstep0 / ksteps_total (in units of 16 k; 0 = this item alone) stack
  * several weights along K in one image.  All items in ONE launch (per 32).
- * hg_panel_gemm_f32: c = act(alpha * a . B + beta * d + bias), a [rows, C] (lda), B the packed C x C image. */
+ * hg_panel_gemm_f32: c = act(alpha * a . B + beta * d + bias), a [rows, C] (lda), B the packed C x C image.
+ *
+ * Matmul precision of the panel kernels.  Every panel entry point that multiplies takes `products` (6, 3 or 1; 0 = 6) and
+ * `planes` (3, 2 or 1; 0 = 3: the planes the weight images of the call were packed with) -- as trailing arguments of the `_p`
+ * variants, as the last two fields of HgConvPanel / HgPanelMulti / HgPanelSum.  `products` has the meaning it has for
+ * hg_gemm_bf16_batch: rows and weights are cut to P = 3, 2, 1 bf16 planes and the terms a_i b_j with i + j < P are summed in
+ * fp32, smallest first -- 6: a1b1 a0b2 a2b0 a0b1 a1b0 a0b0 (bit for bit what the entry points without the arguments compute),
+ * 3: a0b1 a1b0 a0b0, 1: a0b0, with the error bounds stated there.  The row images in LDS hold P planes, a wavefront fetches P
+ * planes of the weight.  Any other `products`, a `planes` outside 1..3 or smaller than P: EQH_ERR_ARG, nothing launched.  An image
+ * of more planes than P serves (the three-plane image serves every mode); one of exactly P planes is the shortest stream.
+ * HgPanelPack.planes (0 = 3) lays down the leading planes only, hg_panel_pack_bytes_p(K, N, planes) bytes; a k_major image
+ * (HgGemmProblem.b_packed) has three.  With products < 6 a launch has eight wavefronts per panel whatever EQH_PANEL_WAVES says.
+ * Row-wise work (bias, ReLU, LayerNorm, SiLU, the gathered means, every reduction) is fp32 in every mode. */
 typedef struct {
     const float* w;
     int64_t ld;
@@ -171,12 +184,17 @@ typedef struct {
     int32_t n_valid;     /* 0 or N: all columns; else columns n >= n_valid of B are zero (N padded to a multiple of 32) */
     int32_t k_major;     /* != 0: image[k / 32][tile n / 32][k half][plane][lane] -- the form HgGemmProblem.b_packed takes (a K step
                             of 32 of ALL column tiles contiguous; needs (kstep0 + K / 16) even); 0: image[tile][k / 16][plane][lane] */
+    int32_t planes;      /* 0 or 3: all three planes; 2, 1: the leading planes only (image[tile][k / 16][plane < planes][lane]) */
 } HgPanelPack;
 size_t hg_panel_pack_bytes(int32_t K, int32_t N);
+size_t hg_panel_pack_bytes_p(int32_t K, int32_t N, int32_t planes);
 int hg_panel_pack(int32_t n_items, const HgPanelPack* items, void* stream);
 int hg_panel_gemm_f32(const float* a, int64_t lda, int64_t rows, int32_t C, const void* wpack, float alpha,
                       const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
                       void* stream);
+int hg_panel_gemm_f32_p(const float* a, int64_t lda, int64_t rows, int32_t C, const void* wpack, float alpha,
+                        const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
+                        int32_t products, int32_t planes, void* stream);
 /* hg_panel_stream_gemm_f32: the same product for MANY rows and a rectangular weight -- a [rows, K] (lda), B the packed K x N
  * image (hg_panel_pack), K in {64, 128, 256}, N in {128, 256} (hg_panel_stream_supported): one persistent workgroup per CU walks
  * 32-row panels with two A images in LDS (the next panel's rows are fetched and split behind the current panel's MFMA loop).
@@ -185,6 +203,9 @@ int hg_panel_stream_supported(int32_t K, int32_t N);
 int hg_panel_stream_gemm_f32(const float* a, int64_t lda, int64_t rows, int32_t K, int32_t N, const void* wpack, float alpha,
                              const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
                              void* stream);
+int hg_panel_stream_gemm_f32_p(const float* a, int64_t lda, int64_t rows, int32_t K, int32_t N, const void* wpack, float alpha,
+                               const float* d, int64_t ldd, float beta, const float* bias, int32_t relu, float* c, int64_t ldc,
+                               int32_t products, int32_t planes, void* stream);
 
 /* One application of the merged MHNNSConv (conv.py:169-182; layers.MHNNSConv._forward_merged) as panel stages: each launch
  * takes panels of 32 rows through one to four [C x C] products with the row-wise work between them (bias, ReLU, LayerNorm and
@@ -240,6 +261,8 @@ typedef struct {
     /* HG_CONV_F2 (round 6): an int32 device counter that the launch's first thread adds 1 to (eqh_signal_post folded into the
      * stage: the trainer's index-prefetch stream waits on it with eqh_signal_wait), or NULL. */
     int32_t* signal;
+    /* matmul precision of every product of the stage, and the planes of its weight images (see above; 0, 0 = 6 products, 3 planes) */
+    int32_t products, planes;
 } HgConvPanel;
 size_t hg_conv_panel_slab_bytes(int64_t rows, int32_t C);
 int hg_conv_panel(int32_t stage, const HgConvPanel* args, void* stream);
@@ -258,6 +281,7 @@ typedef struct {
     int64_t ldd[3];
     float* out[3];
     int64_t ldo[3];
+    int32_t products, planes;      /* matmul precision and the images' planes (0, 0 = 6 products, 3 planes) */
 } HgPanelMulti;
 int hg_panel_multi(const HgPanelMulti* args, void* stream);
 /* A SUM of up to three products over different row blocks of the same rows, one launch: out = sum_g a[g] W_g + d (d may be
@@ -274,6 +298,7 @@ typedef struct {
     int64_t ldd;
     float* out;
     int64_t ldo;
+    int32_t products, planes;      /* matmul precision and the images' planes (0, 0 = 6 products, 3 planes) */
 } HgPanelSum;
 int hg_panel_sum(const HgPanelSum* args, void* stream);
 /* wavefronts per panel workgroup the library launches (8; 4 with EQH_PANEL_WAVES=4 in the environment: round 4's geometry,

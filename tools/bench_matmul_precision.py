@@ -15,6 +15,19 @@ profiles/matmul_precision_bench.json).  Everything is timed in ONE process, "hig
 ``verdict`` says, per shape and mode, whether the mode is faster than "highest" by more than the two spreads.
 
     python tools/bench_matmul_precision.py [--blocks 7] [--steps 10] [--warmup 5] [--skip-steps]
+
+``--panels`` times what ``set_float32_matmul_precision(mode, panels=True)`` gives instead (default output
+profiles/panel_precision_bench.json), in the same way: a lone [4864 x 256].[256 x 256] row-panel product (ops.panel_gemm) with
+6 / 3 / 1 products, each with an image of exactly its planes and with the three-plane image, and the replayed training step of
+``egnn_equihnns`` and ``mhnnm`` (batch 256, hidden 256) under the ``--variants`` (default "highest", "medium" without the flag,
+"high+panels", "medium+panels"), interleaved in one process.  ``--merge [NAME=]FILE`` (repeatable) adds the result of another
+run of this tool on the same box under NAME (default ``other_build``): the same script run from a checkout of an earlier
+commit, with the variants that commit knows; a run with ``--full-images``, under which the operators pack three-plane images
+in every mode (the A/B of the reduced-plane images at step level); or a run against another build of the library
+(EQH_LIB_PATH).  ``--rows`` lists the row counts of the lone product.
+
+    python tools/bench_matmul_precision.py --panels [--variants highest,medium] [--rows 4864,16384] [--skip-products]
+                                           [--full-images] [--merge [NAME=]FILE]
 """
 from __future__ import annotations
 
@@ -96,14 +109,65 @@ def gemm_times(a, dev):
     return res
 
 
-def step_times(method, batch, flavour, seed0, a, dev):
+def _set_mode(variant):
+    import equihgnn_amd
+    mode, _, flag = variant.partition("+")
+    if flag == "panels":
+        equihgnn_amd.set_float32_matmul_precision(mode, panels=True)
+    else:
+        equihgnn_amd.set_float32_matmul_precision(mode)
+
+
+def panel_product_times(a, dev, rows=4864, C=256):
+    """a lone row-panel product under 6 / 3 / 1 products: hipGraphs of REPS launches, interleaved blocks between device events"""
+    from equihgnn_amd import ops
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(rows, C, generator=g).to(dev)
+    w = (torch.randn(C, C, generator=g) * C ** -0.5).to(dev)
+    out = torch.empty(rows, C, device=dev)
+    graphs, keep = {}, []
+    for products, planes in ((6, 3), (3, 2), (3, 3), (1, 1), (1, 3)):
+        (img,) = ops.panel_pack([(w, True)], planes=planes)
+        keep.append(img)
+        for _ in range(3):
+            ops.panel_gemm(x, img, C, out=out, products=products)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for _ in range(REPS):
+                ops.panel_gemm(x, img, C, out=out, products=products)
+        graphs[f"products_{products}_image_planes_{planes}"] = gr
+    for gr in graphs.values():
+        for _ in range(3):
+            gr.replay()
+    torch.cuda.synchronize()
+    times = {k: [] for k in graphs}
+    for _ in range(a.blocks):
+        for k, gr in graphs.items():
+            s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(a.inner):
+                gr.replay()
+            t.record()
+            torch.cuda.synchronize()
+            times[k].append(s.elapsed_time(t) * 1e3 / (a.inner * REPS))
+    entry = {"rows": rows, "C": C, "panels": (rows + 31) // 32}
+    base, base_sp = _stat(times["products_6_image_planes_3"])
+    for k, ts in times.items():
+        med, sp = _stat(ts)
+        entry[k] = {"us": round(med, 2), "spread": round(sp, 4), "vs_six_products": round(med / base, 4),
+                    "faster_than_six_products_beyond_spread": bool(med * (1 + sp) < base * (1 - base_sp))}
+    return entry
+
+
+def step_times(method, batch, flavour, seed0, a, dev, variants=MODES, hidden=None):
     import equihgnn_amd
     from equihgnn_amd.batch import bucket_sizes, pad_batch, synth_batch
     from equihgnn_amd.models import MODELS
     from equihgnn_amd.registry import default_args
     from equihgnn_amd.trainer import GraphedTrainStep
     pool = 4
-    ns = default_args(method=method, batch_size=batch)
+    ns = default_args(method=method, batch_size=batch, **({} if hidden is None else {"MLP_hidden": hidden}))
     host = [synth_batch(batch, seed0 + i, flavour) for i in range(pool)]
     torch.manual_seed(0)
     model = MODELS[method](1, ns).to(dev).train()
@@ -123,14 +187,14 @@ def step_times(method, batch, flavour, seed0, a, dev):
         step()
     while getattr(tr, "calibrating", False):          # the trainer settles the form of its index build under "highest"
         step()
-    for mode in MODES:                                # each mode's capture and warm-up
-        equihgnn_amd.set_float32_matmul_precision(mode)
+    for mode in variants:                             # each mode's capture and warm-up
+        _set_mode(mode)
         for _ in range(1 + a.warmup):
             step()
-    times = {m: [] for m in MODES}
+    times = {m: [] for m in variants}
     for _ in range(a.blocks):
-        for mode in MODES:
-            equihgnn_amd.set_float32_matmul_precision(mode)
+        for mode in variants:
+            _set_mode(mode)
             step()                                    # (the first step after a switch is not timed)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -152,6 +216,39 @@ def step_times(method, batch, flavour, seed0, a, dev):
     return out
 
 
+def main_panels(a, dev):
+    variants = tuple(v for v in a.variants.split(",") if v)
+    if variants[0] != "highest":
+        raise SystemExit("--variants must start with highest (the ratios' base)")
+    result = {"bench": "panel_precision", "device": torch.cuda.get_device_name(0),
+              "timing": f"product: hipGraphs of {REPS} launches, {a.blocks} interleaved blocks of {a.inner} replays between device events; "
+                        f"steps: {a.blocks} interleaved blocks of {a.steps} replayed steps on a host clock; median block, "
+                        "spread = (max - min) / median",
+              "variants": "mode[+panels]: set_float32_matmul_precision(mode, panels=...); without +panels the panel kernels keep six products",
+              "steps": {}}
+    if a.full_images:
+        from equihgnn_amd.ops import panel
+        panel.FULL_IMAGES = True
+        result["images"] = "three planes in every mode (--full-images)"
+    if os.environ.get("EQH_LIB_PATH"):
+        result["library"] = os.path.basename(os.environ["EQH_LIB_PATH"])
+    if not a.skip_products:
+        for rows in (int(r) for r in a.rows.split(",")):
+            result[f"panel_product_{rows}_256_256"] = panel_product_times(a, dev, rows=rows)
+    if not a.skip_steps:
+        result["steps"]["egnn_equihnns_b256_h256"] = step_times("egnn_equihnns", 256, "qm9", 1000, a, dev, variants, hidden=256)
+        result["steps"]["mhnnm_b256_h256"] = step_times("mhnnm", 256, "qm9", 2000, a, dev, variants, hidden=256)
+    for item in a.merge:
+        name, _, path = item.rpartition("=")
+        with open(path) as f:
+            result[name or "other_build"] = json.loads(f.readline())
+    line = json.dumps(result)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=7)
@@ -159,11 +256,21 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-steps", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "matmul_precision_bench.json"))
+    ap.add_argument("--panels", action="store_true", help="time the panel kernels' modes instead (see the module docstring)")
+    ap.add_argument("--variants", default="highest,medium,high+panels,medium+panels")
+    ap.add_argument("--skip-products", action="store_true")
+    ap.add_argument("--rows", default="4864", help="row counts of the lone panel product (--panels)")
+    ap.add_argument("--full-images", action="store_true", help="the operators pack three-plane images in every mode (--panels)")
+    ap.add_argument("--merge", action="append", default=[], metavar="[NAME=]FILE")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "panel_precision_bench.json" if a.panels else "matmul_precision_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_matmul_precision: no GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
+    if a.panels:
+        return main_panels(a, dev)
     result = {"bench": "matmul_precision", "device": torch.cuda.get_device_name(0),
               "timing": f"products: hipGraphs of {REPS} launches, {a.blocks} interleaved blocks of {a.inner} replays between device events; "
                         f"steps: {a.blocks} interleaved blocks of {a.steps} replayed steps on a host clock; median block, "
