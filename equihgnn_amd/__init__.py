@@ -2,7 +2,7 @@
 import os
 
 from .precision import (get_float32_matmul_precision, get_float32_matmul_precision_panels,  # noqa: F401
-                        set_float32_matmul_precision)
+                        get_float32_matmul_precision_wgrads, set_float32_matmul_precision)
 
 
 def enable_tuned_gemms(tuning: bool = False) -> bool:

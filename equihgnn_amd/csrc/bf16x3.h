@@ -23,4 +23,23 @@ __device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& p0, uin
     p2 = __builtin_amdgcn_perm(fbits(s1), fbits(s0), 0x07060302u);
 }
 
+// The same split cut short, for kernels that split in registers and read fewer planes (the reduced matmul precision modes of the
+// batched weight gradients): only the planes a mode reads are formed.  Plane for plane the bits of split_pair.
+// (x0, x1) -> their first two planes
+__device__ __forceinline__ void split_pair2(float x0, float x1, uint32_t& p0, uint32_t& p1) {
+#ifdef GX_ABLATE_SPLIT
+    p0 = fbits(x0); p1 = fbits(x1);
+    return;
+#endif
+    const uint32_t u0 = fbits(x0), u1 = fbits(x1);
+    p0 = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
+    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
+    p1 = __builtin_amdgcn_perm(fbits(r1), fbits(r0), 0x07060302u);
+}
+
+// (x0, x1) -> plane 0 alone: a truncation, the two high halves packed into one register (one instruction per pair)
+__device__ __forceinline__ uint32_t split_pair1(float x0, float x1) {
+    return __builtin_amdgcn_perm(fbits(x1), fbits(x0), 0x07060302u);
+}
+
 }  // namespace

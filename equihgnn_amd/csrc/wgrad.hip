@@ -224,6 +224,12 @@ k_wgrad_batch(WgradBatch b, int O, int I, int tiles_i, int tiles, int splits) {
 // A workgroup of eight wavefronts owns a 128 x 128 output tile of one product over one chunk of K: wavefront (kh, qi, qj) computes
 // the 64 x 64 quadrant (qi, qj) over the kh-th half of the chunk (a quadrant's operand rows are shared with its neighbours through
 // L1, so a product's operands cross L2 -> CU twice instead of four times); the two K-halves meet in LDS, one slab per chunk.
+//
+// NP: the bf16 products per fp32 product (hg_wgrad_batch_bf16's `products`, the matmul precision modes), a compile-time parameter
+// of both kernels; P = wx_planes(NP) planes per operand.  6: the above.  3 ("high"): planes 0 and 1, the terms a0 b1, a1 b0, a0 b0.
+// 1 ("medium"): plane 0, a0 b0 -- the split is one v_perm per value pair.  The terms a_i b_j with i + j < P, smallest first into the
+// one accumulator, as hg_gemm_bf16_batch and the panel kernels; only the planes read are formed (split_pair2 / split_pair1).  Loads,
+// the register ring, tiles, the split of K, the slabs and their reduction are the same for every NP.
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr int WX_THREADS = 512;
 
@@ -266,8 +272,43 @@ __device__ __forceinline__ void wx_split(const float (&v)[8], bf16x8 (&p)[3]) {
     p[2] = __builtin_bit_cast(bf16x8, p2);
 }
 
+__device__ __forceinline__ void wx_split(const float (&v)[8], bf16x8 (&p)[2]) {      // two planes ("high")
+    uint4 p0, p1;
+    split_pair2(v[0], v[1], p0.x, p1.x);
+    split_pair2(v[2], v[3], p0.y, p1.y);
+    split_pair2(v[4], v[5], p0.z, p1.z);
+    split_pair2(v[6], v[7], p0.w, p1.w);
+    p[0] = __builtin_bit_cast(bf16x8, p0);
+    p[1] = __builtin_bit_cast(bf16x8, p1);
+}
+
+__device__ __forceinline__ void wx_split(const float (&v)[8], bf16x8 (&p)[1]) {      // one plane ("medium")
+    const uint4 p0 = make_uint4(split_pair1(v[0], v[1]), split_pair1(v[2], v[3]), split_pair1(v[4], v[5]), split_pair1(v[6], v[7]));
+    p[0] = __builtin_bit_cast(bf16x8, p0);
+}
+
+constexpr int wx_planes(int np) { return np == 6 ? 3 : np == 3 ? 2 : 1; }
+
+// acc += sum_{i + j < P} A_i B_j, smallest terms first, as gemm_x6.hip: a1 b1, a0 b2, a2 b0 | a0 b1, a1 b0 | a0 b0
+template <int P>
+__device__ __forceinline__ void wx_mac(f32x16& acc, const bf16x8 (&A)[P], const bf16x8 (&B)[P]) {
+    if constexpr (P > 2) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[2], B[0], acc, 0, 0, 0);
+    }
+    if constexpr (P > 1) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[0], acc, 0, 0, 0);
+    }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[0], acc, 0, 0, 0);
+}
+
+template <int NP>
 __global__ void __launch_bounds__(WX_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_wgrad_batch_x3(WgradBatch b, int n_prod, int O, int I, int tiles_i, int tiles, int splits, int use_buf) {
+    static_assert(NP == 6 || NP == 3 || NP == 1, "six, three or one product");
+    constexpr int P = wx_planes(NP);
     __shared__ __attribute__((aligned(16))) float s_acc[4][64 * 64];      // the second K-half's quadrants
     // Work unit = (product, chunk of K, 128 x 128 tile).  The tiles of one (product, chunk) read the same operand rows: they go
     // to ONE XCD (blocks are dealt round-robin over the eight XCDs: b and b + 8 share one -- speed only, nothing depends on
@@ -303,7 +344,7 @@ k_wgrad_batch_x3(WgradBatch b, int n_prod, int O, int I, int tiles_i, int tiles,
         const float* __restrict__ gb = en.x + k_beg * ldx + i0;
         const unsigned la = (unsigned)(8 * kg * ldy + m), lb = (unsigned)(8 * kg * ldx + m);
         auto consume = [&](const WxStage& st) {
-            bf16x8 A[2][3], B[2][3];
+            bf16x8 A[2][P], B[2][P];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 wx_split(st.a[t], A[t]);
@@ -312,15 +353,7 @@ k_wgrad_batch_x3(WgradBatch b, int n_prod, int O, int I, int tiles_i, int tiles,
 #pragma unroll
             for (int ta = 0; ta < 2; ++ta)
 #pragma unroll
-                for (int tb = 0; tb < 2; ++tb) {
-                    // smallest terms first, as gemm_x6.hip: a1 b1, a0 b2, a2 b0, a0 b1, a1 b0, a0 b0
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][1], B[tb][1], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][0], B[tb][2], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][2], B[tb][0], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][0], B[tb][1], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][1], B[tb][0], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][0], B[tb][0], acc[ta][tb], 0, 0, 0);
-                }
+                for (int tb = 0; tb < 2; ++tb) wx_mac<P>(acc[ta][tb], A[ta], B[tb]);
         };
         // whole 16-row steps through a ring of four register stages (three in flight behind the one being multiplied), then
         // the ragged last step with its rows masked
@@ -430,8 +463,11 @@ __device__ __forceinline__ void wxw_load(WxStageW& st, const float* __restrict__
     }
 }
 
+template <int NP>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_wgrad_batch_x3w(WgradBatch b, int n_prod, int O, int I, int tiles_i, int tiles, int splits, int use_buf) {
+    static_assert(NP == 6 || NP == 3 || NP == 1, "six, three or one product");
+    constexpr int P = wx_planes(NP);
     const int groups = n_prod * splits;
     const int xcd = blockIdx.x & 7, j_ = blockIdx.x >> 3;
     const int group = xcd + 8 * (j_ / tiles), tile = j_ % tiles;
@@ -463,22 +499,15 @@ k_wgrad_batch_x3w(WgradBatch b, int n_prod, int O, int I, int tiles_i, int tiles
         const unsigned la = (unsigned)(8 * kg * ldy + m), lb = (unsigned)(8 * kg * ldx + m);
         const bool buf_ok = use_buf && en.K * ldy < ((int64_t)1 << 29) && en.K * ldx < ((int64_t)1 << 29);   // byte offsets below 2 GB
         auto consume = [&](const WxStageW& st) {
-            bf16x8 A[2][3];
+            bf16x8 A[2][P];
             wx_split(st.a[0], A[0]);
             wx_split(st.a[1], A[1]);
 #pragma unroll
             for (int tb = 0; tb < 4; ++tb) {
-                bf16x8 B[3];
+                bf16x8 B[P];
                 wx_split(st.b[tb], B);
 #pragma unroll
-                for (int ta = 0; ta < 2; ++ta) {
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][1], B[1], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][0], B[2], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][2], B[0], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][0], B[1], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][1], B[0], acc[ta][tb], 0, 0, 0);
-                    acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[ta][0], B[0], acc[ta][tb], 0, 0, 0);
-                }
+                for (int ta = 0; ta < 2; ++ta) wx_mac<P>(acc[ta][tb], A[ta], B);
             }
         };
         const int n_full = (int)((k_end - k_beg) / 16), tail = (int)((k_end - k_beg) % 16);
@@ -724,10 +753,29 @@ extern "C" size_t hg_wgrad_batch_workspace_bytes(int32_t count, int32_t O, int32
     return (size_t)count * wg_batch_splits(count, O, I) * (size_t)O * (size_t)I * sizeof(float);
 }
 
-extern "C" int hg_wgrad_batch_f32(int32_t count, const float* const* dy, const float* const* x, const int64_t* K,
-                                  int32_t O, int32_t I, const float* alpha, float* const* dw, const int64_t* ldw,
-                                  int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream_,
-                                  const int64_t* ld_dy, const int64_t* ld_x) {
+// one launch of the 128 x 128 form / of the wide form with NP products
+template <int NP>
+static inline void wg_launch_x3(const WgradBatch& b, int m, int O, int I, int splits, int use_buf, hipStream_t stream) {
+    const int t_i = (I + 127) / 128, t_all = ((O + 127) / 128) * t_i;
+    const int groups = m * splits;
+    hipLaunchKernelGGL(k_wgrad_batch_x3<NP>, dim3(8 * ((groups + 7) / 8) * t_all), dim3(WX_THREADS), 0, stream, b, m, O, I, t_i, t_all,
+                       splits, use_buf);
+}
+template <int NP>
+static inline void wg_launch_x3w(const WgradBatch& b, int m, int O, int I, int splits, int use_buf, hipStream_t stream) {
+    const int t_i = I / 256, t_all = (O / 128) * t_i;
+    const int groups = m * splits;
+    hipLaunchKernelGGL(k_wgrad_batch_x3w<NP>, dim3(8 * ((groups + 7) / 8) * t_all), dim3(256), 0, stream, b, m, O, I, t_i, t_all, splits,
+                       use_buf);
+}
+
+/* products: 6, 3 or 1 bf16 products per fp32 product (the matmul precision modes; anything else is EQH_ERR_ARG before anything is
+ * launched).  The form of the launch, the split of K and the workspace do not depend on it. */
+extern "C" int hg_wgrad_batch_bf16(int32_t count, const float* const* dy, const float* const* x, const int64_t* K,
+                                   int32_t O, int32_t I, const float* alpha, float* const* dw, const int64_t* ldw,
+                                   int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream_,
+                                   const int64_t* ld_dy, const int64_t* ld_x, int32_t products) {
+    if (products != 6 && products != 3 && products != 1) return EQH_ERR_ARG;
     if (count < 0 || O <= 0 || I <= 0) return EQH_ERR_ARG;
     if (count == 0) return EQH_OK;
     if (!dy || !x || !K || !alpha || !dw || !ldw || !workspace) return EQH_ERR_ARG;
@@ -740,8 +788,8 @@ extern "C" int hg_wgrad_batch_f32(int32_t count, const float* const* dy, const f
     float* ws = static_cast<float*>(workspace);
     const int per = wg_per_launch(count);
     static const bool debug = std::getenv("EQH_WGRAD_DEBUG") != nullptr;
-    if (debug) fprintf(stderr, "wgrad batch: %d products of %d x %d, %d per launch, %s tiles, %d chunks of K\n", (int)count, (int)O, (int)I,
-                       per, wg_wide(per, O, I) ? "128 x 256" : "128 x 128", SPLITS);
+    if (debug) fprintf(stderr, "wgrad batch: %d products of %d x %d, %d per launch, %s tiles, %d chunks of K, %d bf16 products each\n",
+                       (int)count, (int)O, (int)I, per, wg_wide(per, O, I) ? "128 x 256" : "128 x 128", SPLITS, (int)products);
     for (int i0 = 0; i0 < count; i0 += per) {
         WgradBatch b;
         const int m = (count - i0 < per) ? count - i0 : per;
@@ -754,22 +802,21 @@ extern "C" int hg_wgrad_batch_f32(int32_t count, const float* const* dy, const f
             b.e[i] = WgradEntry{dy[j], x[j], ws + (size_t)j * SPLITS * slab_elems, K[j], ldy, ldx, alpha[j], 0};
         }
         // round 5: the bf16 x 3 kernel (128 x 128 workgroup tiles); EQH_WGRAD_F32=1 keeps the fp32-MFMA kernel for same-box A/B runs
+        // (with six products only: that kernel has no reduced form, so a reduced mode ignores the variable)
         static const bool use_f32 = [] { const char* e = std::getenv("EQH_WGRAD_F32"); return e && e[0] == '1'; }();
         // (EQH_WGRAD_GLOBAL=1: 64-bit global loads instead of buffer loads, for same-box A/B runs)
         static const int use_buf = [] { const char* e = std::getenv("EQH_WGRAD_GLOBAL"); return (e && e[0] == '1') ? 0 : 1; }();
-        if (use_f32) {
+        if (use_f32 && products == 6) {
             hipLaunchKernelGGL(k_wgrad_batch, dim3(tiles * SPLITS, m), dim3(THREADS), 0, stream, b, (int)O, (int)I, tiles_i,
                                tiles, SPLITS);
         } else if (wg_wide(per, O, I)) {
-            const int t_i = I / 256, t_all = (O / 128) * t_i;
-            const int groups = m * SPLITS;
-            hipLaunchKernelGGL(k_wgrad_batch_x3w, dim3(8 * ((groups + 7) / 8) * t_all), dim3(256), 0, stream, b, m, (int)O, (int)I,
-                               t_i, t_all, SPLITS, use_buf);
+            if (products == 6) wg_launch_x3w<6>(b, m, O, I, SPLITS, use_buf, stream);
+            else if (products == 3) wg_launch_x3w<3>(b, m, O, I, SPLITS, use_buf, stream);
+            else wg_launch_x3w<1>(b, m, O, I, SPLITS, use_buf, stream);
         } else {
-            const int t_i = (I + 127) / 128, t_all = ((O + 127) / 128) * t_i;
-            const int groups = m * SPLITS;
-            hipLaunchKernelGGL(k_wgrad_batch_x3, dim3(8 * ((groups + 7) / 8) * t_all), dim3(WX_THREADS), 0, stream, b, m, (int)O,
-                               (int)I, t_i, t_all, SPLITS, use_buf);
+            if (products == 6) wg_launch_x3<6>(b, m, O, I, SPLITS, use_buf, stream);
+            else if (products == 3) wg_launch_x3<3>(b, m, O, I, SPLITS, use_buf, stream);
+            else wg_launch_x3<1>(b, m, O, I, SPLITS, use_buf, stream);
         }
         EQH_CHECK_LAUNCH();
     }
@@ -783,4 +830,11 @@ extern "C" int hg_wgrad_batch_f32(int32_t count, const float* const* dy, const f
         j = j1;
     }
     return EQH_OK;
+}
+
+extern "C" int hg_wgrad_batch_f32(int32_t count, const float* const* dy, const float* const* x, const int64_t* K,
+                                  int32_t O, int32_t I, const float* alpha, float* const* dw, const int64_t* ldw,
+                                  int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream_,
+                                  const int64_t* ld_dy, const int64_t* ld_x) {
+    return hg_wgrad_batch_bf16(count, dy, x, K, O, I, alpha, dw, ldw, accumulate, workspace, workspace_bytes, stream_, ld_dy, ld_x, 6);
 }

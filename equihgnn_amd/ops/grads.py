@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from .. import hip
+from .. import hip, precision
 from ._base import (_DEFER, _f32c, _ptr, _rows_ld, _stream, _workspace)
 from .products import (GemmProblem, USE_X6, X6_DEEP_ROWS, X6_WGRAD_ROWS, gemm, gemm_batch, gemm_out_ok, gemm_supported)
 
@@ -105,8 +105,10 @@ def defer_begin(device, scratch=None):
 
 
 def wgrad_batch(entries):
-    """hg_wgrad_batch_f32: ``entries`` = [(dy [K,O], x [K,I], alpha, into [O,I] view)], all of one O x I;
-    every product is ADDED to its destination, products with the same destination in list order."""
+    """hg_wgrad_batch_bf16: ``entries`` = [(dy [K,O], x [K,I], alpha, into [O,I] view)], all of one O x I;
+    every product is ADDED to its destination, products with the same destination in list order.  The product count is
+    precision.wgrad_products() at the time of the call (defer_flush for a deferred step): 6 unless
+    set_float32_matmul_precision(mode, wgrads=True) is in force."""
     if not entries:
         return
     O, I = entries[0][3].shape
@@ -124,11 +126,12 @@ def wgrad_batch(entries):
     ws_bytes = L.hg_wgrad_batch_workspace_bytes(n, O, I)
     ws = _workspace(ws_bytes, dev)
     _DEFER["keep"].extend(dys + xs)
-    hip.check(L.hg_wgrad_batch_f32(n, vp(*[t.data_ptr() for t in dys]), vp(*[t.data_ptr() for t in xs]),
-                                   i64(*[t.shape[0] for t in dys]), O, I, f32(*[float(en[2]) for en in flat]),
-                                   vp(*[en[3].data_ptr() for en in flat]), i64(*[en[3].stride(0) for en in flat]), 1,
-                                   _ptr(ws), ws_bytes, _stream(dev), i64(*[ld for _, ld in dl]), i64(*[ld for _, ld in xl])),
-              "hg_wgrad_batch_f32")
+    hip.check(L.hg_wgrad_batch_bf16(n, vp(*[t.data_ptr() for t in dys]), vp(*[t.data_ptr() for t in xs]),
+                                    i64(*[t.shape[0] for t in dys]), O, I, f32(*[float(en[2]) for en in flat]),
+                                    vp(*[en[3].data_ptr() for en in flat]), i64(*[en[3].stride(0) for en in flat]), 1,
+                                    _ptr(ws), ws_bytes, _stream(dev), i64(*[ld for _, ld in dl]), i64(*[ld for _, ld in xl]),
+                                    precision.wgrad_products()),
+              "hg_wgrad_batch_bf16")
 
 
 def colsum_batch(entries):

@@ -124,8 +124,8 @@ int hg_gemm_x6_batch(int32_t n_problems, const HgGemmProblem* problems, int32_t 
  * batching, transposition and bitwise reproducibility as above.  A pre-split image (b_packed) holds three planes and goes with
  * products == 6 only: EQH_ERR_ARG otherwise.  hg_gemm_x6_choose_tile and hg_gemm_x6_workspace_bytes hold for every mode: the
  * split-K plan and the tile do not depend on `products`.  Not covered here: the panel kernels take a product count of their own
- * (below: `products` / `planes` of their entry points); the EGNN edge kernel's second Linear and the batched weight-gradient
- * kernels stay at fp32 grade under every mode. */
+ * (below: `products` / `planes` of their entry points), and so do the batched weight gradients (hg_wgrad_batch_bf16); the EGNN
+ * edge kernel's second Linear, hg_wgrad_f32 and hg_wgrad_skinny_f32 stay at fp32 grade under every mode. */
 int hg_gemm_bf16_batch(int32_t n_problems, const HgGemmProblem* problems, int32_t tile, int32_t products, void* workspace,
                        size_t workspace_bytes, void* stream);
 
@@ -979,6 +979,20 @@ int hg_wgrad_batch_f32(int32_t count, const float* const* dy, const float* const
                        int32_t I, const float* alpha, float* const* dw, const int64_t* ldw, int32_t accumulate,
                        void* workspace, size_t workspace_bytes, void* stream,
                        const int64_t* ld_dy, const int64_t* ld_x);
+/* The same launch with `products` bf16 products per fp32 product (the matmul precision modes, as hg_gemm_bf16_batch): both
+ * operands are split into P bf16 planes in registers and the terms dy_i^T x_j with i + j < P are summed, smallest first, into
+ * the one fp32 accumulator.
+ *   6 (P = 3): what hg_wgrad_batch_f32 computes, bit for bit (that entry point is this one with 6);
+ *   3 (P = 2, "high"):   dy0 x1, dy1 x0, dy0 x0;
+ *   1 (P = 1, "medium"): dy0 x0 (operands truncated to bf16).
+ * Any other value: EQH_ERR_ARG, nothing launched.  The choice between the 128 x 128 and the 128 x 256 form, the chunks of K, the
+ * slabs, their fixed-order reduction and hg_wgrad_batch_workspace_bytes do not depend on `products`.  EQH_WGRAD_F32=1 (the
+ * fp32-MFMA kernel, for same-box A/B runs) holds with six products only: that kernel has no reduced form, so with 3 or 1 the
+ * variable is ignored. */
+int hg_wgrad_batch_bf16(int32_t count, const float* const* dy, const float* const* x, const int64_t* K, int32_t O,
+                        int32_t I, const float* alpha, float* const* dw, const int64_t* ldw, int32_t accumulate,
+                        void* workspace, size_t workspace_bytes, void* stream,
+                        const int64_t* ld_dy, const int64_t* ld_x, int32_t products);
 size_t hg_colsum_workspace_bytes(int64_t R, int32_t C);
 int hg_colsum_f32(const float* x, const int32_t* rowptr, int32_t weight_mode, float scale, int64_t R, int32_t C,
                   int32_t accumulate, float* out, void* workspace, size_t workspace_bytes, void* stream);

@@ -28,6 +28,17 @@ in every mode (the A/B of the reduced-plane images at step level); or a run agai
 
     python tools/bench_matmul_precision.py --panels [--variants highest,medium] [--rows 4864,16384] [--skip-products]
                                            [--full-images] [--merge [NAME=]FILE]
+
+``--wgrads`` times what ``set_float32_matmul_precision(mode, wgrads=True)`` gives (default output
+profiles/wgrad_precision_bench.json), again in one process on replayed graphs: the lone batched weight-gradient launch
+(ops.wgrad_batch between defer_begin and defer_flush: the launch and its one slab reduction) at the two shapes of the BASELINE
+batch -- 21 products of [4736 x 256]^T [4736 x 256], which take the 128 x 128 form, and 30, which take the 128 x 256 form -- with
+6 / 3 / 1 products; and the replayed training step of ``egnn_equihnns`` and ``mhnnm`` (batch 256, hidden 256) under
+highest / high / medium with ``panels=True`` alone and with ``panels=True, wgrads=True`` (``--variants`` replaces the list; the
+first is the ratios' base).  ``pairs`` compares each ``mode+panels+wgrads`` with its ``mode+panels`` -- the arithmetic of the
+commit before the flag -- beyond both spreads; ``--merge`` adds that commit's own build timed by its own copy of this tool.
+
+    python tools/bench_matmul_precision.py --wgrads [--variants ...] [--skip-products] [--skip-steps] [--merge [NAME=]FILE]
 """
 from __future__ import annotations
 
@@ -111,11 +122,11 @@ def gemm_times(a, dev):
 
 def _set_mode(variant):
     import equihgnn_amd
-    mode, _, flag = variant.partition("+")
-    if flag == "panels":
-        equihgnn_amd.set_float32_matmul_precision(mode, panels=True)
-    else:
-        equihgnn_amd.set_float32_matmul_precision(mode)
+    mode, *flags = variant.split("+")
+    unknown = set(flags) - {"panels", "wgrads"}
+    if unknown:
+        raise SystemExit(f"unknown flag(s) {sorted(unknown)} in variant {variant!r}")
+    equihgnn_amd.set_float32_matmul_precision(mode, **{f: True for f in flags})
 
 
 def panel_product_times(a, dev, rows=4864, C=256):
@@ -204,7 +215,7 @@ def step_times(method, batch, flavour, seed0, a, dev, variants=MODES, hidden=Non
             times[mode].append((time.perf_counter() - t0) / a.steps * 1e3)
     equihgnn_amd.set_float32_matmul_precision("highest")
     out = {"molecules": batch, "flavour": flavour, "hidden": ns.MLP_hidden, "graphs": len(tr.slots)}
-    base, base_sp = _stat(times["highest"])
+    base, base_sp = _stat(times["highest" if "highest" in times else variants[0]])
     for mode, ts in times.items():
         med, sp = _stat(ts)
         out[mode] = {"ms": round(med, 4), "spread": round(sp, 4), "vs_highest": round(med / base, 4),
@@ -214,6 +225,98 @@ def step_times(method, batch, flavour, seed0, a, dev, variants=MODES, hidden=Non
     gc.collect()
     torch.cuda.empty_cache()
     return out
+
+
+def wgrad_launch_times(a, dev, count, K=4736, C=256):
+    """`count` products of [K x C]^T [K x C] in one batched launch (+ its one deferred slab reduction) under 6 / 3 / 1 products:
+    hipGraphs of REPS launches, interleaved blocks between device events"""
+    import equihgnn_amd
+    from equihgnn_amd import hip, ops
+    g = torch.Generator().manual_seed(0)
+    dys = [torch.randn(K, C, generator=g).to(dev) for _ in range(count)]
+    xs = [torch.randn(K, C, generator=g).to(dev) for _ in range(count)]
+    outs = [torch.zeros(C, C, device=dev) for _ in range(count)]
+    entries = [(dy, x, 1e-3, o) for dy, x, o in zip(dys, xs, outs)]
+
+    def launch():
+        ops.defer_begin(dev)
+        ops.wgrad_batch(entries)
+        ops.defer_flush(dev)
+
+    graphs = {}
+    for mode in MODES:
+        equihgnn_amd.set_float32_matmul_precision(mode, wgrads=True)
+        for _ in range(3):
+            launch()
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for _ in range(REPS):
+                launch()
+        graphs[mode] = gr
+    equihgnn_amd.set_float32_matmul_precision("highest")
+    for gr in graphs.values():
+        for _ in range(3):
+            gr.replay()
+    torch.cuda.synchronize()
+    times = {k: [] for k in graphs}
+    for _ in range(a.blocks):
+        for k, gr in graphs.items():
+            s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(a.inner):
+                gr.replay()
+            t.record()
+            torch.cuda.synchronize()
+            times[k].append(s.elapsed_time(t) * 1e3 / (a.inner * REPS))
+    ws = int(hip.lib().hg_wgrad_batch_workspace_bytes(count, C, C))
+    entry = {"count": count, "K": K, "O": C, "I": C, "chunks_of_K": ws // (count * C * C * 4),
+             "form_by_the_dispatch_rule": "128 x 256" if C % 256 == 0 and (C // 128) * (C // 256) * min(count, 64) * 5 >= 256 else "128 x 128"}
+    base, base_sp = _stat(times["highest"])
+    for k, ts in times.items():
+        med, sp = _stat(ts)
+        entry[k] = {"us": round(med, 2), "spread": round(sp, 4), "vs_highest": round(med / base, 4),
+                    "tflops_fp32_equivalent": round(2.0 * count * K * C * C / med / 1e6, 1),
+                    "faster_than_highest_beyond_spread": bool(med * (1 + sp) < base * (1 - base_sp))}
+    del graphs, dys, xs, outs, entries
+    gc.collect()
+    torch.cuda.empty_cache()
+    return entry
+
+
+def main_wgrads(a, dev):
+    variants = tuple(v for v in a.variants.split(",") if v)
+    result = {"bench": "wgrad_precision", "device": torch.cuda.get_device_name(0),
+              "timing": f"launch: hipGraphs of {REPS} x (batched launch + its slab reduction), {a.blocks} interleaved blocks of {a.inner} "
+                        f"replays between device events; steps: {a.blocks} interleaved blocks of {a.steps} replayed steps on a host "
+                        "clock; median block, spread = (max - min) / median",
+              "variants": "mode[+panels][+wgrads]: set_float32_matmul_precision(mode, panels=..., wgrads=...); without +wgrads the "
+                          "batched weight gradients keep six products (the arithmetic of the commit before the flag)",
+              "steps": {}}
+    if not a.skip_products:
+        result["wgrad_batch_21_x_4736_256_256"] = wgrad_launch_times(a, dev, 21)
+        result["wgrad_batch_30_x_4736_256_256"] = wgrad_launch_times(a, dev, 30)
+    if not a.skip_steps:
+        result["steps"]["egnn_equihnns_b256_h256"] = step_times("egnn_equihnns", 256, "qm9", 1000, a, dev, variants, hidden=256)
+        result["steps"]["mhnnm_b256_h256"] = step_times("mhnnm", 256, "qm9", 2000, a, dev, variants, hidden=256)
+        pairs = {}
+        for name, e in result["steps"].items():
+            for v in variants:
+                off = v.replace("+wgrads", "")
+                if v != off and off in e:
+                    pairs[f"{name}/{v}"] = {"vs": off, "ratio": round(e[v]["ms"] / e[off]["ms"], 4),
+                                            "faster_beyond_both_spreads": bool(e[v]["ms"] * (1 + e[v]["spread"]) <
+                                                                               e[off]["ms"] * (1 - e[off]["spread"]))}
+        result["pairs"] = pairs
+    for item in a.merge:
+        name, _, path = item.rpartition("=")
+        with open(path) as f:
+            result[name or "other_build"] = json.loads(f.readline())
+    line = json.dumps(result)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
 
 
 def main_panels(a, dev):
@@ -257,18 +360,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-steps", action="store_true")
     ap.add_argument("--panels", action="store_true", help="time the panel kernels' modes instead (see the module docstring)")
-    ap.add_argument("--variants", default="highest,medium,high+panels,medium+panels")
+    ap.add_argument("--wgrads", action="store_true", help="time the batched weight gradients' modes instead (see the module docstring)")
+    ap.add_argument("--variants", default=None)
     ap.add_argument("--skip-products", action="store_true")
     ap.add_argument("--rows", default="4864", help="row counts of the lone panel product (--panels)")
     ap.add_argument("--full-images", action="store_true", help="the operators pack three-plane images in every mode (--panels)")
     ap.add_argument("--merge", action="append", default=[], metavar="[NAME=]FILE")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.variants is None:
+        a.variants = ("highest+panels,high+panels,medium+panels,highest+panels+wgrads,high+panels+wgrads,medium+panels+wgrads"
+                      if a.wgrads else "highest,medium,high+panels,medium+panels")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "panel_precision_bench.json" if a.panels else "matmul_precision_bench.json")
+        a.out = os.path.join(ROOT, "profiles", "wgrad_precision_bench.json" if a.wgrads else
+                             "panel_precision_bench.json" if a.panels else "matmul_precision_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_matmul_precision: no GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
+    if a.wgrads:
+        return main_wgrads(a, dev)
     if a.panels:
         return main_panels(a, dev)
     result = {"bench": "matmul_precision", "device": torch.cuda.get_device_name(0),
