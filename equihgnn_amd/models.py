@@ -4,7 +4,8 @@ Constructor and call contract of main.py:28-34,46-47: ``cls(num_target, args)``;
 ``model(data) -> float32 Tensor[B]`` on ``data.x.device``.  Parameter / buffer names and shapes are
 identical to the reference's, so its checkpoints load with ``strict=True``.
 
-The thirteen hypergraph methods are five front-ends (none, EGNN, Equiformer, FAFormer, ViSNet: the ``_Front`` rows below)
+The fourteen hypergraph methods are six front-ends (none, EGNN, Equiformer, FAFormer, SE(3)-Transformer, ViSNet: the
+``_Front`` rows below)
 times three tails (``_STail``, ``_PairedBase``, ``_MTail``).  A registered class is a subclass of one tail that names its
 front-end; a new method is a new row or a new three-line class, never a new ``forward``.
 """
@@ -23,6 +24,7 @@ from .index import HyperIndex
 from .layers import (EGNN, MLP, AtomEncoder, BondEncoder, MHNNConv, MHNNSConv, batch_norm_rows, head_loss, pool_sum, readout,
                      real_row_mask)
 from .registry import registry
+from .se3_transformer import SE3Transformer
 from .visnet import ViSNet
 
 _ACT = {"Id": nn.Identity, "relu": nn.ReLU, "prelu": nn.PReLU}
@@ -41,6 +43,9 @@ _EQUIFORMER = _Front("equiformer_layer",
                      lambda a: Equiformer(dim=a.MLP_hidden, dim_head=48, num_neighbors=16, valid_radius=5.0))
 _FAFORMER = _Front("fa_former",    # equihnn_fa_former.py:36-49,130-143,210-223
                    lambda a: FAFormer(a.MLP_hidden, n_layers=2, n_heads=2, n_neighbors=16, valid_radius=5.0), masked=True)
+_SE3_TRANSFORMER = _Front("se3_transformer_layer",   # equihnn_se3_transformer.py:37-45
+                         lambda a: SE3Transformer(dim=a.MLP_hidden, heads=2, depth=2, dim_head=32, num_degrees=2, valid_radius=5,
+                                                  num_neighbors=16))
 _VISNET = _Front("visnet_layer",   # equihnn_visnet.py:35-37,114-118,183-185
                  lambda a: ViSNet(hidden_channels=a.MLP_hidden, lmax=2, max_num_neighbors=16), embeds=False)
 
@@ -266,6 +271,13 @@ class FAFormerEquiHNNS(_STail):
     front = _FAFORMER
 
 
+@registry.register_model("se3_transformer_equihnns")
+class SE3TransformerEquiHNNS(_STail):
+    """equihnn_se3_transformer.py:12-91: AtomEncoder -> SE3Transformer (once, degree-0 output) -> shared MHNNSConv x L -> pool
+    -> head."""
+    front = _SE3_TRANSFORMER
+
+
 @registry.register_model("visnet_equihnns")
 class VisNetEquiHNNS(_STail):
     """equihnn_visnet.py:92-158: ViSNet (once) -> shared MHNNSConv x L -> pool -> head."""
@@ -329,4 +341,4 @@ class VisNetEquiHNNM(_MTail):
 
 from .baseline_2d import GNN_2D  # noqa: E402, F401  (registers gin / gcn; constructed as GNN_2D(1, gnn_type=...))
 
-MODELS = dict(registry.mapping["model_name_mapping"])   # the thirteen above plus gin / gcn
+MODELS = dict(registry.mapping["model_name_mapping"])   # the fourteen above plus gin / gcn

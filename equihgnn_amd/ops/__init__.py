@@ -16,6 +16,7 @@ One module per subsystem; everything is re-exported here, so cal
   egnn     EGNN edge kernels, feature node, weight packing
   readout  pooled readout head + MSE in one launch, paired node / hyperedge pool
   se3      Equiformer: row GEMMs, radial trunk, attention pooling, RMS norm, edge geometry
+  se3t     SE(3)-Transformer: edge basis, re-associated radial contraction, 17-slot attention, NormSE3
   gnn2d    2-D baselines: graph index (edge CSRs, bond codes), GIN / GCN edge messages, mean pool
   frames   FAFormer: frame-averaged SwiGLU pieces, edge hidden layer, row dots, gates, attention sums, eigh3
   visnet   ViSNet: per-molecule radius graph and slot geometry, neighbour / edge embedding, ViS_MP message and edge update
@@ -76,6 +77,9 @@ from .se3 import (  # noqa: F401
     _RowGemm, _RowGemm2, _RadialWeightLayout, radial_weight_layout, _AttnPool, attn_pool_supported, attn_pool,
     _RmsNormRows, rms_norm_rows, _RadialTrunk, radial_trunk_supported, radial_trunk, rowgemm, rowgemm2, rowgemm_bias_supported,
     edge_geometry, _RowOuter, row_outer, _PooledRadial, pooled_radial, _Pool3, pool3,
+)
+from .se3t import (  # noqa: F401
+    SE3T_PAIRS, _Se3tPair, _Se3tAttn, _Se3tNorm, se3t_edge_basis, se3t_pair, se3t_attn, se3t_norm,
 )
 from .frames import (  # noqa: F401
     _dropout_seed, _SwigluDropout, _DropoutMean, _FramePre, _FrameHidden, _EdgeHidden, edge_hidden, _RowDot,

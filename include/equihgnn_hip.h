@@ -1098,6 +1098,56 @@ int vis_edge_update_bwd(const float* wt, const float* ws, const float* fr, const
                         const int32_t* cnt, const int32_t* src_start, const int32_t* src_cnt, const int32_t* src_eid,
                         const float* ddf, int64_t N, int32_t C, float* dwt, float* dws, float* dfr, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SE(3)-Transformer front-end (se3_transformer_layer.py at heads 2, dim_head 32, degrees 0 and 1, 16 neighbours, radius 5;
+ * csrc/se3t.hip).  Features are component-major, [*, m, C]; E = N * K edges, edge e = n * K + s is slot s of receiver n.
+ *
+ * se3t_edge_basis: per edge, from pos [N,3] and the self-excluded neighbour table nbr [N,K] (K <= 16):
+ *   dist [E] true distance, maskf [E] 1.0 where dist <= radius, meanw [E] = maskf / max(count, 1) (the weights of
+ *   se3_transformer/utils.py::masked_mean), basis [E,34] = b00 [1] | b01 [mo=3] | b10 [mi=3] | b11 [mo=3][mi=3][f=3]:
+ *   K_J = Y_J(r_hat) Q_J^T of se3_transformer/basis.py:223-245 with rel = pos[n] - pos[nbr].
+ *   qtab [100]: Q_0(0,0) [1] | Q_1(0,1) [3x3] | Q_1(1,0) [3x3] | Q_0(1,1) [9] | Q_1(1,1) [9x3] | Q_2(1,1) [9x5], row-major.
+ *   No gradient.
+ *
+ * se3t_pair_fwd: one PairwiseConv with its radial contraction re-associated.  h [E,128] radial trunk; G [N,Q,128,O] and
+ *   GB [N,Q,O] the SENDER's node-level products with the last Linear's weight and bias (Q = mi * F + f); coef + e * cstride
+ *   the edge's [MO,Q] basis block; rowptr [N+1] / perm [E] the transposed neighbour CSR (edges grouped by sender).
+ *     out_e[mo, o] = sum_q coef_e[mo, q] (sum_c h_e[c] G_j[q, c, o] + GB_j[q, o])
+ *   meanw == NULL: out [E,MO,O] (accumulate must be 0).  meanw [E]: out [N,MO,O] = sum_s meanw[n,s] out_(n,s), overwritten or
+ *   added to; the per-edge values pass through `workspace` (se3t_pair_fwd_workspace_bytes).  MO in {1,3}, Q in {1,3,9},
+ *   O a multiple of 16.
+ * se3t_pair_bwd: dout as out ([E,MO,O], or [N,MO,O] with meanw) -> dh [E,128], dG [N,Q,128,O], dGB [N,Q,O], every entry
+ *   written (zeros for a node that is nobody's neighbour).  No gradient for coef.
+ *
+ * se3t_attn_fwd / _bwd: one degree (M = 1 or 3) of AttentionSE3 with 2 heads of 32 channels: q, kself, vself [N,M,64],
+ *   kedge, vedge [E,M,64]; logit_s = scale * sum_(d in head, m) q k_s over slot 0 (self, always valid) and the K neighbour
+ *   slots, masked slots (maskf == 0) filled with -FLT_MAX, softmax, out [N,M,64] = sum_s attn_s v_s.  logits [N,2,K+1] is
+ *   saved; the backward recomputes the softmax from it.
+ *
+ * se3t_norm_fwd / _bwd: NormSE3 on x [R,M,C]: out = GELU(t scale_c) x / t, t = max(|x|_m, eps); the clamp's gradient is
+ *   zero below eps.  dscale [C] is overwritten (per-workgroup slabs in `workspace`, fixed-order reduction).
+ * ------------------------------------------------------------------------------------------- */
+int se3t_edge_basis(const float* pos, const int32_t* nbr, int64_t N, int32_t K, float radius, const float* qtab,
+                    float* dist, float* maskf, float* meanw, float* basis, void* stream);
+size_t se3t_pair_fwd_workspace_bytes(int64_t E, int32_t MO, int32_t O, int32_t pooled);
+int se3t_pair_fwd(const float* h, const float* G, const float* GB, const float* coef, int32_t cstride,
+                  const int32_t* rowptr, const int32_t* perm, int64_t N, int64_t E, int32_t MO, int32_t Q, int32_t O,
+                  const float* meanw, int32_t K, float* out, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                  void* stream);
+int se3t_pair_bwd(const float* h, const float* G, const float* coef, int32_t cstride, const int32_t* rowptr,
+                  const int32_t* perm, int64_t N, int64_t E, int32_t MO, int32_t Q, int32_t O, const float* dout,
+                  const float* meanw, int32_t K, float* dh, float* dG, float* dGB, void* stream);
+int se3t_attn_fwd(const float* q, const float* kself, const float* kedge, const float* vself, const float* vedge,
+                  const float* maskf, int64_t N, int32_t K, int32_t M, float scale, float* out, float* logits,
+                  void* stream);
+int se3t_attn_bwd(const float* q, const float* kself, const float* kedge, const float* vself, const float* vedge,
+                  const float* logits, const float* dout, int64_t N, int32_t K, int32_t M, float scale, float* dq,
+                  float* dkself, float* dkedge, float* dvself, float* dvedge, void* stream);
+int se3t_norm_fwd(const float* x, const float* scale, int64_t R, int32_t M, int32_t C, float eps, float* out, void* stream);
+size_t se3t_norm_bwd_workspace_bytes(int64_t R, int32_t C);
+int se3t_norm_bwd(const float* x, const float* scale, const float* dy, int64_t R, int32_t M, int32_t C, float eps, float* dx,
+                  float* dscale, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
