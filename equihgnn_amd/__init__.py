@@ -1,8 +1,9 @@
 """equihgnn_amd: the MI355X-native training hot path of HySonLab/EquiHGNN."""
 import os
 
-from .precision import (get_float32_matmul_precision, get_float32_matmul_precision_panels,  # noqa: F401
-                        get_float32_matmul_precision_wgrads, set_float32_matmul_precision)
+from .precision import (get_float32_matmul_precision, get_float32_matmul_precision_edges,  # noqa: F401
+                        get_float32_matmul_precision_panels, get_float32_matmul_precision_wgrads,
+                        set_float32_matmul_precision)
 
 
 def enable_tuned_gemms(tuning: bool = False) -> bool:

@@ -42,4 +42,33 @@ __device__ __forceinline__ uint32_t split_pair1(float x0, float x1) {
     return __builtin_amdgcn_perm(fbits(x1), fbits(x0), 0x07060302u);
 }
 
+// (x0, x1) -> their first PL planes through the three functions above; the planes past PL are set to zero and fall away
+template <int PL>
+__device__ __forceinline__ void split_pair_n(float x0, float x1, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
+    static_assert(PL >= 1 && PL <= 3, "one, two or three planes");
+    if constexpr (PL == 3) {
+        split_pair(x0, x1, p0, p1, p2);
+    } else if constexpr (PL == 2) {
+        split_pair2(x0, x1, p0, p1);
+        p2 = 0u;
+    } else {
+        p0 = split_pair1(x0, x1);
+        p1 = p2 = 0u;
+    }
+}
+
+// Four values -> their first PL <= 2 planes, each plane as the two registers a K = 16 bf16 MFMA reads per lane (mfma.h, mfma16_bf16)
+struct Planes4 {
+    uint2 p0, p1;   // p1 is zero, and unused, with one plane
+};
+template <int PL>
+__device__ __forceinline__ Planes4 split_quad(float x0, float x1, float x2, float x3) {
+    static_assert(PL == 1 || PL == 2, "one or two planes");
+    Planes4 o;
+    uint32_t none;
+    split_pair_n<PL>(x0, x1, o.p0.x, o.p1.x, none);
+    split_pair_n<PL>(x2, x3, o.p0.y, o.p1.y, none);
+    return o;
+}
+
 }  // namespace

@@ -285,27 +285,33 @@ k_edge_fwd(const float* __restrict__ ab, const float* __restrict__ wd, const flo
 // contiguous quarter of the hidden units in steps of 32; a wavefront's W2 fragments (its k-steps x 3 planes x 16 bytes per lane)
 // are split ONCE at kernel start and stay in registers; B rows / the A row go row-contiguously through a private LDS tile
 // into MFMA operand order, as above (lane (j = lane & 15, kg = lane >> 4) multiplies units 8 kg .. 8 kg + 7 of neighbour j).
+// NP, the bf16 products per fp32 product (the matmul precision modes, egnn_edge_fwd_p's `products`): with 3, s and W2 are split
+// into TWO planes and the terms s1 w0, s0 w1, s0 w0 are summed; with 1, both are truncated to one plane (one v_perm_b32 per value
+// pair instead of the eleven instructions of the exact split) and multiplied once.  W2's image keeps its three-plane stride in every
+// mode -- a reduced mode writes and reads the first planes only -- so the LDS layout and its size do not depend on the mode.
 // ------------------------------------------------------------------------------------------------
+constexpr int edge_planes(int np) { return np == 6 ? 3 : (np == 3 ? 2 : 1); }   // products -> bf16 planes per operand
 
 constexpr int F2_SPLIT = 4;                              // wavefronts per node
 constexpr int F2_LD = 32 + 4;                            // floats per staged row (32 hidden units + pad)
 constexpr int F2_TILE = (KNB + 1) * F2_LD;               // 16 B rows + the A row
 constexpr int F2_MAXSTEPS = 9;                           // k-steps (of 32 units) per wavefront: Hp <= 4 * 9 * 32 = 1152
 
+template <int PL>
 __device__ __forceinline__ void split8(const float (&v)[8], uint4& p0, uint4& p1, uint4& p2) {
-    split_pair(v[0], v[1], p0.x, p1.x, p2.x);
-    split_pair(v[2], v[3], p0.y, p1.y, p2.y);
-    split_pair(v[4], v[5], p0.z, p1.z, p2.z);
-    split_pair(v[6], v[7], p0.w, p1.w, p2.w);
+    split_pair_n<PL>(v[0], v[1], p0.x, p1.x, p2.x);
+    split_pair_n<PL>(v[2], v[3], p0.y, p1.y, p2.y);
+    split_pair_n<PL>(v[4], v[5], p0.z, p1.z, p2.z);
+    split_pair_n<PL>(v[6], v[7], p0.w, p1.w, p2.w);
 }
 
-template <int NS, int THREADS_, bool W2_LDS>
+template <int NS, int THREADS_, bool W2_LDS, int NP>
 __global__ void __launch_bounds__(THREADS_)
 k_edge_fwd_x3(const float* __restrict__ ab, const float* __restrict__ wd, const float* __restrict__ w2,
               const float* __restrict__ b2, const int* __restrict__ nbr, const float* __restrict__ d2,
               float* __restrict__ m, float* __restrict__ pre2, int N, int Hp, int n_items, int remap) {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
-    constexpr int NWAVES = THREADS_ / 64, NODES = NWAVES / F2_SPLIT;
+    constexpr int NWAVES = THREADS_ / 64, NODES = NWAVES / F2_SPLIT, PL = edge_planes(NP);
     const int item = xcd_item((int)blockIdx.x, (int)gridDim.x, n_items, remap);
     if (item < 0) return;
     const int total = Hp >> 5;                            // k-steps of 32 hidden units
@@ -329,7 +335,7 @@ k_edge_fwd_x3(const float* __restrict__ ab, const float* __restrict__ wd, const 
         const float4 x0 = *reinterpret_cast<const float4*>(w2 + r * Hp + k0);
         const float4 x1 = *reinterpret_cast<const float4*>(w2 + r * Hp + k0 + 4);
         v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
-        split8(v, p0, p1, p2);
+        split8<PL>(v, p0, p1, p2);
     };
     uint4 wf[W2_LDS ? 1 : NS][3];
     if constexpr (W2_LDS) {
@@ -337,8 +343,8 @@ k_edge_fwd_x3(const float* __restrict__ ab, const float* __restrict__ wd, const 
             uint4 p0, p1, p2;
             w2_frag(step, p0, p1, p2);
             s_w2[(step * 3 + 0) * 64 + lane] = p0;
-            s_w2[(step * 3 + 1) * 64 + lane] = p1;
-            s_w2[(step * 3 + 2) * 64 + lane] = p2;
+            if constexpr (PL > 1) s_w2[(step * 3 + 1) * 64 + lane] = p1;
+            if constexpr (PL > 2) s_w2[(step * 3 + 2) * 64 + lane] = p2;
         }
     } else {
 #pragma unroll
@@ -428,25 +434,33 @@ k_edge_fwd_x3(const float* __restrict__ ab, const float* __restrict__ wd, const 
                 const f32x2 s45 = silu_fast2(f32x2{c1.x, c1.y} * dd2 + (f32x2{a1.x, a1.y} + f32x2{b1.x, b1.y}));
                 const f32x2 s67 = silu_fast2(f32x2{c1.z, c1.w} * dd2 + (f32x2{a1.z, a1.w} + f32x2{b1.z, b1.w}));
                 uint4 p0_, p1_, p2_;
-                split_pair(s01.x, s01.y, p0_.x, p1_.x, p2_.x);
-                split_pair(s23.x, s23.y, p0_.y, p1_.y, p2_.y);
-                split_pair(s45.x, s45.y, p0_.z, p1_.z, p2_.z);
-                split_pair(s67.x, s67.y, p0_.w, p1_.w, p2_.w);
+                split_pair_n<PL>(s01.x, s01.y, p0_.x, p1_.x, p2_.x);
+                split_pair_n<PL>(s23.x, s23.y, p0_.y, p1_.y, p2_.y);
+                split_pair_n<PL>(s45.x, s45.y, p0_.z, p1_.z, p2_.z);
+                split_pair_n<PL>(s67.x, s67.y, p0_.w, p1_.w, p2_.w);
                 const bf16x8 x0 = __builtin_bit_cast(bf16x8, p0_), x1 = __builtin_bit_cast(bf16x8, p1_), x2 = __builtin_bit_cast(bf16x8, p2_);
-                uint4 q0, q1, q2;
+                uint4 q0, q1 = make_uint4(0u, 0u, 0u, 0u), q2 = q1;
                 if constexpr (W2_LDS) {
                     const uint4* wp = s_w2 + (s_beg + st) * 3 * 64 + lane;
-                    q0 = wp[0]; q1 = wp[64]; q2 = wp[128];
+                    q0 = wp[0];
+                    if constexpr (PL > 1) q1 = wp[64];
+                    if constexpr (PL > 2) q2 = wp[128];
                 } else {
                     q0 = wf[st][0]; q1 = wf[st][1]; q2 = wf[st][2];
                 }
                 const bf16x8 w0 = __builtin_bit_cast(bf16x8, q0), w1 = __builtin_bit_cast(bf16x8, q1), w2p = __builtin_bit_cast(bf16x8, q2);
-                // smallest terms first, as gemm_x6.hip: s1 w1, s0 w2, s2 w0, s0 w1, s1 w0, s0 w0
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w2p, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x2, w0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w0, acc, 0, 0, 0);
+                // smallest terms first, as gemm_x6.hip: s1 w1, s0 w2, s2 w0, s0 w1, s1 w0, s0 w0 (three products: the last three
+                // with s1 w0 in front of s0 w1; one product: the last)
+                if constexpr (NP == 6) {
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w1, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w2p, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x2, w0, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w1, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w0, acc, 0, 0, 0);
+                } else if constexpr (NP == 3) {
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, w0, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w1, acc, 0, 0, 0);
+                }
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, w0, acc, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -489,7 +503,33 @@ k_edge_fwd_x3(const float* __restrict__ ab, const float* __restrict__ wd, const 
 // wavefront all nodes of a 16-node chunk for hidden tiles w, w+4, ...: 17 tiles over 4 wavefronts and
 // 288 workgroups over 256 CUs lost ~45% to quantisation), and the chunk count is chosen so that the
 // whole grid is resident at once (4 workgroups per CU).
+// NP (the matmul precision modes, egnn_edge_bwd_p's `products`): with 6 the three 16-wide products of the main kernels run on the
+// fp32 MFMA as described above.  With 3 / 1 they run on v_mfma_f32_16x16x16_bf16 (mfma.h, mfma16_bf16): every one of them has
+// K = 16, and the float4 a lane already holds -- four consecutive o of dpre2, four consecutive j of its transposed copy, the four W2
+// rows 4q .. 4q+3 of one hidden unit, the SiLU of its four edges -- is exactly its four K values A[r][4q .. 4q+3] / B[4q .. 4q+3][r].
+// Operands are split into two / one bf16 plane in registers (W2 once per workgroup, dpre2 and silu(h) per node or tile) and the terms
+// a1 b0, a0 b1, a0 b0 / a0 b0 are summed into fp32: 4 x {3, 1} matrix instructions where the fp32 form issues 16.  The
+// recomputation of h, SiLU and its derivative, dwd, the row sums and every reduction stay fp32 VALU work in every mode.
 // ------------------------------------------------------------------------------------------------
+// one K = 16 product over the planes of a mode (NP = 3 or 1), smallest terms first
+template <int NP>
+__device__ __forceinline__ f32x4 mfma16_planes(const Planes4& a, const Planes4& b, f32x4 c) {
+    if constexpr (NP == 3) {
+        c = mfma16_bf16(a.p1, b.p0, c);
+        c = mfma16_bf16(a.p0, b.p1, c);
+    }
+    return mfma16_bf16(a.p0, b.p0, c);
+}
+// W2[4q .. 4q+3][k4 + c], c = 0..3, as the B operands of the K = 16 products g_c = dpre2 . W2[:, k4 + c]
+template <int NP>
+__device__ __forceinline__ void w2_planes(const float4& w0, const float4& w1, const float4& w2v, const float4& w3, Planes4& c0,
+                                          Planes4& c1, Planes4& c2, Planes4& c3) {
+    constexpr int PL = edge_planes(NP);
+    c0 = split_quad<PL>(w0.x, w1.x, w2v.x, w3.x);
+    c1 = split_quad<PL>(w0.y, w1.y, w2v.y, w3.y);
+    c2 = split_quad<PL>(w0.z, w1.z, w2v.z, w3.z);
+    c3 = split_quad<PL>(w0.w, w1.w, w2v.w, w3.w);
+}
 constexpr int BW_RESIDENT = 768;  // 256 CUs x 3 workgroups of 4 wavefronts (129..168 VGPRs per lane)
 
 __host__ __device__ inline int bw_chunks(int64_t n_items, int tiles) {
@@ -572,9 +612,11 @@ __device__ __forceinline__ void recv_load(RecvOps& o, const float* __restrict__ 
 }
 
 // One hidden unit column c (of the lane's four) of one node: the four edges g = 0..3 of this lane.
-// Returns sum_g dh, accumulates dwd, and feeds dW2[o][k4 + c] += sum_j dpre2[j][o] * silu(h[j][k4 + c]).
+// Returns sum_g dh, accumulates dwd, and feeds dW2[o][k4 + c] += sum_j dpre2[j][o] * silu(h[j][k4 + c]) (NP = 6: four fp32
+// products over pt; else one K = 16 product of pt's planes ptp with the planes of the four SiLU values).
+template <int NP>
 __device__ __forceinline__ float recv_column(float a, float wdc, const float4& dd, float b0, float b1, float b2,
-                                             float b3, const f32x4& gk, const float4& pt, float& acc_wd,
+                                             float b3, const f32x4& gk, const float4& pt, const Planes4& ptp, float& acc_wd,
                                              f32x4& acc_w) {
     float ds0, ds1, ds2, ds3;
     const float s0 = silu_grad(fmaf(wdc, dd.x, a + b0), &ds0);
@@ -586,13 +628,18 @@ __device__ __forceinline__ float recv_column(float a, float wdc, const float4& d
     acc_wd = fmaf(dh1, dd.y, acc_wd);
     acc_wd = fmaf(dh2, dd.z, acc_wd);
     acc_wd = fmaf(dh3, dd.w, acc_wd);
-    acc_w = mfma16(pt.x, s0, acc_w);
-    acc_w = mfma16(pt.y, s1, acc_w);
-    acc_w = mfma16(pt.z, s2, acc_w);
-    acc_w = mfma16(pt.w, s3, acc_w);
+    if constexpr (NP == 6) {
+        acc_w = mfma16(pt.x, s0, acc_w);
+        acc_w = mfma16(pt.y, s1, acc_w);
+        acc_w = mfma16(pt.z, s2, acc_w);
+        acc_w = mfma16(pt.w, s3, acc_w);
+    } else {
+        acc_w = mfma16_planes<NP>(ptp, split_quad<edge_planes(NP)>(s0, s1, s2, s3), acc_w);
+    }
     return (dh0 + dh1) + (dh2 + dh3);
 }
 
+template <int NP>
 __global__ void __launch_bounds__(THREADS)
 k_edge_bwd_recv(const float* __restrict__ ab, const float* __restrict__ wd, const float* __restrict__ w2,
                 const int* __restrict__ nbr, const float* __restrict__ d2, const float* __restrict__ dpre2,
@@ -615,6 +662,8 @@ k_edge_bwd_recv(const float* __restrict__ ab, const float* __restrict__ wd, cons
     const float4 w2v = *reinterpret_cast<const float4*>(w2 + (4 * q + 2) * Hp + k4);
     const float4 w3 = *reinterpret_cast<const float4*>(w2 + (4 * q + 3) * Hp + k4);
     const float4 wd4 = *reinterpret_cast<const float4*>(wd + k4);
+    Planes4 wp0 = {}, wp1 = {}, wp2 = {}, wp3 = {};   // NP < 6: W2's planes, split once per workgroup
+    if constexpr (NP != 6) w2_planes<NP>(w0, w1, w2v, w3, wp0, wp1, wp2, wp3);
     f32x4 aw0 = {0.f, 0.f, 0.f, 0.f}, aw1 = aw0, aw2 = aw0, aw3 = aw0;  // aw_c[g] = dW2[o = 4q+g][k4 + c]
     float ad0 = 0.f, ad1 = 0.f, ad2 = 0.f, ad3 = 0.f;                   // dwd[k4 + c], this lane's edges
     // software pipeline over this wavefront's nodes n = wave, wave + 4, ...: operands of node n+1 and the
@@ -644,18 +693,28 @@ k_edge_bwd_recv(const float* __restrict__ ab, const float* __restrict__ wd, cons
 #endif
             // gk_c[g] = sum_o dpre2[j = 4q+g][o] * W2[o][k4 + c]
             f32x4 g0 = {0.f, 0.f, 0.f, 0.f}, g1 = g0, g2 = g0, g3 = g0;
-            g0 = mfma16(cur.pa.x, w0.x, g0); g1 = mfma16(cur.pa.x, w0.y, g1);
-            g2 = mfma16(cur.pa.x, w0.z, g2); g3 = mfma16(cur.pa.x, w0.w, g3);
-            g0 = mfma16(cur.pa.y, w1.x, g0); g1 = mfma16(cur.pa.y, w1.y, g1);
-            g2 = mfma16(cur.pa.y, w1.z, g2); g3 = mfma16(cur.pa.y, w1.w, g3);
-            g0 = mfma16(cur.pa.z, w2v.x, g0); g1 = mfma16(cur.pa.z, w2v.y, g1);
-            g2 = mfma16(cur.pa.z, w2v.z, g2); g3 = mfma16(cur.pa.z, w2v.w, g3);
-            g0 = mfma16(cur.pa.w, w3.x, g0); g1 = mfma16(cur.pa.w, w3.y, g1);
-            g2 = mfma16(cur.pa.w, w3.z, g2); g3 = mfma16(cur.pa.w, w3.w, g3);
-            float da0 = recv_column(cur.a.x, wd4.x, cur.dd, cur.b0.x, cur.b1.x, cur.b2.x, cur.b3.x, g0, cur.pt, ad0, aw0);
-            float da1 = recv_column(cur.a.y, wd4.y, cur.dd, cur.b0.y, cur.b1.y, cur.b2.y, cur.b3.y, g1, cur.pt, ad1, aw1);
-            float da2 = recv_column(cur.a.z, wd4.z, cur.dd, cur.b0.z, cur.b1.z, cur.b2.z, cur.b3.z, g2, cur.pt, ad2, aw2);
-            float da3 = recv_column(cur.a.w, wd4.w, cur.dd, cur.b0.w, cur.b1.w, cur.b2.w, cur.b3.w, g3, cur.pt, ad3, aw3);
+            Planes4 ptp = {};   // NP < 6: the planes of pt, the A operand of the four dW2 products of this node
+            if constexpr (NP == 6) {
+                g0 = mfma16(cur.pa.x, w0.x, g0); g1 = mfma16(cur.pa.x, w0.y, g1);
+                g2 = mfma16(cur.pa.x, w0.z, g2); g3 = mfma16(cur.pa.x, w0.w, g3);
+                g0 = mfma16(cur.pa.y, w1.x, g0); g1 = mfma16(cur.pa.y, w1.y, g1);
+                g2 = mfma16(cur.pa.y, w1.z, g2); g3 = mfma16(cur.pa.y, w1.w, g3);
+                g0 = mfma16(cur.pa.z, w2v.x, g0); g1 = mfma16(cur.pa.z, w2v.y, g1);
+                g2 = mfma16(cur.pa.z, w2v.z, g2); g3 = mfma16(cur.pa.z, w2v.w, g3);
+                g0 = mfma16(cur.pa.w, w3.x, g0); g1 = mfma16(cur.pa.w, w3.y, g1);
+                g2 = mfma16(cur.pa.w, w3.z, g2); g3 = mfma16(cur.pa.w, w3.w, g3);
+            } else {
+                // A[r][4q + i] = dpre2[j = r][o = 4q + i] = pa[i];  B[4q + i][r] = W2[4q + i][k4 + c]
+                const Planes4 pap = split_quad<edge_planes(NP)>(cur.pa.x, cur.pa.y, cur.pa.z, cur.pa.w);
+                g0 = mfma16_planes<NP>(pap, wp0, g0); g1 = mfma16_planes<NP>(pap, wp1, g1);
+                g2 = mfma16_planes<NP>(pap, wp2, g2); g3 = mfma16_planes<NP>(pap, wp3, g3);
+                // A[r][4q + i] = dpre2[j = 4q + i][o = r] = pt[i];  B[4q + i][r] = silu(h[j = 4q + i][k4 + c]) (recv_column)
+                ptp = split_quad<edge_planes(NP)>(cur.pt.x, cur.pt.y, cur.pt.z, cur.pt.w);
+            }
+            float da0 = recv_column<NP>(cur.a.x, wd4.x, cur.dd, cur.b0.x, cur.b1.x, cur.b2.x, cur.b3.x, g0, cur.pt, ptp, ad0, aw0);
+            float da1 = recv_column<NP>(cur.a.y, wd4.y, cur.dd, cur.b0.y, cur.b1.y, cur.b2.y, cur.b3.y, g1, cur.pt, ptp, ad1, aw1);
+            float da2 = recv_column<NP>(cur.a.z, wd4.z, cur.dd, cur.b0.z, cur.b1.z, cur.b2.z, cur.b3.z, g2, cur.pt, ptp, ad2, aw2);
+            float da3 = recv_column<NP>(cur.a.w, wd4.w, cur.dd, cur.b0.w, cur.b1.w, cur.b2.w, cur.b3.w, g3, cur.pt, ptp, ad3, aw3);
             da0 += __shfl_xor(da0, 16, 64); da1 += __shfl_xor(da1, 16, 64);
             da2 += __shfl_xor(da2, 16, 64); da3 += __shfl_xor(da3, 16, 64);
             da0 += __shfl_xor(da0, 32, 64); da1 += __shfl_xor(da1, 32, 64);
@@ -748,6 +807,7 @@ __device__ __forceinline__ float4 send_row(const float4& wd4, float dd, const fl
     return dh;
 }
 
+template <int NP>
 __global__ void __launch_bounds__(THREADS)
 k_edge_bwd_send(const float* __restrict__ ab, const float* __restrict__ wd, const float* __restrict__ w2,
                 const float* __restrict__ dpre2, const int* __restrict__ t_rowptr, const int4* __restrict__ rec,
@@ -778,6 +838,8 @@ k_edge_bwd_send(const float* __restrict__ ab, const float* __restrict__ wd, cons
     const float4 w2v = *reinterpret_cast<const float4*>(w2 + (4 * q + 2) * Hp + k4);
     const float4 w3 = *reinterpret_cast<const float4*>(w2 + (4 * q + 3) * Hp + k4);
     const float4 wd4 = *reinterpret_cast<const float4*>(wd + k4);
+    Planes4 wp0 = {}, wp1 = {}, wp2 = {}, wp3 = {};   // NP < 6: W2's planes, split once per wavefront
+    if constexpr (NP != 6) w2_planes<NP>(w0, w1, w2v, w3, wp0, wp1, wp2, wp3);
     float* tile = s_tile[wave];
     // end positions of up to 64 consecutive senders live in one VGPR (lane i: sender rp_base + i),
     // read with v_readlane as the walk advances
@@ -810,10 +872,16 @@ k_edge_bwd_send(const float* __restrict__ ab, const float* __restrict__ wd, cons
         }
 #endif
         f32x4 g0 = {0.f, 0.f, 0.f, 0.f}, g1 = g0, g2 = g0, g3 = g0;
-        g0 = mfma16(pa.x, w0.x, g0); g1 = mfma16(pa.x, w0.y, g1); g2 = mfma16(pa.x, w0.z, g2); g3 = mfma16(pa.x, w0.w, g3);
-        g0 = mfma16(pa.y, w1.x, g0); g1 = mfma16(pa.y, w1.y, g1); g2 = mfma16(pa.y, w1.z, g2); g3 = mfma16(pa.y, w1.w, g3);
-        g0 = mfma16(pa.z, w2v.x, g0); g1 = mfma16(pa.z, w2v.y, g1); g2 = mfma16(pa.z, w2v.z, g2); g3 = mfma16(pa.z, w2v.w, g3);
-        g0 = mfma16(pa.w, w3.x, g0); g1 = mfma16(pa.w, w3.y, g1); g2 = mfma16(pa.w, w3.z, g2); g3 = mfma16(pa.w, w3.w, g3);
+        if constexpr (NP == 6) {
+            g0 = mfma16(pa.x, w0.x, g0); g1 = mfma16(pa.x, w0.y, g1); g2 = mfma16(pa.x, w0.z, g2); g3 = mfma16(pa.x, w0.w, g3);
+            g0 = mfma16(pa.y, w1.x, g0); g1 = mfma16(pa.y, w1.y, g1); g2 = mfma16(pa.y, w1.z, g2); g3 = mfma16(pa.y, w1.w, g3);
+            g0 = mfma16(pa.z, w2v.x, g0); g1 = mfma16(pa.z, w2v.y, g1); g2 = mfma16(pa.z, w2v.z, g2); g3 = mfma16(pa.z, w2v.w, g3);
+            g0 = mfma16(pa.w, w3.x, g0); g1 = mfma16(pa.w, w3.y, g1); g2 = mfma16(pa.w, w3.z, g2); g3 = mfma16(pa.w, w3.w, g3);
+        } else {   // (the receiver pass's first product; a padding row's pa is zero in every plane)
+            const Planes4 pap = split_quad<edge_planes(NP)>(pa.x, pa.y, pa.z, pa.w);
+            g0 = mfma16_planes<NP>(pap, wp0, g0); g1 = mfma16_planes<NP>(pap, wp1, g1);
+            g2 = mfma16_planes<NP>(pap, wp2, g2); g3 = mfma16_planes<NP>(pap, wp3, g3);
+        }
         // dh of the four entries whose results land in this lane (MFMA rows 4q + g); gk = 0 on padding rows
         float* trow = tile + 4 * q * SEND_LD + 4 * r;
         *reinterpret_cast<float4*>(trow) = send_row(wd4, cur_ops.dd0, cur_ops.a0, cur_ops.b0, g0[0], g1[0], g2[0], g3[0]);
@@ -863,11 +931,48 @@ int check_common(int64_t N, int Hp) {
     return EQH_OK;
 }
 
+// one launch of the bf16 forward with NP products: 16 wavefronts (four per SIMD, W2's planes in LDS), or 8 with W2 in registers
+template <int NP>
+int fwd_x3_launch(const float* ab, const float* wd, const float* w2, const float* b2, const int32_t* nbr, const float* d2,
+                  int64_t N, int32_t Hp, float* m, float* pre2, hipStream_t stream, int per, bool w8, size_t lds2) {
+    const int threads = w8 ? 512 : 1024;
+    const int items2 = eqh_grid_for(N, threads / 64 / F2_SPLIT, 256);  // one workgroup per CU
+    const int remap = edge_xcd_remap();
+    const int grid2 = xcd_grid(items2, remap);
+    static bool attr2 = false;   // (one per NP)
+#define F2_ATTR(NS_)                                                                                                          \
+    (hipFuncSetAttribute(reinterpret_cast<const void*>(k_edge_fwd_x3<NS_, 1024, true, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                         160 * 1024) == hipSuccess)
+    if (!attr2) {
+        if (!(F2_ATTR(1) && F2_ATTR(2) && F2_ATTR(3) && F2_ATTR(5) && F2_ATTR(9))) return EQH_ERR_LAUNCH;
+        attr2 = true;
+    }
+#undef F2_ATTR
+#define F2_LAUNCH(NS_)                                                                                                         \
+    do {                                                                                                                   \
+        if (w8) hipLaunchKernelGGL((k_edge_fwd_x3<NS_, 512, false, NP>), dim3(grid2), dim3(512), lds2, stream, ab, wd, w2, b2, nbr, d2, m, \
+                                   pre2, (int)N, (int)Hp, items2, remap);                                                  \
+        else hipLaunchKernelGGL((k_edge_fwd_x3<NS_, 1024, true, NP>), dim3(grid2), dim3(1024), lds2, stream, ab, wd, w2, b2, nbr, d2, m, \
+                                pre2, (int)N, (int)Hp, items2, remap);                                                     \
+    } while (0)
+    if (per <= 1) F2_LAUNCH(1);
+    else if (per <= 2) F2_LAUNCH(2);
+    else if (per <= 3) F2_LAUNCH(3);
+    else if (per <= 5) F2_LAUNCH(5);
+    else F2_LAUNCH(9);
+#undef F2_LAUNCH
+    EQH_CHECK_LAUNCH();
+    return EQH_OK;
+}
+
 }  // namespace
 
-extern "C" int egnn_edge_fwd(const float* ab, const float* wd, const float* w2, const float* b2,
-                             const int32_t* nbr, const float* d2, int64_t N, int32_t Hp, float* m,
-                             float* pre2, void* stream_) {
+/* products: 6, 3 or 1 bf16 products per fp32 product (the matmul precision modes; anything else is EQH_ERR_ARG before anything is
+ * looked at).  6 is egnn_edge_fwd.  Where the fp32-MFMA kernel runs (Hp > 1152, EQH_EDGE_F32=1) every count gives its result. */
+extern "C" int egnn_edge_fwd_p(const float* ab, const float* wd, const float* w2, const float* b2,
+                               const int32_t* nbr, const float* d2, int64_t N, int32_t Hp, float* m,
+                               float* pre2, void* stream_, int32_t products) {
+    if (products != 6 && products != 3 && products != 1) return EQH_ERR_ARG;
     int rc = check_common(N, Hp);
     if (rc) return rc;
     if (N == 0) return EQH_OK;
@@ -883,34 +988,10 @@ extern "C" int egnn_edge_fwd(const float* ab, const float* wd, const float* w2, 
         static const bool w8 = [] { const char* e = std::getenv("EQH_EDGE_W8"); return e && e[0] == '1'; }();
         const int threads = w8 ? 512 : 1024;
         const size_t lds2 = ((size_t)Hp + (size_t)(threads / 64) * F2_TILE) * sizeof(float) + (w8 ? 0 : (size_t)(Hp >> 5) * 3 * 64 * 16);
-        const int items2 = eqh_grid_for(N, threads / 64 / F2_SPLIT, 256);  // one workgroup per CU
-        const int remap = edge_xcd_remap();
-        const int grid2 = xcd_grid(items2, remap);
-        static bool attr2 = false;
-#define F2_ATTR(NS_)                                                                                                          \
-        (hipFuncSetAttribute(reinterpret_cast<const void*>(k_edge_fwd_x3<NS_, 1024, true>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                             160 * 1024) == hipSuccess)
-        if (!attr2) {
-            if (!(F2_ATTR(1) && F2_ATTR(2) && F2_ATTR(3) && F2_ATTR(5) && F2_ATTR(9))) return EQH_ERR_LAUNCH;
-            attr2 = true;
-        }
-#undef F2_ATTR
         if (lds2 > 160 * 1024) return EQH_ERR_RANGE;
-#define F2_LAUNCH(NS_)                                                                                                         \
-        do {                                                                                                                   \
-            if (w8) hipLaunchKernelGGL((k_edge_fwd_x3<NS_, 512, false>), dim3(grid2), dim3(512), lds2, stream, ab, wd, w2, b2, nbr, d2, m, \
-                                       pre2, (int)N, (int)Hp, items2, remap);                                                  \
-            else hipLaunchKernelGGL((k_edge_fwd_x3<NS_, 1024, true>), dim3(grid2), dim3(1024), lds2, stream, ab, wd, w2, b2, nbr, d2, m, \
-                                    pre2, (int)N, (int)Hp, items2, remap);                                                     \
-        } while (0)
-        if (per <= 1) F2_LAUNCH(1);
-        else if (per <= 2) F2_LAUNCH(2);
-        else if (per <= 3) F2_LAUNCH(3);
-        else if (per <= 5) F2_LAUNCH(5);
-        else F2_LAUNCH(9);
-#undef F2_LAUNCH
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
+        if (products == 6) return fwd_x3_launch<6>(ab, wd, w2, b2, nbr, d2, N, Hp, m, pre2, stream, per, w8, lds2);
+        if (products == 3) return fwd_x3_launch<3>(ab, wd, w2, b2, nbr, d2, N, Hp, m, pre2, stream, per, w8, lds2);
+        return fwd_x3_launch<1>(ab, wd, w2, b2, nbr, d2, N, Hp, m, pre2, stream, per, w8, lds2);
     }
     const size_t lds_rest = ((size_t)Hp + (size_t)(FWD_THREADS / 64) * FWD_TILE) * sizeof(float);
     const size_t lds_w2 = (size_t)MDIM * lds_row_stride(Hp) * sizeof(float);
@@ -937,6 +1018,12 @@ extern "C" int egnn_edge_fwd(const float* ab, const float* wd, const float* w2, 
     return EQH_OK;
 }
 
+extern "C" int egnn_edge_fwd(const float* ab, const float* wd, const float* w2, const float* b2,
+                             const int32_t* nbr, const float* d2, int64_t N, int32_t Hp, float* m,
+                             float* pre2, void* stream_) {
+    return egnn_edge_fwd_p(ab, wd, w2, b2, nbr, d2, N, Hp, m, pre2, stream_, 6);
+}
+
 static inline int prep_blocks(int64_t N) { return eqh_grid_for(N, WAVES, 2048); }
 
 extern "C" size_t egnn_edge_bwd_workspace_bytes(int64_t N, int32_t Hp) {
@@ -949,12 +1036,15 @@ extern "C" size_t egnn_edge_bwd_workspace_bytes(int64_t N, int32_t Hp) {
             (size_t)(N > 0 ? N : 1) * KNB * 4 + (size_t)prep_blocks(N) * MDIM) * sizeof(float);
 }
 
-extern "C" int egnn_edge_bwd(const float* ab, const float* wd, const float* w2, const int32_t* nbr,
-                             const float* d2, const float* pre2, const float* dm, int64_t dm_ld,
-                             const int32_t* t_rowptr, const int32_t* t_perm, int64_t N, int32_t Hp,
-                             float* dab, float* dwd, float* dw2, float* dpre2, float* db2,
-                             int32_t db2_accumulate, int32_t dw_accumulate, void* workspace, size_t workspace_bytes,
-                             void* stream_) {
+/* products: as egnn_edge_fwd_p; 6 is egnn_edge_bwd.  The workspace is that of egnn_edge_bwd_workspace_bytes for every count (operands
+ * are split in registers). */
+extern "C" int egnn_edge_bwd_p(const float* ab, const float* wd, const float* w2, const int32_t* nbr,
+                               const float* d2, const float* pre2, const float* dm, int64_t dm_ld,
+                               const int32_t* t_rowptr, const int32_t* t_perm, int64_t N, int32_t Hp,
+                               float* dab, float* dwd, float* dw2, float* dpre2, float* db2,
+                               int32_t db2_accumulate, int32_t dw_accumulate, void* workspace, size_t workspace_bytes,
+                               void* stream_, int32_t products) {
+    if (products != 6 && products != 3 && products != 1) return EQH_ERR_ARG;
     int rc = check_common(N, Hp);
     if (rc) return rc;
     if (!dwd || !dw2) return EQH_ERR_ARG;
@@ -992,14 +1082,26 @@ extern "C" int egnn_edge_bwd(const float* ab, const float* wd, const float* w2, 
         if (rc) return rc;
     }
     const int remap = edge_xcd_remap();
-    hipLaunchKernelGGL(k_edge_bwd_recv, dim3(xcd_grid(used * tiles, remap)), dim3(THREADS), 0, stream, ab, wd, w2, nbr, d2, dpre2,
+    const auto recv = products == 6 ? k_edge_bwd_recv<6> : (products == 3 ? k_edge_bwd_recv<3> : k_edge_bwd_recv<1>);
+    const auto send = products == 6 ? k_edge_bwd_send<6> : (products == 3 ? k_edge_bwd_send<3> : k_edge_bwd_send<1>);
+    hipLaunchKernelGGL(recv, dim3(xcd_grid(used * tiles, remap)), dim3(THREADS), 0, stream, ab, wd, w2, nbr, d2, dpre2,
                        dpre2_t, dab, slab_w2, slab_wd, (int)N, (int)Hp, tiles, chunk_items, used * tiles, remap);
     EQH_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_edge_bwd_send, dim3(xcd_grid(used * tiles, remap)), dim3(THREADS), 0, stream, ab, wd, w2, dpre2, t_rowptr,
+    hipLaunchKernelGGL(send, dim3(xcd_grid(used * tiles, remap)), dim3(THREADS), 0, stream, ab, wd, w2, dpre2, t_rowptr,
                        rec, dab, (int)N, (int)Hp, tiles, chunk_items, used * tiles, remap);
     EQH_CHECK_LAUNCH();
     // (dw_accumulate: dw2 / dwd are accumulators -- the packed weights' own, ops.egnn_pack_weights -- and the reduction joins
     // the step's batched one when a deferral window is open)
     return eqh_reduce_slabs3_async(slab_w2, used, (int64_t)(MDIM + 1) * Hp, dw2, dwd, dwd, (int64_t)MDIM * Hp, Hp,
                                    dw_accumulate ? 1 : 0, stream);
+}
+
+extern "C" int egnn_edge_bwd(const float* ab, const float* wd, const float* w2, const int32_t* nbr,
+                             const float* d2, const float* pre2, const float* dm, int64_t dm_ld,
+                             const int32_t* t_rowptr, const int32_t* t_perm, int64_t N, int32_t Hp,
+                             float* dab, float* dwd, float* dw2, float* dpre2, float* db2,
+                             int32_t db2_accumulate, int32_t dw_accumulate, void* workspace, size_t workspace_bytes,
+                             void* stream_) {
+    return egnn_edge_bwd_p(ab, wd, w2, nbr, d2, pre2, dm, dm_ld, t_rowptr, t_perm, N, Hp, dab, dwd, dw2, dpre2, db2,
+                           db2_accumulate, dw_accumulate, workspace, workspace_bytes, stream_, 6);
 }

@@ -8,7 +8,7 @@ import os
 
 import torch
 
-from .. import hip
+from .. import hip, precision
 from ._base import (
     ACC_PARAMS, LINEAR_PARAMS, _DEFER, _acc_target, _f32c, _hand_out, _note_acc, _ptr, _require_gpu, _rows_ld, _stream,
     _workspace, timed)
@@ -21,7 +21,9 @@ from .panel import backward_as_forward
 class _EgnnEdge(torch.autograd.Function):
     """m_i = sum_j silu(W2 silu(A_i + B_j + wd d2_ij) + b2) — the fused EGNN edge update
     (egnn_layer.py:298-310,357-358).  Saves only ``ab`` and the 16x16 second-layer
-    pre-activations; the per-edge hidden activations are recomputed in the backward."""
+    pre-activations; the per-edge hidden activations are recomputed in the backward.  The matrix products run with
+    ``precision.edge_products()`` bf16 terms, read once in the forward: the backward multiplies as its forward did,
+    whatever the mode is by then (the rule of the panel nodes, ``backward_as_forward``)."""
 
     @staticmethod
     def forward(ctx, ab, wd, w2, b2, nbr, d2, csr_t: CSR, b2_param=None, w_refs=None):
@@ -32,10 +34,11 @@ class _EgnnEdge(torch.autograd.Function):
             raise ValueError("egnn_edge: shapes must be ab[N,2Hp] wd[Hp] w2[16,Hp] b2[16] nbr[N,16]")
         m = torch.empty((N, 16), dtype=torch.float32, device=ab.device)
         pre2 = torch.empty((N, 16, 16), dtype=torch.float32, device=ab.device)
+        ctx.products = products = precision.edge_products()
         # MFMA flops only: 2 * 16 outputs per (edge, hidden unit)
         timed("egnn_edge_fwd", N * 16 * Hp * 32,
-              lambda: hip.check(hip.lib().egnn_edge_fwd(_ptr(ab), _ptr(wd), _ptr(w2), _ptr(b2), _ptr(nbr), _ptr(d2), N, Hp,
-                                                        _ptr(m), _ptr(pre2), _stream(ab.device)), "egnn_edge_fwd"))
+              lambda: hip.check(hip.lib().egnn_edge_fwd_p(_ptr(ab), _ptr(wd), _ptr(w2), _ptr(b2), _ptr(nbr), _ptr(d2), N, Hp,
+                                                          _ptr(m), _ptr(pre2), _stream(ab.device), products), "egnn_edge_fwd"))
         ctx.save_for_backward(ab, wd, w2, pre2)
         ctx.nbr, ctx.d2, ctx.csr_t, ctx.b2_param, ctx.w_refs = nbr, d2, csr_t, b2_param, w_refs
         return m
@@ -60,10 +63,11 @@ class _EgnnEdge(torch.autograd.Function):
         tg = _acc_target(ctx.b2_param)   # d b2 = sum of dpre2 over nodes and slots, from the same pass
         db2 = tg if tg is not None else torch.empty(16, dtype=torch.float32, device=dev)
         timed("egnn_edge_bwd", N * 16 * Hp * 96,     # MFMA flops only: three 16-wide products per (edge, hidden unit)
-              lambda: hip.check(L.egnn_edge_bwd(_ptr(ab), _ptr(wd), _ptr(w2), _ptr(ctx.nbr), _ptr(ctx.d2), _ptr(pre2),
-                                                _ptr(dm), dm_ld, _ptr(ctx.csr_t.rowptr), _ptr(ctx.csr_t.perm), N, Hp, _ptr(dab),
-                                                _ptr(dwd), _ptr(dw2), _ptr(dpre2), _ptr(db2), 1 if tg is not None else 0,
-                                                1 if w_acc else 0, _ptr(ws), ws_bytes, _stream(dev)), "egnn_edge_bwd"))
+              lambda: hip.check(L.egnn_edge_bwd_p(_ptr(ab), _ptr(wd), _ptr(w2), _ptr(ctx.nbr), _ptr(ctx.d2), _ptr(pre2),
+                                                  _ptr(dm), dm_ld, _ptr(ctx.csr_t.rowptr), _ptr(ctx.csr_t.perm), N, Hp, _ptr(dab),
+                                                  _ptr(dwd), _ptr(dw2), _ptr(dpre2), _ptr(db2), 1 if tg is not None else 0,
+                                                  1 if w_acc else 0, _ptr(ws), ws_bytes, _stream(dev), ctx.products),
+                                "egnn_edge_bwd"))
         return (dab, None if w_acc else dwd, None if w_acc else dw2, (None if tg is not None else db2), None, None, None, None,
                 None)
 

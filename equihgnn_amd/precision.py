@@ -9,28 +9,38 @@ their row images in LDS hold two / one plane, and they sum the same three / one 
 without the keyword switches it off again, so the word keeps its earlier meaning at every earlier call site.
 ``set_float32_matmul_precision(mode, wgrads=True)`` extends it, in the same way, to the batched weight gradients of a training
 step (csrc/wgrad.hip, hg_wgrad_batch_bf16: the dY^T X products that defer_flush runs in one launch per shape): both operands are
-then split into two / one plane in registers and the same three / one terms are summed.  Products that go to none of these (the
-fp32 library below its threshold, the EGNN edge kernel, the single-product and skinny weight gradients hg_wgrad_f32 and
-hg_wgrad_skinny_f32) and all row-wise work stay at fp32 grade in every mode.  ops.products and the panel operators read the mode at call time (an autograd node of the panel
-operators multiplies its backward pass as it multiplied its forward pass); a captured step replays the mode it was captured
-under (trainer keys its graphs by the word and both flags; ops.wgrad_batch reads the mode when it runs, at defer_flush).
+then split into two / one plane in registers and the same three / one terms are summed.
+``set_float32_matmul_precision(mode, edges=True)`` extends it to the fused EGNN edge update (csrc/egnn_edge.hip, egnn_edge_fwd_p /
+egnn_edge_bwd_p): the forward's silu(h) W2^T product, and the backward's dpre2 W2 products of the receiver and the sender pass
+and its dW2 = dpre2^T silu(h) product (which lives in that kernel, so `edges` governs it, not `wgrads`), split their operands
+into two / one plane in registers and sum three / one bf16 terms into fp32.  Where the forward runs its fp32-MFMA kernel (Hp above
+1152, or EQH_EDGE_F32=1) it stays at fp32 grade in every mode; the backward is reduced at every width.  The three flags are
+independent.  Products that go to none of these (the fp32 library below its threshold, the EGNN edge kernel without the `edges`
+flag, the single-product and skinny weight gradients hg_wgrad_f32 and hg_wgrad_skinny_f32) and all row-wise work (the
+recomputation of h, SiLU and its derivative, dwd, the row sums of dA / dB, every reduction) stay at fp32 grade in every mode.
+ops.products and the panel operators read the mode at call time (an autograd node of the panel
+operators, and of the edge update, multiplies its backward pass as it multiplied its forward pass); a captured step replays the
+mode it was captured under (trainer keys its graphs by the word and the three flags; ops.wgrad_batch reads the mode when it runs, at defer_flush).
 profiles/panel_precision_bench.json has what the `panels` flag gains; tools/bench_matmul_precision.py --wgrads measures the
-`wgrads` flag (into profiles/wgrad_precision_bench.json).
+`wgrads` flag (into profiles/wgrad_precision_bench.json) and, with --edges, the `edges` flag (into
+profiles/edge_precision_bench.json; no run of it is recorded yet).
 """
 PRODUCTS = {"highest": 6, "high": 3, "medium": 1}     # mode -> `products` of hg_gemm_bf16_batch and of the panel entry points
 PLANES = {6: 3, 3: 2, 1: 1}                           # products -> bf16 planes per operand
 _mode = "highest"
 _panels = False
 _wgrads = False
+_edges = False
 
 
-def set_float32_matmul_precision(mode: str, panels: bool = False, wgrads: bool = False) -> None:
-    global _mode, _panels, _wgrads
+def set_float32_matmul_precision(mode: str, panels: bool = False, wgrads: bool = False, edges: bool = False) -> None:
+    global _mode, _panels, _wgrads, _edges
     if mode not in PRODUCTS:
         raise ValueError(f"matmul precision must be one of {tuple(PRODUCTS)}, not {mode!r}")
     _mode = mode
     _panels = bool(panels)
     _wgrads = bool(wgrads)
+    _edges = bool(edges)
 
 
 def get_float32_matmul_precision() -> str:
@@ -47,6 +57,11 @@ def get_float32_matmul_precision_wgrads() -> bool:
     return _wgrads
 
 
+def get_float32_matmul_precision_edges() -> bool:
+    """Whether the mode also governs the fused EGNN edge kernels (the ``edges`` keyword of the last set call)."""
+    return _edges
+
+
 def products() -> int:
     """Partial products per fp32 product under the current mode (6, 3 or 1)."""
     return PRODUCTS[_mode]
@@ -60,3 +75,8 @@ def panel_products() -> int:
 def wgrad_products() -> int:
     """Partial products per fp32 product of the batched weight gradients: the mode's with ``wgrads=True``, else 6."""
     return PRODUCTS[_mode] if _wgrads else 6
+
+
+def edge_products() -> int:
+    """Partial products per fp32 product of the fused EGNN edge kernels: the mode's with ``edges=True``, else 6."""
+    return PRODUCTS[_mode] if _edges else 6

@@ -18,8 +18,8 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .precision import (get_float32_matmul_precision, get_float32_matmul_precision_panels,
-                        get_float32_matmul_precision_wgrads)
+from .precision import (get_float32_matmul_precision, get_float32_matmul_precision_edges,
+                        get_float32_matmul_precision_panels, get_float32_matmul_precision_wgrads)
 
 
 def _world() -> int:
@@ -312,14 +312,14 @@ class GraphedTrainStep:
 
     @staticmethod
     def _key(b):
-        # (the matmul precision mode, and whether it governs the panel kernels and the batched weight gradients, are part of the
-        # key: a graph replays the arithmetic it was captured under -- the step's weight packs and its batched weight-gradient
+        # (the matmul precision mode, and whether it governs the panel kernels, the batched weight gradients and the EGNN edge
+        # kernels, are part of the key: a graph replays the arithmetic it was captured under -- the step's weight packs and its batched weight-gradient
         # launch are launches of that graph, so they follow the key too)
         mode, panels = get_float32_matmul_precision(), get_float32_matmul_precision_panels()
-        wgrads = get_float32_matmul_precision_wgrads()
+        wgrads, edges = get_float32_matmul_precision_wgrads(), get_float32_matmul_precision_edges()
         if not hasattr(b, "edge_index0"):       # a 2-D batch (batch.GBatch): atoms, edges, molecules
-            return (b.x.shape[0], b.edge_index.shape[1], b.y.shape[0], wgrads, panels, mode)
-        return (b.x.shape[0], b.edge_attr.shape[0], b.edge_index0.shape[0], b.y.shape[0], wgrads, panels, mode)
+            return (b.x.shape[0], b.edge_index.shape[1], b.y.shape[0], edges, wgrads, panels, mode)
+        return (b.x.shape[0], b.edge_attr.shape[0], b.edge_index0.shape[0], b.y.shape[0], edges, wgrads, panels, mode)
 
     def _loss(self, data):
         nb = getattr(data, "num_real_graphs", None) or data.y.shape[0]

@@ -516,6 +516,20 @@ int egnn_edge_bwd(const float* ab, const float* wd, const float* w2, const int32
                   const int32_t* t_perm, int64_t N, int32_t Hp, float* dab, float* dwd, float* dw2,
                   float* dpre2, float* db2, int32_t db2_accumulate, int32_t dw_accumulate, void* workspace,
                   size_t workspace_bytes, void* stream);
+/* The same two with `products` bf16 products per fp32 product in their matrix products (the matmul precision modes: 6, 3 or 1;
+ * anything else is EQH_ERR_ARG before any other argument is looked at).  6 is egnn_edge_fwd / egnn_edge_bwd, bit for bit.  3 / 1:
+ * the forward's silu(h) W2^T, the backward's dpre2 W2 (receiver and sender pass) and dW2 = dpre2^T silu(h) split both operands
+ * into two / one bf16 plane and sum three / one terms into fp32; everything row-wise stays fp32.  Where the forward runs its
+ * fp32-MFMA kernel (Hp > 1152, or EQH_EDGE_F32=1) every count gives that kernel's result.  egnn_edge_bwd_workspace_bytes holds
+ * for every count. */
+int egnn_edge_fwd_p(const float* ab, const float* wd, const float* w2, const float* b2,
+                    const int32_t* nbr, const float* d2, int64_t N, int32_t Hp, float* m, float* pre2,
+                    void* stream, int32_t products);
+int egnn_edge_bwd_p(const float* ab, const float* wd, const float* w2, const int32_t* nbr,
+                    const float* d2, const float* pre2, const float* dm, int64_t dm_ld, const int32_t* t_rowptr,
+                    const int32_t* t_perm, int64_t N, int32_t Hp, float* dab, float* dwd, float* dw2,
+                    float* dpre2, float* db2, int32_t db2_accumulate, int32_t dw_accumulate, void* workspace,
+                    size_t workspace_bytes, void* stream, int32_t products);
 
 /* ---------------------------------------------------------------------------------------------
  * CSR-grouped small GEMMs — the Equiformer's radial tensor product (equiformer_layer.py:376-383:

@@ -39,6 +39,17 @@ first is the ratios' base).  ``pairs`` compares each ``mode+panels+wgrads`` with
 commit before the flag -- beyond both spreads; ``--merge`` adds that commit's own build timed by its own copy of this tool.
 
     python tools/bench_matmul_precision.py --wgrads [--variants ...] [--skip-products] [--skip-steps] [--merge [NAME=]FILE]
+
+``--edges`` times what ``set_float32_matmul_precision(mode, edges=True)`` gives (default output
+profiles/edge_precision_bench.json), in one process on replayed graphs: the lone forward launch of the fused EGNN edge update
+(egnn_edge_fwd_p) and its lone backward (egnn_edge_bwd_p: prep + receiver pass + sender pass + the slab reductions) at
+N = 4608 / Hp = 1088 (the BASELINE batch) and N = 29696 / Hp = 1088 (batch 1024), the neighbours a kNN over one cloud of the whole
+batch as in the model, with 6 / 3 / 1 products; and the replayed training step of ``egnn_equihnns`` (batch 256, hidden 256)
+under highest, medium, medium+edges and medium+panels+wgrads+edges.  ``pairs`` compares each variant with ``+edges`` with the
+same variant without it, where that was timed, beyond both spreads; ``--merge`` adds the flag-off rows of the commit before the
+flag, timed by its own copy of this tool (``--wgrads --variants highest,medium --skip-products``).
+
+    python tools/bench_matmul_precision.py --edges [--variants ...] [--skip-products] [--skip-steps] [--merge [NAME=]FILE]
 """
 from __future__ import annotations
 
@@ -123,7 +134,7 @@ def gemm_times(a, dev):
 def _set_mode(variant):
     import equihgnn_amd
     mode, *flags = variant.split("+")
-    unknown = set(flags) - {"panels", "wgrads"}
+    unknown = set(flags) - {"panels", "wgrads", "edges"}
     if unknown:
         raise SystemExit(f"unknown flag(s) {sorted(unknown)} in variant {variant!r}")
     equihgnn_amd.set_float32_matmul_precision(mode, **{f: True for f in flags})
@@ -284,6 +295,110 @@ def wgrad_launch_times(a, dev, count, K=4736, C=256):
     return entry
 
 
+def edge_launch_times(a, dev, N, Hp=1088):
+    """the lone forward launch and the lone backward of the fused EGNN edge update under 6 / 3 / 1 products: hipGraphs of REPS
+    launches, interleaved blocks between device events"""
+    import ctypes
+    from equihgnn_amd import hip, ops
+    L = hip.lib()
+    g = torch.Generator().manual_seed(0)
+    ab = torch.randn(N, 2 * Hp, generator=g).to(dev)
+    wd = (torch.randn(Hp, generator=g) * 0.3).to(dev)
+    w2 = (torch.randn(16, Hp, generator=g) / Hp ** 0.5).to(dev)
+    b2 = (torch.randn(16, generator=g) * 0.1).to(dev)
+    dm = torch.randn(N, 16, generator=g).to(dev)
+    nbr, d2 = ops.knn((torch.randn(N, 3, generator=g) * 2).to(dev), 16, 0)      # one cloud: the kNN ignores molecule boundaries
+    nbr, d2 = nbr.int().contiguous(), d2.contiguous()
+    csr_t = ops.csr_build(nbr.reshape(-1).long(), None, N)
+    m, pre2 = torch.empty(N, 16, device=dev), torch.empty(N, 16, 16, device=dev)
+    dab, dwd, dw2 = torch.empty(N, 2 * Hp, device=dev), torch.empty(Hp, device=dev), torch.empty(16, Hp, device=dev)
+    dpre2, db2 = torch.empty(N, 16, 16, device=dev), torch.empty(16, device=dev)
+    ws_bytes = L.egnn_edge_bwd_workspace_bytes(N, Hp)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+
+    def forward(products):
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        hip.check(L.egnn_edge_fwd_p(p(ab), p(wd), p(w2), p(b2), p(nbr), p(d2), N, Hp, p(m), p(pre2), st, products), "egnn_edge_fwd_p")
+
+    def backward(products):
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        hip.check(L.egnn_edge_bwd_p(p(ab), p(wd), p(w2), p(nbr), p(d2), p(pre2), p(dm), 16, p(csr_t.rowptr), p(csr_t.perm), N, Hp,
+                                    p(dab), p(dwd), p(dw2), p(dpre2), p(db2), 0, 0, p(ws), ws_bytes, st, products), "egnn_edge_bwd_p")
+
+    forward(6)
+    graphs = {}
+    for what, fn in (("forward", forward), ("backward", backward)):
+        for products in (6, 3, 1):
+            for _ in range(3):
+                fn(products)
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                for _ in range(REPS):
+                    fn(products)
+            graphs[what, products] = gr
+    for gr in graphs.values():
+        for _ in range(3):
+            gr.replay()
+    torch.cuda.synchronize()
+    times = {k: [] for k in graphs}
+    for _ in range(a.blocks):
+        for k, gr in graphs.items():
+            s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(a.inner):
+                gr.replay()
+            t.record()
+            torch.cuda.synchronize()
+            times[k].append(s.elapsed_time(t) * 1e3 / (a.inner * REPS))
+    entry = {"N": N, "Hp": Hp, "forward": {}, "backward": {}}
+    for what in ("forward", "backward"):
+        base, base_sp = _stat(times[what, 6])
+        for products in (6, 3, 1):
+            med, sp = _stat(times[what, products])
+            entry[what][f"products_{products}"] = {"us": round(med, 2), "spread": round(sp, 4), "vs_six_products": round(med / base, 4),
+                                                   "faster_than_six_products_beyond_spread": bool(med * (1 + sp) < base * (1 - base_sp))}
+    del graphs, ab, dab, ws
+    gc.collect()
+    torch.cuda.empty_cache()
+    return entry
+
+
+def main_edges(a, dev):
+    variants = tuple(v for v in a.variants.split(",") if v)
+    result = {"bench": "edge_precision", "device": torch.cuda.get_device_name(0),
+              "timing": f"launches: hipGraphs of {REPS} x (the forward launch | prep + receiver + sender pass + slab reductions), {a.blocks} "
+                        f"interleaved blocks of {a.inner} replays between device events; steps: {a.blocks} interleaved blocks of {a.steps} "
+                        "replayed steps on a host clock; median block, spread = (max - min) / median",
+              "variants": "mode[+panels][+wgrads][+edges]: set_float32_matmul_precision(mode, panels=..., wgrads=..., edges=...); without "
+                          "+edges the edge kernels keep six products (the arithmetic of the commit before the flag)",
+              "steps": {}}
+    if not a.skip_products:
+        result["edge_4608_1088"] = edge_launch_times(a, dev, 4608)
+        result["edge_29696_1088"] = edge_launch_times(a, dev, 29696)
+    if not a.skip_steps:
+        result["steps"]["egnn_equihnns_b256_h256"] = step_times("egnn_equihnns", 256, "qm9", 1000, a, dev, variants, hidden=256)
+        pairs = {}
+        for name, e in result["steps"].items():
+            for v in variants:
+                off = v.replace("+edges", "")
+                if v != off and off in e:
+                    pairs[f"{name}/{v}"] = {"vs": off, "ratio": round(e[v]["ms"] / e[off]["ms"], 4),
+                                            "faster_beyond_both_spreads": bool(e[v]["ms"] * (1 + e[v]["spread"]) <
+                                                                               e[off]["ms"] * (1 - e[off]["spread"]))}
+        result["pairs"] = pairs
+    for item in a.merge:
+        name, _, path = item.rpartition("=")
+        with open(path) as f:
+            result[name or "other_build"] = json.loads(f.readline())
+    line = json.dumps(result)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main_wgrads(a, dev):
     variants = tuple(v for v in a.variants.split(",") if v)
     result = {"bench": "wgrad_precision", "device": torch.cuda.get_device_name(0),
@@ -361,6 +476,7 @@ def main():
     ap.add_argument("--skip-steps", action="store_true")
     ap.add_argument("--panels", action="store_true", help="time the panel kernels' modes instead (see the module docstring)")
     ap.add_argument("--wgrads", action="store_true", help="time the batched weight gradients' modes instead (see the module docstring)")
+    ap.add_argument("--edges", action="store_true", help="time the EGNN edge kernels' modes instead (see the module docstring)")
     ap.add_argument("--variants", default=None)
     ap.add_argument("--skip-products", action="store_true")
     ap.add_argument("--rows", default="4864", help="row counts of the lone panel product (--panels)")
@@ -369,14 +485,17 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.variants is None:
-        a.variants = ("highest+panels,high+panels,medium+panels,highest+panels+wgrads,high+panels+wgrads,medium+panels+wgrads"
+        a.variants = ("highest,medium,medium+edges,medium+panels+wgrads+edges" if a.edges else
+                      "highest+panels,high+panels,medium+panels,highest+panels+wgrads,high+panels+wgrads,medium+panels+wgrads"
                       if a.wgrads else "highest,medium,high+panels,medium+panels")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "wgrad_precision_bench.json" if a.wgrads else
+        a.out = os.path.join(ROOT, "profiles", "edge_precision_bench.json" if a.edges else "wgrad_precision_bench.json" if a.wgrads else
                              "panel_precision_bench.json" if a.panels else "matmul_precision_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_matmul_precision: no GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
+    if a.edges:
+        return main_edges(a, dev)
     if a.wgrads:
         return main_wgrads(a, dev)
     if a.panels:
