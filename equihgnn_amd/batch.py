@@ -215,6 +215,27 @@ class MolStore:
         idx = np.asarray(idx, dtype=np.int64)
         return int(self.n_nodes[idx].sum()), int(self.n_he[idx].sum()), int(self.n_inc[idx].sum())
 
+    # what fit.BucketedLoader asks a store for (GraphStore answers with two extents instead of three)
+    SPARE = (1, 1, 1)                   # slots a padded batch needs beyond its molecules' (the padding molecule's own)
+
+    def count_columns(self) -> tuple:
+        """Per-molecule counts, one array per extent of a batch."""
+        return self.n_nodes, self.n_he, self.n_inc
+
+    @staticmethod
+    def bucket(ext, quantum: int) -> tuple:
+        """The static extents of the bucket that holds a batch of extents ``ext``."""
+        return bucket_sizes(ext[0], ext[1], ext[2], quantum)
+
+    @staticmethod
+    def ladder_step(quantum: int) -> tuple:
+        """Distance between neighbouring rungs of the loader's bucket ladder, per extent."""
+        return quantum, quantum, 2 * quantum
+
+    def empty_staging(self, tgt, n_graphs: int, pin: bool = False) -> "HBatch":
+        """An empty packed staging batch of extents ``tgt`` for ``collate(out=...)``."""
+        return HBatch.empty_packed(tgt[0], tgt[1], tgt[2], n_graphs, pin=pin)
+
     @staticmethod
     def _ranges(starts, counts):
         """Concatenation of arange(starts[i], starts[i] + counts[i]) and the owner i of every element."""
@@ -499,11 +520,59 @@ class GBatch:
     num_graphs: int = 0
 
     def to(self, device, non_blocking: bool = False) -> "GBatch":
+        flat = getattr(self, "_flat", None)
+        if flat is not None:   # packed: ONE transfer, then the same views over the new buffer
+            return self._from_flat(flat.to(device, non_blocking=non_blocking), self._layout)
         kw = {}
         for f in fields(self):
             v = getattr(self, f.name)
             kw[f.name] = v.to(device, non_blocking=non_blocking) if torch.is_tensor(v) else v
         out = GBatch(**kw)
+        if hasattr(self, "num_real_graphs"):
+            out.num_real_graphs = self.num_real_graphs
+        return out
+
+    @staticmethod
+    def _plan(spec):
+        """(layout, bytes) of the tensors ``spec`` = ((name, shape, dtype), ...) in one flat buffer, 256-byte aligned slots"""
+        layout, total = [], 0
+        for name, shape, dtype in spec:
+            layout.append((name, total, tuple(shape), dtype))
+            nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+            total += (nbytes + 255) // 256 * 256
+        return tuple(layout), max(total, 256)
+
+    def packed(self) -> "GBatch":
+        """The same batch with every tensor field a view into ONE flat byte buffer (256-byte aligned slots), as
+        ``HBatch.packed``: host-to-device staging and the refresh of a captured graph's static inputs are one copy."""
+        names = [f.name for f in fields(self) if torch.is_tensor(getattr(self, f.name))]
+        layout, total = self._plan([(n, getattr(self, n).shape, getattr(self, n).dtype) for n in names])
+        out = self._from_flat(torch.empty(total, dtype=torch.uint8, device=self.x.device), layout)
+        for n in names:
+            getattr(out, n).copy_(getattr(self, n))
+        return out
+
+    @classmethod
+    def empty_packed(cls, n_nodes: int, n_edges: int, n_bond_features: int, n_graphs: int, pin: bool = False) -> "GBatch":
+        """An uninitialised packed host batch of the given extents (one flat buffer, optionally pinned): the staging buffer
+        a loader thread collates into (``GraphStore.collate(out=...)``)."""
+        spec = (("x", (n_nodes, 9), torch.int64), ("edge_index", (2, n_edges), torch.int64),
+                ("edge_attr", (n_edges, n_bond_features), torch.int64), ("batch", (n_nodes,), torch.int64),
+                ("y", (n_graphs,), torch.float32))
+        layout, total = cls._plan(spec)
+        flat = torch.empty(total, dtype=torch.uint8)
+        if pin:
+            flat = flat.pin_memory()
+        proto = cls(**{name: torch.empty(0) for name, _, _ in spec}, num_nodes=n_nodes, num_edges=n_edges, num_graphs=n_graphs)
+        return proto._from_flat(flat, layout)
+
+    def _from_flat(self, flat, layout) -> "GBatch":
+        kw = {f.name: getattr(self, f.name) for f in fields(self) if not torch.is_tensor(getattr(self, f.name))}
+        for n, off, shape, dtype in layout:
+            nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+            kw[n] = flat[off:off + nbytes].view(dtype).view(shape)
+        out = GBatch(**kw)
+        out._flat, out._layout = flat, layout
         if hasattr(self, "num_real_graphs"):
             out.num_real_graphs = self.num_real_graphs
         return out
@@ -534,16 +603,157 @@ def collate_graphs(mols: Sequence[GMol]) -> GBatch:
 
 
 class GraphStore:
-    """In-memory list of 2-D molecules (the reference's ``*_g`` datasets) with numpy collate."""
+    """A dataset of 2-D molecules (the reference's ``*_g`` datasets) as a structure of arrays, the counterpart of
+    ``MolStore``: the concatenated fields plus per-molecule offsets, so that a batch is assembled without a Python loop over
+    molecules (the library's host-side ``gb_collate``).  Field semantics as GBatch / PyG ``Data``; ``src`` / ``dst`` are
+    the two rows of ``edge_index`` with atom ids LOCAL to their molecule; all molecules share one bond-feature width F."""
 
     def __init__(self, mols: Sequence[GMol]):
-        self.mols = list(mols)
+        mols = list(mols)
+        widths = {int(m.edge_attr.shape[1]) if m.edge_attr.ndim == 2 else 1 for m in mols}
+        if len(widths) > 1:
+            raise ValueError(f"GraphStore: the molecules disagree on the number of bond features: {sorted(widths)}")
+        F = widths.pop() if widths else 1
+        cat = lambda xs, dt, shape, ax=0: (np.ascontiguousarray(np.concatenate(xs, ax), dtype=dt) if len(xs)
+                                           else np.zeros(shape, dt))
+        ei = cat([m.edge_index.reshape(2, -1) for m in mols], np.int64, (2, 0), 1)
+        self._seat(n_nodes=np.array([m.x.shape[0] for m in mols], dtype=np.int64),
+                   n_edges=np.array([m.edge_index.shape[1] for m in mols], dtype=np.int64),
+                   x=cat([m.x for m in mols], np.int64, (0, 9)), src=np.ascontiguousarray(ei[0]),
+                   dst=np.ascontiguousarray(ei[1]), edge_attr=cat([m.edge_attr.reshape(-1, F) for m in mols], np.int64, (0, F)),
+                   y=np.array([m.y for m in mols], dtype=np.float32), F=F)
 
-    def __len__(self):
-        return len(self.mols)
+    @classmethod
+    def from_arrays(cls, n_nodes, n_edges, x, src, dst, edge_attr, y) -> "GraphStore":
+        """A store over arrays that are already concatenated (a processed dataset file: reader.read_processed_graph):
+        per-molecule counts, x [N, 9], local src / dst [E], edge_attr [E, F], y [n_mols].  Arrays of the right dtype and
+        layout are kept as they are, not copied."""
+        c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
+        edge_attr = c(edge_attr, np.int64)
+        if edge_attr.ndim != 2:
+            raise ValueError("GraphStore: edge_attr must be [E, F]")
+        st = cls.__new__(cls)
+        st._seat(n_nodes=c(n_nodes, np.int64), n_edges=c(n_edges, np.int64), x=c(x, np.int64), src=c(src, np.int64),
+                 dst=c(dst, np.int64), edge_attr=edge_attr, y=c(y, np.float32), F=int(edge_attr.shape[1]))
+        st._checked_pointers()
+        return st
 
-    def collate(self, indices) -> GBatch:
-        return collate_graphs([self.mols[int(i)] for i in indices])
+    def subset(self, idx) -> "GraphStore":
+        """The store of molecules ``idx`` (a train / valid / test split), by array gathers."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
+            raise IndexError("subset: molecule index outside the store")
+        rows = lambda off, cnt: MolStore._ranges(off[idx], cnt[idx])[0]
+        a, e = rows(self.node_off, self.n_nodes), rows(self.edge_off, self.n_edges)
+        return GraphStore.from_arrays(self.n_nodes[idx], self.n_edges[idx], self.x[a], self.src[e], self.dst[e],
+                                      self.edge_attr[e], self.y[idx])
+
+    def _seat(self, n_nodes, n_edges, x, src, dst, edge_attr, y, F):
+        off = lambda c: np.concatenate(([0], np.cumsum(c))).astype(np.int64)
+        self.n_nodes, self.n_edges = n_nodes, n_edges
+        self.node_off, self.edge_off = off(n_nodes), off(n_edges)
+        self.x, self.src, self.dst, self.edge_attr, self.y, self.F = x, src, dst, edge_attr, y, F
+
+    def __len__(self) -> int:
+        return int(self.n_nodes.shape[0])
+
+    def extents(self, idx) -> tuple:
+        """(atoms, edges) of the batch made of molecules ``idx``."""
+        idx = np.asarray(idx, dtype=np.int64)
+        return int(self.n_nodes[idx].sum()), int(self.n_edges[idx].sum())
+
+    # what fit.BucketedLoader asks a store for (MolStore answers with three extents, this one with two)
+    SPARE = (1, 0)                      # slots a padded batch needs beyond its molecules': the padding molecule's atom
+
+    def count_columns(self) -> tuple:
+        return self.n_nodes, self.n_edges
+
+    @staticmethod
+    def bucket(ext, quantum: int) -> tuple:
+        return graph_bucket_sizes(ext[0], ext[1], quantum)
+
+    @staticmethod
+    def ladder_step(quantum: int) -> tuple:
+        return quantum, 2 * quantum
+
+    def empty_staging(self, tgt, n_graphs: int, pin: bool = False) -> "GBatch":
+        return GBatch.empty_packed(tgt[0], tgt[1], self.F, n_graphs, pin=pin)
+
+    def collate(self, idx, pad_to: Optional[tuple] = None, out: Optional["GBatch"] = None) -> "GBatch":
+        """The batch of molecules ``idx`` (what ``collate_graphs`` returns for them), optionally padded to the static
+        extents ``pad_to`` = (atoms, edges) exactly as ``pad_graph_batch`` does, optionally written into the tensors of
+        ``out`` (a packed, pinned staging batch of those extents).  Assembled by the library's host-side ``gb_collate``
+        (csrc/collate.hip); ``collate_graphs`` + ``pad_graph_batch`` are the restatement the tests compare it with, bit
+        for bit."""
+        from . import hip
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        B, F = idx.shape[0], self.F
+        if B and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
+            raise IndexError("collate: molecule index outside the store")
+        if pad_to is None:
+            PN, PE = self.extents(idx)
+            PB = B
+        else:
+            PN, PE = (int(v) for v in pad_to)
+            PB = B + 1
+        if out is None:
+            t = lambda shape, dt: torch.empty(shape, dtype=dt)
+            out = GBatch(x=t((PN, 9), torch.int64), edge_index=t((2, PE), torch.int64), edge_attr=t((PE, F), torch.int64),
+                         batch=t((PN,), torch.int64), y=t((PB,), torch.float32))
+        a = hip.GbCollate()
+        a.B, a.n_mols, a.idx = B, len(self), idx.ctypes.data
+        for name, ptr in self._checked_pointers().items():
+            setattr(a, name, ptr)
+        a.F, a.PN, a.PE, a.padded = F, PN, PE, 0 if pad_to is None else 1
+        shapes = dict(x=(PN, 9), edge_index=(2, PE), edge_attr=(PE, F), batch=(PN,), y=(PB,))
+        for name, shp in shapes.items():
+            ten = getattr(out, name)
+            want = torch.float32 if name == "y" else torch.int64
+            if tuple(ten.shape) != shp or ten.dtype != want or not ten.is_contiguous() or ten.device.type != "cpu":
+                raise ValueError(f"collate: out.{name} must be a contiguous CPU {want} tensor of shape {shp}")
+            setattr(a, "out_" + name, ten.data_ptr())
+        counts = np.zeros(2, dtype=np.int64)
+        a.out_counts = counts.ctypes.data
+        rc = hip.lib().gb_collate(ctypes.byref(a))
+        if rc == hip.EQH_ERR_RANGE and pad_to is not None:       # the extents do not fit (indices were checked above)
+            raise ValueError("collate: pad_to must exceed the batch (atoms strictly)")
+        hip.check(rc, "gb_collate")
+        if pad_to is not None:
+            out.num_real_graphs = B
+        out.num_nodes, out.num_edges, out.num_graphs = PN, PE, PB
+        return out
+
+    _ARRAYS = ("node_off", "edge_off", "x", "src", "dst", "edge_attr", "y")
+
+    def _checked_pointers(self) -> dict:
+        """Addresses of the store's arrays for ``gb_collate``, which copies whole rows by them: arrays of another dtype,
+        width or length must fail HERE, not read the wrong rows or run past the end.  Checked once per set of array
+        objects (and bond-feature width)."""
+        key = tuple(id(getattr(self, n)) for n in self._ARRAYS) + (self.F,)
+        cached = getattr(self, "_ptr_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        n_mols = len(self)
+        for name in ("node_off", "edge_off"):
+            arr = getattr(self, name)
+            if arr.dtype != np.int64 or arr.shape != (n_mols + 1,) or not arr.flags.c_contiguous:
+                raise ValueError(f"GraphStore.{name} must be a C-contiguous int64 array of {n_mols + 1} offsets")
+            if int(arr[0]) != 0 or (n_mols and int(np.diff(arr).min()) < 0):
+                raise ValueError(f"GraphStore.{name} must start at 0 and not decrease")
+        N, E = int(self.node_off[-1]), int(self.edge_off[-1])
+        want = dict(x=(np.int64, (N, 9)), src=(np.int64, (E,)), dst=(np.int64, (E,)), edge_attr=(np.int64, (E, int(self.F))),
+                    y=(np.float32, (n_mols,)))
+        ptrs = {}
+        for name in self._ARRAYS:
+            arr = getattr(self, name)
+            if name in want:
+                dt, shape = want[name]
+                if arr.dtype != dt or tuple(arr.shape) != shape or not arr.flags.c_contiguous:
+                    raise ValueError(f"GraphStore.{name} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}, got "
+                                     f"{arr.dtype} {tuple(arr.shape)}{'' if arr.flags.c_contiguous else ' (strided)'}")
+            ptrs[name] = arr.ctypes.data if arr.size else None
+        self._ptr_cache = (key, ptrs)
+        return ptrs
 
 
 def graph_bucket_sizes(n_nodes: int, n_edges: int, quantum: int = 128):

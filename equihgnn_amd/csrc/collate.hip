@@ -75,3 +75,63 @@ extern "C" int hb_collate(const HbCollate* q) {
     }
     return EQH_OK;
 }
+
+// The same assembly for 2-D molecular graphs (batch.GraphStore -> GBatch): PyG's Batch.from_data_list for Data(x, edge_index,
+// edge_attr, y) plus the padding of batch.pad_graph_batch (one dummy molecule owns the padded atoms, padded edges form a ring
+// over them).  out_edge_index is [2, PE]: sources in row 0, targets in row 1.
+extern "C" int gb_collate(const GbCollate* q) {
+    if (!q || q->B < 0 || q->F < 0 || (q->B > 0 && !q->idx) || !q->out_counts) return EQH_ERR_ARG;
+    if (q->B > 0 && (!q->node_off || !q->edge_off)) return EQH_ERR_ARG;
+    const int64_t B = q->B, F = q->F;
+    int64_t N = 0, E = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t m = q->idx[b];
+        if (m < 0 || m >= q->n_mols) return EQH_ERR_RANGE;
+        N += q->node_off[m + 1] - q->node_off[m];
+        E += q->edge_off[m + 1] - q->edge_off[m];
+    }
+    q->out_counts[0] = N; q->out_counts[1] = E;
+    const int64_t PN = q->padded ? q->PN : N, PE = q->padded ? q->PE : E;
+    // the padding molecule needs an atom of its own (its edges may be none)
+    if (q->padded && (PN <= N || PE < E)) return EQH_ERR_RANGE;
+    const int64_t PB = B + (q->padded ? 1 : 0);
+    // an array may be NULL exactly when its extent is zero (edge_attr rows of width F = 0 have none)
+    const struct { const void* p; int64_t extent; } need[] = {
+        {q->x, N}, {q->src, E}, {q->dst, E}, {q->edge_attr, E * F}, {q->y, B},
+        {q->out_x, PN}, {q->out_batch, PN}, {q->out_edge_index, PE}, {q->out_edge_attr, PE * F}, {q->out_y, PB}};
+    for (const auto& a : need)
+        if (!a.p && a.extent > 0) return EQH_ERR_ARG;
+    int64_t* const out_src = q->out_edge_index;
+    int64_t* const out_dst = q->out_edge_index + PE;
+    int64_t n0 = 0, e0 = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t m = q->idx[b];
+        const int64_t ns = q->node_off[m], n = q->node_off[m + 1] - ns;
+        const int64_t es = q->edge_off[m], e = q->edge_off[m + 1] - es;
+        if (n) std::memcpy(q->out_x + n0 * 9, q->x + ns * 9, (size_t)n * 9 * sizeof(int64_t));
+        for (int64_t i = 0; i < n; ++i) q->out_batch[n0 + i] = b;
+        for (int64_t i = 0; i < e; ++i) {
+            out_src[e0 + i] = q->src[es + i] + n0;
+            out_dst[e0 + i] = q->dst[es + i] + n0;
+        }
+        if (e && F) std::memcpy(q->out_edge_attr + e0 * F, q->edge_attr + es * F, (size_t)e * F * sizeof(int64_t));
+        q->out_y[b] = q->y[m];
+        n0 += n; e0 += e;
+    }
+    if (q->padded) {
+        const int64_t pn = PN - N, pe = PE - E;
+        std::memset(q->out_x + N * 9, 0, (size_t)pn * 9 * sizeof(int64_t));
+        for (int64_t i = 0; i < pn; ++i) q->out_batch[N + i] = B;
+        // a ring over the padded atoms: edge k from N + k % pn to N + (k + 1) % pn (pn = 1: self-loops)
+        int64_t a = 0;
+        for (int64_t k = 0; k < pe; ++k) {
+            const int64_t nxt = (a + 1 == pn) ? 0 : a + 1;
+            out_src[E + k] = N + a;
+            out_dst[E + k] = N + nxt;
+            a = nxt;
+        }
+        if (pe && F) std::memset(q->out_edge_attr + E * F, 0, (size_t)pe * F * sizeof(int64_t));
+        q->out_y[B] = 0.f;
+    }
+    return EQH_OK;
+}

@@ -124,10 +124,14 @@ class BucketedLoader:
     shipped to the device with one asynchronous copy each.  ``GraphedTrainStep`` then replays one captured hipGraph
     for (almost) every batch of the run; only a smaller last batch has a shape of its own.
 
+    ``store`` is a ``MolStore`` (hypergraph batches, three extents) or a ``GraphStore`` (2-D graphs for gin / gcn, two
+    extents: atoms and edges).  The store answers everything that differs -- ``count_columns``, ``bucket``,
+    ``ladder_step``, ``SPARE``, ``empty_staging`` -- and the rest is one code path.
+
     The reference does this with torch_geometric's DataLoader (main.py:227-229): a per-molecule Python collate on
     the training process's own thread."""
 
-    def __init__(self, store: MolStore, batch_size: int, shuffle: bool, seed: int = 0, device=None, rank: int = 0,
+    def __init__(self, store, batch_size: int, shuffle: bool, seed: int = 0, device=None, rank: int = 0,
                  world: int = 1, quantum: int = 64, prefetch: int = 3, pin: Optional[bool] = None, levels: int = 1):
         self.store, self.bs, self.shuffle, self.seed = store, batch_size, shuffle, seed
         self.device, self.rank, self.world, self.quantum, self.prefetch = device, rank, world, quantum, prefetch
@@ -163,7 +167,7 @@ class BucketedLoader:
         batches = [idx[i:i + self.bs] for i in range(0, len(idx), self.bs)]
         # extents of every batch at once: prefix sums of the permuted per-molecule sizes (shards have equal lengths)
         cut = np.minimum(np.arange(0, len(idx) + self.bs, self.bs), len(idx))
-        counts = (self.store.n_nodes, self.store.n_he, self.store.n_inc)
+        counts = self.store.count_columns()                # (nodes, hyperedges, incidences) or (atoms, edges)
         sizes = [np.max([np.diff(np.concatenate(([0], np.cumsum(c[sh])))[cut]) for sh in shards], axis=0) for c in counts]
         ext = [sz.max() for sz in sizes]
         # ONE bucket for (almost) the whole run: the largest batch seen so far, a little above the first epoch's own
@@ -172,14 +176,14 @@ class BucketedLoader:
         # epoch whose largest batch still exceeds the envelope raises it (one more capture).  Every padded atom is
         # GPU work: the 4.5 sigma bound used before cost 3 % of the step.
         nb = min(self.bs, len(idx))
-        stat = [c.mean() * nb + 3.3 * c.std() * np.sqrt(nb) for c in (self.store.n_nodes, self.store.n_he, self.store.n_inc)]
+        stat = [c.mean() * nb + 3.3 * c.std() * np.sqrt(nb) for c in counts]
         env = getattr(self, "_envelope", None)
         ext = [max(int(e), int(np.ceil(s_)) if env is None else 0, 0 if env is None else env[i])
                for i, (e, s_) in enumerate(zip(ext, stat))]
         if nb == self.bs:
             self._envelope = ext
-        top = bucket_sizes(ext[0], ext[1], ext[2], self.quantum)
-        q = (self.quantum, self.quantum, 2 * self.quantum)
+        top = self.store.bucket(ext, self.quantum)        # bucket_sizes, or graph_bucket_sizes for a GraphStore
+        q = self.store.ladder_step(self.quantum)
         ladder = [tuple(t - l * qq for t, qq in zip(top, q)) for l in range(self.levels)]      # ladder[0] = top
         # the rungs in use are those the FIRST epoch populated (each is then captured in that epoch); later epochs choose
         # among them only, so a rare small or large batch never triggers a capture (seconds, with GEMM tuning) mid-run
@@ -188,7 +192,8 @@ class BucketedLoader:
             known = None                                      # the envelope grew: a new ladder
         tgts, used = [], {0}
         for i in range(len(batches)):
-            need = [int(sz[i]) + 1 for sz in sizes]          # (one spare slot: the padding molecule's own node / hyperedge)
+            # (the spare slots are the padding molecule's own node / hyperedge; a 2-D graph needs a spare atom only)
+            need = [int(sz[i]) + sp for sz, sp in zip(sizes, self.store.SPARE)]
             lvl = 0
             for cand in range(1, len(ladder)):
                 if known is not None and cand not in known[1]:
@@ -231,7 +236,7 @@ class BucketedLoader:
             [host, h2d_done, device, consumed]"""
             slot = ring.setdefault((tgt, n_mols), {"bufs": [], "next": 0})
             if len(slot["bufs"]) < self.prefetch + 4:
-                host = HBatch.empty_packed(tgt[0], tgt[1], tgt[2], n_mols + 1, pin=self.pin)
+                host = self.store.empty_staging(tgt, n_mols + 1, pin=self.pin)
                 with torch.cuda.stream(side) if cuda else contextlib.nullcontext():
                     devb = host.to(self.device) if cuda else None
                 slot["bufs"].append([host, None, devb, None])
@@ -327,6 +332,7 @@ class BucketedLoader:
             # and HyperIndex.from_batch caches the batch's CSRs / kNN lists on the object: a refilled buffer must not
             # carry the index of the molecules it held before.
             b._hyper_index = None
+            b._graph_index = None                                # (GraphIndex.from_batch, the 2-D models')
             b._generation = getattr(b, "_generation", 0) + 1     # (GraphedTrainStep's index prefetch: new contents, same object)
             return b
 
@@ -391,9 +397,10 @@ atexit.register(_close_live_loaders)
 
 def _drop_index(data):
     """A loader may hand the same batch OBJECT out with new contents: the per-batch index cached on it
-    (HyperIndex.from_batch) belongs to the previous contents."""
+    (HyperIndex.from_batch, GraphIndex.from_batch) belongs to the previous contents."""
     try:
         data._hyper_index = None
+        data._graph_index = None
     except Exception:
         pass
 

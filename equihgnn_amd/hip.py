@@ -105,7 +105,7 @@ def parse_header(text: str, path: str = "<header>"):
 
 with open(HEADER) as _f:
     _structs, SIGNATURES, _constants = parse_header(_f.read(), HEADER)
-globals().update(_structs)         # HgSmallMM, HgGemmProblem, HgPanelPack, HgConvPanel, HgPanelMulti, HgPanelSum, HbCollate
+globals().update(_structs)         # HgSmallMM, HgGemmProblem, HgPanelPack, HgConvPanel, HgPanelMulti, HgPanelSum, HbCollate, GbCollate
 globals().update(_constants)       # EQH_OK, EQH_ERR_*, HG_CONV_F1 .. HG_EGNN_NODE_B
 
 _lib = None

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from .batch import GMol, GraphStore, MolStore
+from .batch import GMol, GraphStore, MolStore  # noqa: F401  (GMol: no longer built here; kept importable from this module)
 
 FIELDS = ("x", "pos", "edge_index0", "edge_index1", "edge_attr", "e_order", "y", "n_e")
 _FOREIGN = ("torch_geometric", "equihgnn")
@@ -157,9 +157,13 @@ def read_processed_graph(path, target: int = 0):
     if ea.shape[1] > len(BOND_FEATURE_DIMS) or any(
             ea.shape[0] and (int(ea[:, f].min()) < 0 or int(ea[:, f].max()) >= d) for f, d in enumerate(BOND_FEATURE_DIMS[:ea.shape[1]])):
         raise ValueError(f"edge_attr outside the ogb bond tables {BOND_FEATURE_DIMS}: the kernels would clamp it")
-    mols = [GMol(x=x[ns[i]:ns[i + 1]], edge_index=ei[:, es[i]:es[i + 1]], edge_attr=ea[es[i]:es[i + 1]], y=float(y[i]))
-            for i in range(n_mol)]
-    for m in mols:
-        if m.edge_index.size and int(m.edge_index.max()) >= m.x.shape[0]:
+    n_nodes, n_edges = np.diff(ns), np.diff(es)
+    if ns[0] != 0 or es[0] != 0 or (n_mol and (int(n_nodes.min()) < 0 or int(n_edges.min()) < 0)):
+        raise ValueError("slices must start at 0 and not decrease")
+    if ei.size:     # the largest atom id of each molecule's edges against its atom count (molecules without edges: none)
+        has = n_edges > 0
+        top = np.maximum.reduceat(ei.max(0), es[:-1][has])
+        if int(ei.min()) < 0 or bool((top >= n_nodes[has]).any()):
             raise ValueError("edge_index is not local to its molecule")
-    return GraphStore(mols)
+    # the structure of arrays as the file holds it: no per-molecule objects (a pcqm_g file has millions of molecules)
+    return GraphStore.from_arrays(n_nodes, n_edges, x, ei[0], ei[1], ea, y)

@@ -331,6 +331,29 @@ typedef struct {
 } HbCollate;
 int hb_collate(const HbCollate* args);
 
+/* hb_collate's counterpart for 2-D molecular graphs (batch.GraphStore; PyG Data(x, edge_index, edge_attr, y) as the reference's
+ * *_g datasets hold them): atom rows x [., 9] int64, directed edges src / dst (atom ids LOCAL to their molecule, shifted here by
+ * the atoms of the molecules before) with edge_attr [., F] int64, y per molecule.  out_edge_index is [2, PE] row-major: row 0
+ * sources, row 1 targets.  padded != 0: outputs have PN / PE rows and B + 1 molecules, padded exactly as batch.pad_graph_batch
+ * does: padded atoms have x = 0 and molecule id B, padded edge k runs from atom N + k % (PN - N) to N + (k + 1) % (PN - N) with
+ * edge_attr 0 (a ring over the padded atoms; self-loops when there is one), y[B] = 0; PN > N, PE >= E required.
+ * out_counts[2] = N, E of the real molecules.  Host code: no stream, no allocation. */
+typedef struct {
+    int64_t B, n_mols;
+    const int64_t* idx;
+    const int64_t *node_off, *edge_off;
+    const int64_t* x;
+    const int64_t *src, *dst, *edge_attr;
+    int64_t F;
+    const float* y;
+    int64_t PN, PE;
+    int32_t padded;
+    int64_t *out_x, *out_edge_index, *out_edge_attr, *out_batch;
+    float* out_y;
+    int64_t* out_counts;
+} GbCollate;
+int gb_collate(const GbCollate* args);
+
 /* Measurement aid (bench.py, not used by the models): eqh_stamp stores the device's constant-rate wall clock into
  * *slot (uint64, device memory) from a one-thread kernel on `stream` -- capturable, so two stamps around a launch
  * time it INSIDE a replayed hipGraph; eqh_wall_clock_khz is that clock's rate. */
