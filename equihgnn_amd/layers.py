@@ -114,8 +114,14 @@ class MLP(nn.Module):
         """Whether forward(x, first=...) uses a precomputed first GEMM (hidden layers on the fused path)."""
         return len(self.lins) > 1 and not self.InputNorm and self._fusable(x)
 
+    @property
+    def drop_p(self) -> float:
+        """The dropout probability in effect (mlp.py:97): 0 in eval mode."""
+        return float(self.dropout) if (self.training and self.dropout > 0) else 0.0
+
     def _fusable(self, x):
-        return (x.is_cuda and x.dim() == 2 and not (self.training and self.dropout > 0)
+        # (an active dropout rides the fused kernels -- ops.FUSED_DROPOUT -- or sends the MLP down hidden())
+        return (x.is_cuda and x.dim() == 2 and (self.drop_p == 0.0 or ops.FUSED_DROPOUT)
                 and all(isinstance(n, nn.LayerNorm) for n in self.normalizations[1:])
                 and all(l.out_features % 4 == 0 and l.out_features <= 1024 for l in self.lins[:-1]))
 
@@ -126,12 +132,12 @@ class MLP(nn.Module):
         if len(self.lins) == 1:
             return ops.linear(x, self.lins[0].weight, self.lins[0].bias)
         if self._fusable(x):
-            # bias-free GEMM, then bias + ReLU + LayerNorm in one launch (its backward also yields
-            # the bias gradient, so no separate column-sum kernel runs)
+            # bias-free GEMM, then bias + ReLU + LayerNorm (+ dropout: one seed per hidden layer, in layer order) in one
+            # launch (its backward also yields the bias gradient, so no separate column-sum kernel runs)
             for i in range(len(self.lins) - 1):
                 lin, norm = self.lins[i], self.normalizations[i + 1]
                 h = first if (i == 0 and first is not None) else ops.linear(x, lin.weight)
-                x = ops.bias_relu_ln(h, lin.bias, norm.weight, norm.bias, norm.eps)
+                x = ops.bias_relu_ln(h, lin.bias, norm.weight, norm.bias, norm.eps, p=self.drop_p)
             return ops.linear(x, self.lins[-1].weight, self.lins[-1].bias)
         h = self.hidden(ops.linear(x, self.lins[0].weight, self.lins[0].bias), 0, mask)
         return ops.linear(h, self.lins[-1].weight, self.lins[-1].bias)
@@ -167,12 +173,13 @@ def _pair_message(mlp: MLP, a, b, idx_a32, idx_b32, csr_a, csr_b, out_csr, out_k
     qb = ops.linear(b, lin0.weight, lin0.bias, (ca, cin))       # rows of b
     norm = mlp.normalizations[1] if len(mlp.lins) > 1 else None
     fused = (len(mlp.lins) == 2 and isinstance(norm, nn.LayerNorm) and pa.dim() == 2
-             and pa.shape[-1] % 4 == 0 and pa.shape[-1] <= 1024 and not (mlp.training and mlp.dropout > 0))
+             and pa.shape[-1] % 4 == 0 and pa.shape[-1] <= 1024
+             and (mlp.drop_p == 0.0 or (ops.FUSED_DROPOUT and pa.is_cuda)))
     last = mlp.lins[-1]
     if fused:
         # gather + gather + add + ReLU + LayerNorm + segmented reduce in ONE kernel (incidence.hip)
         s = ops.incidence_ln_reduce(pa, qb, norm.weight, norm.bias, idx_a32, idx_b32, csr_a, csr_b,
-                                    out_csr, out_key32, aggr, norm.eps)
+                                    out_csr, out_key32, aggr, norm.eps, p=mlp.drop_p)
         if residual is not None:   # (scale, c): scale * last(s) + c, c already holds the scaled bias
             return ops.linear_add(s, last.weight, residual[1], residual[0])
         return torch.addcmul(ops.linear(s, last.weight), _row_weight(out_csr, has_row, aggr, s.dtype), last.bias)
@@ -355,13 +362,16 @@ class MHNNSConv(nn.Module):
         W1, W2, W3 = self.W1, self.W2, self.W3
         h1, pa = ops.linear2(X, W1.lins[0].weight, None, W2.lins[0].weight, (0, c))
         n1, n2, n3 = W1.normalizations[1], W2.normalizations[1], W3.normalizations[1]
-        # W1's hidden layer + the mean over the hyperedge's nodes (conv.py:172-173) in one launch each way
-        hbar = ops.gather_ln_reduce(h1, W1.lins[0].bias, n1.weight, n1.bias, ix.by_e, ix.by_v, "mean", n1.eps)
+        # W1's hidden layer + the mean over the hyperedge's nodes (conv.py:172-173) in one launch each way.  Training
+        # dropout (mlp.py:97) sits behind each MLP's LayerNorm, i.e. in front of its last Linear, so the merged products
+        # hold; the three sites draw their seeds in the order W1, W2, W3
+        hbar = ops.gather_ln_reduce(h1, W1.lins[0].bias, n1.weight, n1.bias, ix.by_e, ix.by_v, "mean", n1.eps, p=W1.drop_p)
         qb = ops.linear(hbar, m["w12"], m["b12"])
         s = ops.incidence_ln_reduce(pa, qb, n2.weight, n2.bias, ix.v32, ix.e32, ix.by_v, ix.by_e, ix.by_v, ix.v32,
-                                    "mean", n2.eps)                                            # conv.py:175-177
+                                    "mean", n2.eps, p=W2.drop_p)                               # conv.py:175-177
         # conv.py:179-180 + W3's first Linear and hidden layer: scale * (s Wd^T) + cw + bias -> ReLU -> LayerNorm
-        x = ops.linear_add_relu_ln(s, m["w23"], m["cw"], m["scale"], W3.lins[0].bias, n3.weight, n3.bias, n3.eps, fan=m["fan"])
+        x = ops.linear_add_relu_ln(s, m["w23"], m["cw"], m["scale"], W3.lins[0].bias, n3.weight, n3.bias, n3.eps, fan=m["fan"],
+                                   p=W3.drop_p)
         return ops.linear(x, W3.lins[1].weight, W3.lins[1].bias, relu=relu_out)
 
     def stack_supported(self, X, residual) -> bool:

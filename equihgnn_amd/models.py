@@ -87,6 +87,27 @@ class _Wrapper(nn.Module):
     def _embeds(self):
         return self.front is None or self.front.embeds
 
+    # -- training dropout (--dropout, main.py:202) -------------------------------------------------------------------
+    # With ops.FUSED_DROPOUT the tail's dropout sites take their keep decisions from the hash of (seed, element index)
+    # (csrc/drop_hash.h) and their seeds, one per site, from one pool of 64 draws per forward pass, in this FIXED order:
+    #   per application of a conv layer: the wrapper's input dropout(s) (x, then e), then the layer's MLPs W1, W2, W3 (W4),
+    #   one seed per hidden layer of each; after the applications the dropout in front of the pool (the paired / M tails
+    #   draw theirs, x then e, after each application instead: mhnn.py:208-214), then the head's hidden layers.
+    @property
+    def _drop_p(self) -> float:
+        return float(self.dropout.p) if (self.training and self.dropout.p > 0) else 0.0
+
+    def _dropout_scope(self, x):
+        """The seed pool around the tail (it nests with FAFormer's own: the outermost block draws)."""
+        return ops.dropout_seeds(x.device, 64, enabled=x.is_cuda and self._drop_p > 0 and ops.FUSED_DROPOUT)
+
+    def _drop(self, x):
+        """self.dropout(x) (equihnn_egnn.py:162-166, mhnn.py:208-214) on rows: one pass, no mask tensor."""
+        p = self._drop_p
+        if p > 0 and ops.FUSED_DROPOUT and x.is_cuda and ops.dropout_add_supported(x, None):
+            return ops.dropout_add(x, None, p)
+        return self.dropout(x)
+
     def _build_front(self, args):
         if self.front is not None:
             setattr(self, self.front.attr, self.front.build(args))
@@ -114,7 +135,9 @@ def _conv_layers(model, x, index, x0, res, fuse_act, taps):
     if model.nlayer >= 1 and fuse_act and taps is None and drop_off and model.conv.stack_supported(x, res):
         return model.conv.forward_stack(x, index, res, model.nlayer, relu_out=True)
     for i in range(model.nlayer):
-        x = model.conv(model.dropout(x), index, x0, res, relu_out=fuse_act)
+        if i == 0 and isinstance(res, dict) and x is res["x0"] and model._drop_p > 0:
+            x = res["x0_pass"]      # x0 reaches the first application through the residual's autograd node (one route for its gradient)
+        x = model.conv(model._drop(x), index, x0, res, relu_out=fuse_act)
         if taps is not None:
             taps[f"conv{i}"] = x
         if not fuse_act:
@@ -144,10 +167,11 @@ class _STail(_Wrapper):
         index = HyperIndex.from_batch(data)
         x = self._apply_front(data, index, taps)
         x0 = x
-        res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
-        fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
-        x = _conv_layers(self, x, index, x0, res, fuse_act, taps)
-        return readout(self.mlp_out, self.dropout(x), index, taps, head)
+        with self._dropout_scope(x):
+            res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
+            fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
+            x = _conv_layers(self, x, index, x0, res, fuse_act, taps)
+            return readout(self.mlp_out, self._drop(x), index, taps, head)
 
 
 class _PairedBase(_Wrapper):
@@ -175,16 +199,17 @@ class _PairedBase(_Wrapper):
         index = HyperIndex.from_batch(data)
         x = self._apply_front(data, index, taps)
         e = self.bond_encoder(data.edge_attr)
-        with _merged_scope([self.conv], x, e):      # the shared layer's weight-level products once per step
-            for i in range(self.nlayer):
-                x, e = self.conv(x, e, index)
-                if i != self.nlayer - 1:
-                    x, e = self.act(x), self.act(e)
-                x, e = self.dropout(x), self.dropout(e)
-        both = self._pool(x, e, index, data)
-        if taps is not None:
-            taps["pool"] = both
-        return head_loss(self.mlp_out(both, mask=index.pad_masks()[3]).view(-1), head)
+        with self._dropout_scope(x):
+            with _merged_scope([self.conv], x, e):      # the shared layer's weight-level products once per step
+                for i in range(self.nlayer):
+                    x, e = self.conv(x, e, index)
+                    if i != self.nlayer - 1:
+                        x, e = self.act(x), self.act(e)
+                    x, e = self._drop(x), self._drop(e)
+            both = self._pool(x, e, index, data)
+            if taps is not None:
+                taps["pool"] = both
+            return head_loss(self.mlp_out(both, mask=index.pad_masks()[3]).view(-1), head)
 
     fused_pool = False   # the read-out as ONE launch each way (ops.pool_pair) instead of mask, product, two reduces and a cat
 
@@ -230,18 +255,19 @@ class _MTail(_Wrapper):
         x = self._apply_front(data, index, taps)
         e = self.bond_encoder(data.edge_attr)
         mask = real_row_mask(data, x)   # padded batch: BatchNorm statistics over the real atoms only
-        with _merged_scope(self.layers, x, e) if self.merged_layers else contextlib.nullcontext():
-            for i, layer in enumerate(self.layers):
-                x, e = layer(x, e, index)
-                # (the ReLU behind the normalisation rides its launches, unless the pre-activation value is tapped)
-                fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
-                x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
-                if taps is not None:
-                    taps[f"bn{i}"] = x
-                if i != self.nlayer - 1:  # no activation after the last layer, mhnn.py:208-214
-                    x, e = (x if fuse else self.act(x)), self.act(e)
-                x, e = self.dropout(x), self.dropout(e)
-        return readout(self.mlp_out, x, index, taps, head)
+        with self._dropout_scope(x):
+            with _merged_scope(self.layers, x, e) if self.merged_layers else contextlib.nullcontext():
+                for i, layer in enumerate(self.layers):
+                    x, e = layer(x, e, index)
+                    # (the ReLU behind the normalisation rides its launches, unless the pre-activation value is tapped)
+                    fuse = taps is None and i != self.nlayer - 1 and isinstance(self.act, nn.ReLU)
+                    x = batch_norm_rows(self.batch_norms[i], x, mask, relu=fuse)
+                    if taps is not None:
+                        taps[f"bn{i}"] = x
+                    if i != self.nlayer - 1:  # no activation after the last layer, mhnn.py:208-214
+                        x, e = (x if fuse else self.act(x)), self.act(e)
+                    x, e = self._drop(x), self._drop(e)
+            return readout(self.mlp_out, x, index, taps, head)
 
 
 @registry.register_model("mhnns")

@@ -12,7 +12,8 @@ One module per subsystem; everything is re-exported here, so cal
   products x6 GEMM, fp32-MFMA dense batch, dispatch against the library, weight-level small products
   grads    persistent gradient accumulators, deferred weight / bias gradients and slab reductions, gradient fan-in
   linears  nn.Linear-shaped autograd nodes, merged consecutive Linears, matmul fans
-  rows     per-incidence hidden layer + reduce, bias/ReLU/LayerNorm rows, BatchNorm / LayerNorm rows, residual mix
+  rows     per-incidence hidden layer + reduce, bias/ReLU/LayerNorm rows (with their training-dropout forms), BatchNorm /
+           LayerNorm rows, residual mix
   egnn     EGNN edge kernels, feature node, weight packing
   readout  pooled readout head + MSE in one launch, paired node / hyperedge pool
   se3      Equiformer: row GEMMs, radial trunk, attention pooling, RMS norm, edge geometry
@@ -63,7 +64,8 @@ from . import mhnn_panel  # noqa: F401
 from .rows import (  # noqa: F401
     _IncidenceLnReduce, _BiasReluLn, _LinearAddReluLn, linear_add_relu_ln, _GatherLnReduce, gather_ln_reduce,
     _BatchNormRows, batch_norm_rows, batch_norm_rows_supported, _LayerNormRows, incidence_ln_reduce, bias_relu_ln,
-    _ResidualMix, residual_mix, layer_norm_rows,
+    _ResidualMix, residual_mix, layer_norm_rows, FUSED_DROPOUT, _IncidenceLnReduceDrop, _BiasReluLnDrop, _LinearAddReluLnDrop,
+    _GatherLnReduceDrop,
 )
 from .egnn import (  # noqa: F401
     _EgnnEdge, _EgnnFeats, egnn_feats, _EgnnPackWeights, egnn_pack_weights, egnn_edge, _EgnnNodeMlp, egnn_node_mlp,
@@ -99,6 +101,7 @@ from .visnet import (  # noqa: F401
 # switches that tests / tools / bench.py set as ``ops.NAME = value``: owner module of each
 _SWITCH_OWNER = {
     "DEFER_WGRAD": "grads",
+    "FUSED_DROPOUT": "rows",
     "GEMM_TILE": "products",
     "KNN_GRID_MIN_POINTS": "aggregate",
     "TIMELINE": "_base",

@@ -662,6 +662,59 @@ int hg_gather_ln_reduce_bwd(const float* h, const float* bias, const float* gamm
                             int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The three hidden-layer kernels above with the training dropout of mlp.py:97 behind the LayerNorm (csrc/conv_dropout.hip):
+ *   keep = 0 or 1 / (1 - p), decided by the hash of (*seed, element index) of csrc/drop_hash.h, as in the faf_* entries:
+ *   seed is a DEVICE pointer (a new value per hipGraph replay), 0 <= p < 1 (else EQH_ERR_ARG), the realised drop
+ *   probability is round(p 2^16) / 2^16.  No mask is stored: every backward recomputes the decisions from the same seed.
+ * The element index is the flat index of the tensor F.dropout would have been applied to, so the keep matrix is what
+ * faf_dropout_add gives on a tensor of ones of that shape with the same seed:
+ *   hg_bias_relu_ln_drop_*       out[r] = keep . LN(relu(h_scale h[r] + pre_add[r] + bias))           index r C + c
+ *                                (the _ex form: pre_add may be NULL with h_scale 1; acc_out / acc_first as _bwd_ex);
+ *                                bwd: dy is multiplied by keep ahead of the LayerNorm backward, dgamma / dbeta use that dy
+ *   hg_gather_ln_reduce_drop_*   out[r] = reduce_{q in row r} keep[src] . LN(relu(h[src] + bias)), src = col[q]:
+ *                                the decision belongs to the SOURCE row                                 index src C + c
+ *                                (= dropout of the [rows of h, C] hidden tensor, then the gathered reduction)
+ *   hg_incidence_ln_reduce_drop_* out[r] = reduce_{q in row r} keep[p] . LN(relu(pa[ia[p]] + qb[ib[p]])): the decision
+ *                                belongs to the INCIDENCE, p = its position in ia / ib                  index p C + c
+ *                                (so the (rowptr, col) forward also takes the output CSR's perm); the backward produces
+ *                                dbeta itself (workspace: [dgamma | dbeta] per workgroup) -- with a mask between beta and
+ *                                the sum it is no longer a column sum of ds.
+ * Everything else (shapes, CSRs, mean, workspaces from the *_workspace_bytes queries, accumulate, error codes, no
+ * allocation) is as for the entries without _drop.
+ * ------------------------------------------------------------------------------------------- */
+int hg_bias_relu_ln_drop_fwd(const float* h, float h_scale, const float* pre_add, const float* bias, const float* gamma,
+                             const float* beta, int64_t n_rows, int32_t C, float eps, float p, const int64_t* seed,
+                             float* out, void* stream);
+size_t hg_bias_relu_ln_drop_bwd_workspace_bytes(int64_t n_rows, int32_t C);
+int hg_bias_relu_ln_drop_bwd(const float* h, float h_scale, const float* pre_add, const float* bias, const float* gamma,
+                             const float* dy, int64_t n_rows, int32_t C, float eps, float p, const int64_t* seed, float* dh,
+                             float* dbias, float* dgamma, float* dbeta, int32_t accumulate, void* workspace,
+                             size_t workspace_bytes, float* acc_out, int32_t acc_first, void* stream);
+int hg_gather_ln_reduce_drop_fwd(const float* h, const float* bias, const float* gamma, const float* beta,
+                                 const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t C, int32_t mean,
+                                 float eps, float p, const int64_t* seed, float* out, void* stream);
+size_t hg_gather_ln_reduce_drop_bwd_workspace_bytes(int64_t n_src_rows, int32_t C);
+int hg_gather_ln_reduce_drop_bwd(const float* h, const float* bias, const float* gamma, const float* dout,
+                                 const int32_t* t_rowptr, const int32_t* t_col, const float* t_w, int64_t n_src_rows,
+                                 int32_t C, float eps, float p, const int64_t* seed, float* dh, float* dbias, float* dgamma,
+                                 float* dbeta, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int hg_incidence_ln_reduce_drop_fwd(const float* pa, const float* qb, const int32_t* ia, const int32_t* ib,
+                                    const int32_t* rowptr, const int32_t* perm, const float* gamma, const float* beta,
+                                    int64_t n_rows, int32_t C, int32_t mean, float eps, float p, const int64_t* seed,
+                                    float* out, void* stream);
+int hg_incidence_ln_reduce_drop_fwd_col(const float* pa, const float* qb, const int32_t* rowptr, const int32_t* col,
+                                        const int32_t* perm, int32_t row_is_a, const float* gamma, const float* beta,
+                                        int64_t n_rows, int32_t C, int32_t mean, float eps, float p, const int64_t* seed,
+                                        float* out, void* stream);
+size_t hg_incidence_ln_reduce_drop_bwd_workspace_bytes(int64_t n_a_rows, int32_t C);
+int hg_incidence_ln_reduce_drop_bwd(const float* pa, const float* qb, const int32_t* ia, const int32_t* ib,
+                                    const int32_t* a_rowptr, const int32_t* a_perm, int64_t n_a_rows,
+                                    const int32_t* b_rowptr, const int32_t* b_perm, int64_t n_b_rows, const int32_t* okey,
+                                    const int32_t* orowptr, const float* ds, const float* gamma, int32_t C, int32_t mean,
+                                    float eps, float p, const int64_t* seed, float* dpa, float* dqb, float* dgamma,
+                                    float* dbeta, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training-mode nn.BatchNorm1d over node rows (mhnn.py:182,206; equihnn_egnn.py egnn_equihnnm) whose batch statistics
  * count only the rows with row_mask[i] > 0 (NULL: all rows) -- the real atoms of a padded static-shape batch:
  *   y = (x - mean) * rstd * gamma + beta,  mean / var over the masked rows (biased var for the output, unbiased into
