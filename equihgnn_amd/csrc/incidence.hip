@@ -15,6 +15,18 @@
 // over the CSR keyed by `ia` (giving dPA) and once over the CSR keyed by `ib` (giving dQB) — so
 // that each gradient row is owned by one wavefront; d gamma is accumulated per workgroup into a
 // slab reduced in block order (bitwise reproducible).
+//
+// Every hidden-layer kernel here is ONE body templated on DROP: the training dropout of mlp.py:97 behind the LayerNorm
+// (rowln.h: LnArgs, Keep).  The decision of an element is the hash of the flat index of the tensor F.dropout would have
+// been applied to, so the decisions are those of faf_dropout_add on that tensor:
+//   dense rows       out[r]  = keep[r] . LN(relu(h_scale h[r] + pre_add[r] + bias))                      element r C + c
+//   gathered reduce  out[r]  = reduce_{q in row r} keep[src] . LN(relu(h[src] + bias)),  src = col[q]    element src C + c
+//   per incidence    out[r]  = reduce_{q in row r} keep[p] . LN(relu(pa[ia[p]] + qb[ib[p]])), p = perm[q] element p C + c
+// With a mask between beta and the sum, beta no longer factors out of the reduction (its term is beta * sum keep): the
+// DROP forwards accumulate keep * fma(gamma, xhat, beta) per entry, and the per-incidence backward produces d beta itself
+// (slab row next to d gamma's) instead of leaving it to a column sum of the output gradient.
+// The p = 0 statements are left as they were written wherever a shared helper would change the DROP = false instruction
+// stream: those instantiations are the training step's kernels, and their code is compared against the previous build.
 #include "common.h"
 #include "rowln.h"
 
@@ -44,14 +56,21 @@ __device__ __forceinline__ void load_norm(const float* __restrict__ pa, const fl
     norm_pair<NV>(u, w, C, lane, inv_c, eps, x, pos, rstd);
 }
 
-template <int NV>
+template <int NV, bool DROP>
 __global__ void __launch_bounds__(THREADS)
 k_inc_fwd(const float* __restrict__ pa, const float* __restrict__ qb, const int* __restrict__ ia,
           const int* __restrict__ ib, const int* __restrict__ rowptr, const int* __restrict__ perm,
           const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ out,
-          int n_rows, int C, int mean, float eps) {
+          int n_rows, int C, int mean, LnArgs<DROP> ln) {
+    const Keep<DROP> kp(ln);
+    const float eps = ln.eps;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv_c = 1.0f / (float)C;
+    Row<NV> gam, bet;       // DROP: applied per entry
+    if constexpr (DROP) {
+        load_row<NV>(gamma, 0, C, lane, gam);
+        load_row<NV>(beta, 0, C, lane, bet);
+    }
     for (int r = blockIdx.x * WAVES + wave; r < n_rows; r += gridDim.x * WAVES) {
         const int beg = rowptr[r], end = rowptr[r + 1];
         Row<NV> acc;
@@ -60,20 +79,29 @@ k_inc_fwd(const float* __restrict__ pa, const float* __restrict__ qb, const int*
         for (int q0 = beg; q0 < end; q0 += 64) {
             // the row's incidence ids and operand rows: one coalesced load each, then broadcast
             const int cnt = (end - q0 < 64) ? (end - q0) : 64;
-            int my_a = 0, my_b = 0;
+            int my_a = 0, my_b = 0, my_p = 0;
             if (lane < cnt) {
                 const int p = perm[q0 + lane];
                 my_a = ia[p];
                 my_b = ib[p];
+                if constexpr (DROP) my_p = p;
             }
             for (int j = 0; j < cnt; ++j) {
                 Row<NV> x;
                 unsigned pos;
                 float rstd;
                 load_norm<NV>(pa, qb, __shfl(my_a, j, 64), __shfl(my_b, j, 64), C, lane, inv_c, eps, x, pos, &rstd);
+                if constexpr (DROP) {
+                    add_kept<NV>(kp, __shfl(my_p, j, 64), C, lane, x, gam, bet, acc);
+                } else {
 #pragma unroll
-                for (int i = 0; i < NV; ++i) f4_add(acc.v[i], x.v[i]);
+                    for (int i = 0; i < NV; ++i) f4_add(acc.v[i], x.v[i]);
+                }
             }
+        }
+        if constexpr (DROP) {
+            store_reduced<NV>(out, r, C, lane, acc, end - beg, mean);
+            continue;
         }
         const int deg = end - beg;
         const float den = (mean && deg > 1) ? (float)deg : 1.0f;
@@ -98,12 +126,15 @@ k_inc_fwd(const float* __restrict__ pa, const float* __restrict__ qb, const int*
 // The same sum when the OUTPUT row is one of the two operands' indices (always the case in conv.py: messages are
 // reduced over the hyperedges or over the nodes of the incidences): row r's own operand row is r itself and the other
 // operand's row is the CSR's `col` entry, so the chain rowptr -> perm -> (ia, ib) -> rows shortens to rowptr -> col ->
-// rows, and the rows of incidence j+1 are gathered while incidence j is normalised.
-template <int NV>
+// rows, and the rows of incidence j+1 are gathered while incidence j is normalised.  DROP: the decision belongs to the
+// incidence, i.e. to its position in ia / ib, which ln.perm gives for the entries of (rowptr, col).
+template <int NV, bool DROP>
 __global__ void __launch_bounds__(THREADS)
 k_inc_fwd_col(const float* __restrict__ pa, const float* __restrict__ qb, const int* __restrict__ rowptr,
               const int* __restrict__ col, int row_is_a, const float* __restrict__ gamma, const float* __restrict__ beta,
-              float* __restrict__ out, int n_rows, int C, int mean, float eps) {
+              float* __restrict__ out, int n_rows, int C, int mean, LnArgs<DROP> ln) {
+    const Keep<DROP> kp(ln);
+    const float eps = ln.eps;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv_c = 1.0f / (float)C;
     const float* __restrict__ own = row_is_a ? pa : qb;      // the operand indexed by the output row
@@ -115,7 +146,7 @@ k_inc_fwd_col(const float* __restrict__ pa, const float* __restrict__ qb, const 
         gam.v[i] = (c < C) ? *reinterpret_cast<const float4*>(gamma + c) : f4_zero();
         bet.v[i] = (c < C) ? *reinterpret_cast<const float4*>(beta + c) : f4_zero();
     }
-    auto fetch = [&](const float* __restrict__ base, int o, Row<NV>& u) {
+    auto fetch = [&](const float* __restrict__ base, int o, Row<NV>& u) {    // (row.h's load_row here moves the p = 0 stream)
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = (lane + 64 * i) * 4;
@@ -128,7 +159,7 @@ k_inc_fwd_col(const float* __restrict__ pa, const float* __restrict__ qb, const 
         fetch(own, r, mine);                                 // once per row (it does not wait for the index chain)
 #pragma unroll
         for (int i = 0; i < NV; ++i) acc.v[i] = f4_zero();
-        auto add_norm = [&](const Row<NV>& w) {
+        auto add_norm = [&](const Row<NV>& w, int p) {      // p: the incidence's position (DROP)
 #if defined(INC_ABLATE) && INC_ABLATE >= 1      // diagnostic build (tools/inc_ablation.py): the rows are gathered, the LayerNorm is not
 #pragma unroll
             for (int i = 0; i < NV; ++i) { f4_add(acc.v[i], mine.v[i]); f4_add(acc.v[i], w.v[i]); }
@@ -138,12 +169,18 @@ k_inc_fwd_col(const float* __restrict__ pa, const float* __restrict__ qb, const 
             unsigned pos;
             float rstd;
             norm_pair<NV>(mine, w, C, lane, inv_c, eps, x, pos, &rstd);
+            if constexpr (DROP) {
+                add_kept<NV>(kp, p, C, lane, x, gam, bet, acc);
+            } else {
 #pragma unroll
-            for (int i = 0; i < NV; ++i) f4_add(acc.v[i], x.v[i]);
+                for (int i = 0; i < NV; ++i) f4_add(acc.v[i], x.v[i]);
+            }
         };
         for (int q0 = beg; q0 < end; q0 += 64) {
             const int cnt = (end - q0 < 64) ? (end - q0) : 64;
             const int my_o = (lane < cnt) ? col[q0 + lane] : 0;
+            int my_p = 0;
+            if constexpr (DROP) my_p = (lane < cnt) ? ln.perm[q0 + lane] : 0;
 #if defined(INC_ABLATE) && INC_ABLATE >= 2      // ... and not even gathered: index chain (rowptr -> col) + own row + store only
             acc.v[0].x += (float)my_o;
             continue;
@@ -155,11 +192,15 @@ k_inc_fwd_col(const float* __restrict__ pa, const float* __restrict__ qb, const 
                 fetch(oth, __builtin_amdgcn_readlane(my_o, (j + 1 < cnt) ? j + 1 : last), w1);
                 fetch(oth, __builtin_amdgcn_readlane(my_o, (j + 2 < cnt) ? j + 2 : last), w2);
                 fetch(oth, __builtin_amdgcn_readlane(my_o, (j + 3 < cnt) ? j + 3 : last), w3);
-                add_norm(w0);
-                if (j + 1 < cnt) add_norm(w1);
-                if (j + 2 < cnt) add_norm(w2);
-                if (j + 3 < cnt) add_norm(w3);
+                add_norm(w0, __builtin_amdgcn_readlane(my_p, j));
+                if (j + 1 < cnt) add_norm(w1, __builtin_amdgcn_readlane(my_p, j + 1));
+                if (j + 2 < cnt) add_norm(w2, __builtin_amdgcn_readlane(my_p, j + 2));
+                if (j + 3 < cnt) add_norm(w3, __builtin_amdgcn_readlane(my_p, j + 3));
             }
+        }
+        if constexpr (DROP) {
+            store_reduced<NV>(out, r, C, lane, acc, end - beg, mean);
+            continue;
         }
         const int deg = end - beg;
         const float den = (mean && deg > 1) ? (float)deg : 1.0f;
@@ -183,12 +224,15 @@ k_inc_fwd_col(const float* __restrict__ pa, const float* __restrict__ qb, const 
 // ONE gathered operand: out[r] = gamma * reduce_{q in row r} xhat(relu(h[col[q]] + bias)) + beta * [..] -- a dense-row hidden
 // layer (Linear -> ReLU -> LayerNorm, mlp.py:91-99) whose output is only ever consumed through the gathered reduction
 // that follows it (conv.py:172-173: scatter(W1(X)[vertex], edges) after moving W1's last Linear behind the mean).
-// The [N, C] normalised tensor is never written: k_rowln_fwd + k_segment_reduce in one launch.
-template <int NV>
+// The [N, C] normalised tensor is never written: k_rowln_fwd + k_segment_reduce in one launch.  DROP: the decision belongs
+// to the SOURCE row (dropout of the [N, C] tensor, then the reduction).
+template <int NV, bool DROP>
 __global__ void __launch_bounds__(THREADS)
 k_gather_ln_fwd(const float* __restrict__ h, const float* __restrict__ bias, const int* __restrict__ rowptr,
                 const int* __restrict__ col, const float* __restrict__ gamma, const float* __restrict__ beta,
-                float* __restrict__ out, int n_rows, int C, int mean, float eps) {
+                float* __restrict__ out, int n_rows, int C, int mean, LnArgs<DROP> ln) {
+    const Keep<DROP> kp(ln);
+    const float eps = ln.eps;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv_c = 1.0f / (float)C;
     Row<NV> bias_row, gam, bet;
@@ -199,7 +243,7 @@ k_gather_ln_fwd(const float* __restrict__ h, const float* __restrict__ bias, con
         gam.v[i] = (c < C) ? *reinterpret_cast<const float4*>(gamma + c) : f4_zero();
         bet.v[i] = (c < C) ? *reinterpret_cast<const float4*>(beta + c) : f4_zero();
     }
-    auto fetch = [&](int o, Row<NV>& u) {
+    auto fetch = [&](int o, Row<NV>& u) {       // (row.h's load_row here moves the p = 0 stream)
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = (lane + 64 * i) * 4;
@@ -211,13 +255,17 @@ k_gather_ln_fwd(const float* __restrict__ h, const float* __restrict__ bias, con
         Row<NV> acc;
 #pragma unroll
         for (int i = 0; i < NV; ++i) acc.v[i] = f4_zero();
-        auto add_norm = [&](const Row<NV>& u) {
+        auto add_norm = [&](const Row<NV>& u, int o) {         // o: the source row (DROP)
             Row<NV> x;
             unsigned pos;
             float rstd;
             norm_pair<NV>(u, bias_row, C, lane, inv_c, eps, x, pos, &rstd);
+            if constexpr (DROP) {
+                add_kept<NV>(kp, o, C, lane, x, gam, bet, acc);
+            } else {
 #pragma unroll
-            for (int i = 0; i < NV; ++i) f4_add(acc.v[i], x.v[i]);
+                for (int i = 0; i < NV; ++i) f4_add(acc.v[i], x.v[i]);
+            }
         };
         for (int q0 = beg; q0 < end; q0 += 64) {
             const int cnt = (end - q0 < 64) ? (end - q0) : 64;
@@ -231,11 +279,15 @@ k_gather_ln_fwd(const float* __restrict__ h, const float* __restrict__ bias, con
                 fetch(__builtin_amdgcn_readlane(my_o, (j + 1 < cnt) ? j + 1 : last), u1);
                 fetch(__builtin_amdgcn_readlane(my_o, (j + 2 < cnt) ? j + 2 : last), u2);
                 fetch(__builtin_amdgcn_readlane(my_o, (j + 3 < cnt) ? j + 3 : last), u3);
-                add_norm(u0);
-                if (j + 1 < cnt) add_norm(u1);
-                if (j + 2 < cnt) add_norm(u2);
-                if (j + 3 < cnt) add_norm(u3);
+                add_norm(u0, __builtin_amdgcn_readlane(my_o, j));
+                if (j + 1 < cnt) add_norm(u1, __builtin_amdgcn_readlane(my_o, j + 1));
+                if (j + 2 < cnt) add_norm(u2, __builtin_amdgcn_readlane(my_o, j + 2));
+                if (j + 3 < cnt) add_norm(u3, __builtin_amdgcn_readlane(my_o, j + 3));
             }
+        }
+        if constexpr (DROP) {
+            store_reduced<NV>(out, r, C, lane, acc, end - beg, mean);
+            continue;
         }
         const int deg = end - beg;
         const float den = (mean && deg > 1) ? (float)deg : 1.0f;
@@ -265,9 +317,11 @@ k_gather_ln_fwd(const float* __restrict__ h, const float* __restrict__ bias, con
 // consecutive rows: one chain fetches the metadata of up to 64 incidences at once (a lane each), the
 // operand rows of incidence j+1 are gathered while incidence j is normalised, and the per-row sums are
 // flushed when the (wavefront-uniform) row index changes.
-template <int NV, bool DGAMMA, bool SIDE_A>
+// DROP: the upstream gradient of incidence p is w . keep[p] . ds[okey[p]], and the side that accumulates d gamma also
+// accumulates d beta: slab [dgamma | dbeta] per workgroup.
+template <int NV, bool DGAMMA, bool SIDE_A, bool DROP>
 __device__ __forceinline__ void
-inc_bwd_body(const int block, float4* s_g, const float* __restrict__ pa, const float* __restrict__ qb,
+inc_bwd_body(const int block, float4* s_g, const Keep<DROP>& kp, const float* __restrict__ pa, const float* __restrict__ qb,
              const int* __restrict__ ia, const int* __restrict__ ib, const int* __restrict__ side_rowptr,
              const int* __restrict__ side_perm, const int* __restrict__ okey,
              const int* __restrict__ orowptr, const float* __restrict__ ds,
@@ -275,12 +329,13 @@ inc_bwd_body(const int block, float4* s_g, const float* __restrict__ pa, const f
              int n_side_rows, int C, int mean, float eps, int rows_per_wave) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv_c = 1.0f / (float)C;
-    Row<NV> gam, dgam;
+    Row<NV> gam, dgam, dbet;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = (lane + 64 * i) * 4;
         gam.v[i] = (c < C) ? *reinterpret_cast<const float4*>(gamma + c) : f4_zero();
         dgam.v[i] = f4_zero();
+        if constexpr (DROP) dbet.v[i] = f4_zero();
     }
     const int64_t s_beg64 = (int64_t)(block * WAVES + wave) * rows_per_wave;
     const int s_beg = (s_beg64 < n_side_rows) ? (int)s_beg64 : n_side_rows;
@@ -305,11 +360,13 @@ inc_bwd_body(const int block, float4* s_g, const float* __restrict__ pa, const f
             const int cnt = (p_end - q0 < 64) ? (p_end - q0) : 64;
             int my_a = 0, my_b = 0, my_r = 0;
             float my_w = 1.0f;
+            int my_p = 0;       // DROP: the incidence's position
             if (lane < cnt) {
                 const int p = side_perm[q0 + lane];
                 my_a = ia[p];
                 my_b = ib[p];
                 my_r = okey[p];
+                if constexpr (DROP) my_p = p;
                 const int deg = orowptr[my_r + 1] - orowptr[my_r];
                 my_w = (mean && deg > 1) ? 1.0f / (float)deg : 1.0f;
             }
@@ -349,8 +406,14 @@ inc_bwd_body(const int block, float4* s_g, const float* __restrict__ pa, const f
 #pragma unroll
                 for (int i = 0; i < NV; ++i) {
                     float4 d = draw.v[i];
-                    d.x *= w; d.y *= w; d.z *= w; d.w *= w;
+                    if constexpr (DROP) {   // (no Row of keep-scales beside g: declaring one moves the p = 0 stream)
+                        const float4 k = keep_group(kp, __builtin_amdgcn_readlane(my_p, j), C, lane, i);
+                        d.x *= w * k.x; d.y *= w * k.y; d.z *= w * k.z; d.w *= w * k.w;
+                    } else {
+                        d.x *= w; d.y *= w; d.z *= w; d.w *= w;
+                    }
                     if (DGAMMA) {
+                        if constexpr (DROP) f4_add(dbet.v[i], d);
                         dgam.v[i].x = fmaf(d.x, x.v[i].x, dgam.v[i].x); dgam.v[i].y = fmaf(d.y, x.v[i].y, dgam.v[i].y);
                         dgam.v[i].z = fmaf(d.z, x.v[i].z, dgam.v[i].z); dgam.v[i].w = fmaf(d.w, x.v[i].w, dgam.v[i].w);
                     }
@@ -377,6 +440,11 @@ inc_bwd_body(const int block, float4* s_g, const float* __restrict__ pa, const f
         flush_until(s_end);
     }
     if (DGAMMA) {
+        if constexpr (DROP) {
+            slab_store<NV, WAVES>(s_g, slab_dgamma + (int64_t)block * 2 * C, C, dgam);
+            slab_store<NV, WAVES>(s_g, slab_dgamma + ((int64_t)block * 2 + 1) * C, C, dbet);
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             s_g[threadIdx.x] = dgam.v[i];
@@ -398,11 +466,14 @@ inc_bwd_body(const int block, float4* s_g, const float* __restrict__ pa, const f
 // the bias gradient of the preceding Linear, d gamma and d beta (per-workgroup slabs, fixed order).
 // ------------------------------------------------------------------------------------------------
 // RELU: LayerNorm(relu(h + bias)) (mlp.py:91-99); !RELU: plain LayerNorm(h) (bias unused; egnn_layer.py:192)
-template <int NV, bool RELU>
+template <int NV, bool RELU, bool DROP = false>
 __global__ void __launch_bounds__(THREADS)
 k_rowln_fwd(const float* __restrict__ h, const float* __restrict__ bias, const float* __restrict__ gamma,
-            const float* __restrict__ beta, float* __restrict__ out, int n_rows, int C, float eps,
+            const float* __restrict__ beta, float* __restrict__ out, int n_rows, int C, LnArgs<DROP> ln,
             const float* __restrict__ pre_add = nullptr, float h_scale = 1.0f) {
+    static_assert(RELU || !DROP, "dropout exists only behind the hidden layer's ReLU + LayerNorm");
+    const Keep<DROP> kp(ln);
+    const float eps = ln.eps;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv_c = 1.0f / (float)C;
     Row<NV> bias_row;
@@ -426,6 +497,8 @@ k_rowln_fwd(const float* __restrict__ h, const float* __restrict__ bias, const f
             }
         }
         norm_pair<NV, RELU>(hr, bias_row, C, lane, inv_c, eps, x, pos, &rstd);
+        Row<NV> k;
+        if constexpr (DROP) keep_row<NV>(kp, r, C, lane, k);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = (lane + 64 * i) * 4;
@@ -435,6 +508,7 @@ k_rowln_fwd(const float* __restrict__ h, const float* __restrict__ bias, const f
                 float4 o;
                 o.x = fmaf(g.x, x.v[i].x, b.x); o.y = fmaf(g.y, x.v[i].y, b.y);
                 o.z = fmaf(g.z, x.v[i].z, b.z); o.w = fmaf(g.w, x.v[i].w, b.w);
+                if constexpr (DROP) { o.x *= k.v[i].x; o.y *= k.v[i].y; o.z *= k.v[i].z; o.w *= k.v[i].w; }
                 *reinterpret_cast<float4*>(out + (int64_t)r * C + c) = o;
             }
         }
@@ -444,31 +518,37 @@ k_rowln_fwd(const float* __restrict__ h, const float* __restrict__ bias, const f
 // both sides of the backward in ONE launch: workgroups [0, blocks_a) take the side keyed by ia (d pa and the
 // d gamma slabs), the rest the side keyed by ib (d qb).  The two sides are independent, so one launch saves a
 // kernel boundary and lets the shorter side's tail overlap the other.
-template <int NV>
+template <int NV, bool DROP>
 __global__ void __launch_bounds__(THREADS)
 k_inc_bwd_both(const float* __restrict__ pa, const float* __restrict__ qb, const int* __restrict__ ia,
                const int* __restrict__ ib, const int* __restrict__ a_rowptr, const int* __restrict__ a_perm,
                const int* __restrict__ b_rowptr, const int* __restrict__ b_perm, const int* __restrict__ okey,
                const int* __restrict__ orowptr, const float* __restrict__ ds, const float* __restrict__ gamma,
                float* __restrict__ dpa, float* __restrict__ dqb, float* __restrict__ slab_dgamma, int n_a_rows,
-               int n_b_rows, int blocks_a, int C, int mean, float eps, int rpw_a, int rpw_b) {
+               int n_b_rows, int blocks_a, int C, int mean, LnArgs<DROP> ln, int rpw_a, int rpw_b) {
     __shared__ float4 s_g[THREADS];
+    const Keep<DROP> kp(ln);
+    const float eps = ln.eps;
     if ((int)blockIdx.x < blocks_a)
-        inc_bwd_body<NV, true, true>((int)blockIdx.x, s_g, pa, qb, ia, ib, a_rowptr, a_perm, okey, orowptr, ds, gamma, dpa,
-                                     slab_dgamma, n_a_rows, C, mean, eps, rpw_a);
+        inc_bwd_body<NV, true, true, DROP>((int)blockIdx.x, s_g, kp, pa, qb, ia, ib, a_rowptr, a_perm, okey, orowptr, ds,
+                                           gamma, dpa, slab_dgamma, n_a_rows, C, mean, eps, rpw_a);
     else
-        inc_bwd_body<NV, false, false>((int)blockIdx.x - blocks_a, s_g, pa, qb, ia, ib, b_rowptr, b_perm, okey, orowptr,
-                                       ds, gamma, dqb, nullptr, n_b_rows, C, mean, eps, rpw_b);
+        inc_bwd_body<NV, false, false, DROP>((int)blockIdx.x - blocks_a, s_g, kp, pa, qb, ia, ib, b_rowptr, b_perm, okey,
+                                             orowptr, ds, gamma, dqb, nullptr, n_b_rows, C, mean, eps, rpw_b);
 }
 
-// slab layout per workgroup: [dbias | dgamma | dbeta], each C floats
-template <int NV, bool RELU>
+// slab layout per workgroup: [dbias | dgamma | dbeta], each C floats.  DROP: dy is masked ahead of the LayerNorm
+// backward, d gamma and d beta use that dy.
+template <int NV, bool RELU, bool DROP = false>
 __global__ void __launch_bounds__(THREADS)
 k_rowln_bwd(const float* __restrict__ h, const float* __restrict__ bias, const float* __restrict__ gamma,
             const float* __restrict__ dy, const float* __restrict__ add, float* __restrict__ dh,
-            float* __restrict__ slab, int n_rows, int C, float eps, int64_t dy_ld, float* __restrict__ acc_out = nullptr,
+            float* __restrict__ slab, int n_rows, int C, LnArgs<DROP> ln, int64_t dy_ld, float* __restrict__ acc_out = nullptr,
             int acc_first = 0, const float* __restrict__ pre_add = nullptr, float h_scale = 1.0f) {
+    static_assert(RELU || !DROP, "dropout exists only behind the hidden layer's ReLU + LayerNorm");
     __shared__ float4 s_red[THREADS];
+    const Keep<DROP> kp(ln);
+    const float eps = ln.eps;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv_c = 1.0f / (float)C;
     Row<NV> gam, a_db, a_dg, a_dbeta;
@@ -506,12 +586,16 @@ k_rowln_bwd(const float* __restrict__ h, const float* __restrict__ bias, const f
     };
     if (r < n_rows) fetch(r);
     for (; r < n_rows; r += stride) {
-        const Row<NV> ch = nh, cd = nd, ca = na;
+        const Row<NV> ch = nh, ca = na;
+        Row<NV> cd = nd;
         fetch(r + stride);
         Row<NV> x, g;
         unsigned pos;
         float rstd;
         norm_pair<NV, RELU>(ch, bias_row, C, lane, inv_c, eps, x, pos, &rstd);
+        if constexpr (DROP) mask_row<NV>(kp, r, C, lane, cd);
+        // the LayerNorm + ReLU backward, written out in each of the three backward kernels: as a shared function it
+        // moves every p = 0 stream (as does rowln.h's slab_store in place of the epilogues)
         float m1 = 0.f, m2 = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -546,7 +630,7 @@ k_rowln_bwd(const float* __restrict__ h, const float* __restrict__ bias, const f
             }
         }
     }
-    // combine the workgroup's four wavefronts in a fixed order, one slab row per quantity
+    // combine the workgroup's four wavefronts in a fixed order, one slab row per quantity (written out: see above)
     float* __restrict__ sl = slab + (int64_t)blockIdx.x * 3 * C;
 #pragma unroll
     for (int which = 0; which < 3; ++which) {
@@ -571,14 +655,17 @@ k_rowln_bwd(const float* __restrict__ h, const float* __restrict__ bias, const f
 // them.  w[q] = 1 / deg(col[q]) for the mean (hg_entry_weights), NULL for the sum.  A wavefront owns a range of
 // consecutive rows: one chain fetches the row ends and up to 64 entries of the range (a lane each), the next gathered row
 // and the next h row are in flight while the current ones are used.  Slab layout as k_rowln_bwd: [dbias | dgamma | dbeta].
+// DROP: every entry of source row v shares v's keep decisions too, so the mask is applied to the gathered sum.
 constexpr int GL_WAVES = 8;    // wavefronts per workgroup of k_gather_ln_bwd (one slab per workgroup)
-template <int NV>
+template <int NV, bool DROP>
 __global__ void __launch_bounds__(GL_WAVES * 64)
 k_gather_ln_bwd(const float* __restrict__ h, const float* __restrict__ bias, const float* __restrict__ gamma,
                 const float* __restrict__ dout, const int* __restrict__ t_rowptr, const int* __restrict__ t_col,
                 const float* __restrict__ t_w, float* __restrict__ dh, float* __restrict__ slab, int n_rows, int C,
-                float eps, int rows_per_wave) {
+                LnArgs<DROP> ln, int rows_per_wave) {
     __shared__ float4 s_red[GL_WAVES * 64];
+    const Keep<DROP> kp(ln);
+    const float eps = ln.eps;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv_c = 1.0f / (float)C;
     Row<NV> gam, a_db, a_dg, a_dbeta, bias_row;
@@ -596,7 +683,7 @@ k_gather_ln_bwd(const float* __restrict__ h, const float* __restrict__ bias, con
         const int p_beg = t_rowptr[s_beg];
         const int my_rend = (s_beg + lane < s_end) ? t_rowptr[s_beg + lane + 1] : 0;   // lane i: end of row s_beg + i
         const int p_end = t_rowptr[s_end];
-        auto fetch_h = [&](int row, Row<NV>& u) {
+        auto fetch_h = [&](int row, Row<NV>& u) {       // (row.h's load_row in these two moves the p = 0 stream)
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int c = (lane + 64 * i) * 4;
@@ -660,6 +747,7 @@ k_gather_ln_bwd(const float* __restrict__ h, const float* __restrict__ bias, con
             unsigned pos;
             float rstd;
             norm_pair<NV>(ch, bias_row, C, lane, inv_c, eps, x, pos, &rstd);
+            if constexpr (DROP) mask_row<NV>(kp, row, C, lane, dsum);
             float m1 = 0.f, m2 = 0.f;
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
@@ -731,11 +819,188 @@ inline int gl_blocks(int64_t rows) {
     return (int)(b < 1 ? 1 : b);
 }
 
-int check(int64_t rows, int C) {
-    if (rows < 0 || C <= 0) return EQH_ERR_ARG;
+// p: the dropout probability of a *_drop_* entry (the entries without dropout have none: 0)
+int check(int64_t rows, int C, float p = 0.f) {
+    if (rows < 0 || C <= 0 || !(p >= 0.f) || !(p < 1.f)) return EQH_ERR_ARG;
     if ((C & 3) || C > 1024) return EQH_ERR_ALIGN;
     if (rows >= ((int64_t)1 << 31) - 1) return EQH_ERR_RANGE;
     return EQH_OK;
+}
+
+// the parameter gradients of an empty input (b and c may be NULL)
+int zero3(float* a, float* b, float* c, int C, hipStream_t stream) {
+    if (eqh_zero_async(a, C, stream) || (b && eqh_zero_async(b, C, stream))) return EQH_ERR_LAUNCH;
+    return c ? eqh_zero_async(c, C, stream) : EQH_OK;
+}
+
+// The entry points without dropout and their *_drop_* twins validate alike and launch the two instantiations of one
+// kernel: each pair is one function templated on DROP (p = 0, seed = NULL for DROP = false).  A *_drop_* entry called
+// with p = 0 still launches DROP = true, with threshold 0.
+template <bool DROP>
+int inc_fwd(const float* pa, const float* qb, const int32_t* ia, const int32_t* ib, const int32_t* rowptr,
+            const int32_t* perm, const float* gamma, const float* beta, int64_t n_rows, int32_t C, int32_t mean, float eps,
+            float p, const int64_t* seed, float* out, void* stream_) {
+    int rc = check(n_rows, C, p);
+    if (rc) return rc;
+    if (n_rows == 0) return EQH_OK;
+    if (!pa || !qb || !ia || !ib || !rowptr || !perm || !gamma || !beta || !out || (p > 0.f && !seed)) return EQH_ERR_ARG;
+    if (!eqh_aligned16(pa) || !eqh_aligned16(qb) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) ||
+        !eqh_aligned16(out))
+        return EQH_ERR_ALIGN;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return dispatch_nv(C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((k_inc_fwd<NV, DROP>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream,
+                           pa, qb, ia, ib, rowptr, perm, gamma, beta, out, (int)n_rows, (int)C, (int)mean,
+                           ln_args<DROP>(eps, p, seed));
+        EQH_CHECK_LAUNCH();
+        return EQH_OK;
+    });
+}
+
+// perm: the positions of the CSR's entries in ia / ib, which only the dropout decisions need
+template <bool DROP>
+int inc_fwd_col(const float* pa, const float* qb, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                int32_t row_is_a, const float* gamma, const float* beta, int64_t n_rows, int32_t C, int32_t mean, float eps,
+                float p, const int64_t* seed, float* out, void* stream_) {
+    int rc = check(n_rows, C, p);
+    if (rc) return rc;
+    if (n_rows == 0) return EQH_OK;
+    if (!pa || !qb || !rowptr || !col || (DROP && !perm) || !gamma || !beta || !out || (p > 0.f && !seed)) return EQH_ERR_ARG;
+    if (!eqh_aligned16(pa) || !eqh_aligned16(qb) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) ||
+        !eqh_aligned16(out))
+        return EQH_ERR_ALIGN;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return dispatch_nv(C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((k_inc_fwd_col<NV, DROP>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream,
+                           pa, qb, rowptr, col, (int)row_is_a, gamma, beta, out, (int)n_rows, (int)C, (int)mean,
+                           ln_args<DROP>(eps, p, seed, perm));
+        EQH_CHECK_LAUNCH();
+        return EQH_OK;
+    });
+}
+
+// both sides of the per-incidence backward; the caller has validated, and reduces the blocks_a slabs
+template <bool DROP>
+int launch_inc_bwd(const float* pa, const float* qb, const int32_t* ia, const int32_t* ib, const int32_t* a_rowptr,
+                   const int32_t* a_perm, int64_t n_a_rows, const int32_t* b_rowptr, const int32_t* b_perm, int64_t n_b_rows,
+                   const int32_t* okey, const int32_t* orowptr, const float* ds, const float* gamma, int32_t C, int32_t mean,
+                   LnArgs<DROP> ln, float* dpa, float* dqb, float* slab, hipStream_t stream) {
+    const int blocks_a = bwd_blocks(n_a_rows);
+    return dispatch_nv(C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((k_inc_bwd_both<NV, DROP>), dim3(blocks_a + bwd_blocks(n_b_rows)), dim3(THREADS), 0, stream, pa,
+                           qb, ia, ib, a_rowptr, a_perm, b_rowptr, b_perm, okey, orowptr, ds, gamma, dpa, dqb, slab,
+                           (int)n_a_rows, (int)n_b_rows, blocks_a, (int)C, (int)mean, ln, bwd_rpw(n_a_rows),
+                           bwd_rpw(n_b_rows));
+        EQH_CHECK_LAUNCH();
+        return EQH_OK;
+    });
+}
+
+/* Generalised form of the dense-row layer: the pre-activation is h_scale * h + pre_add[r] + bias (pre_add [n_rows, C] may be
+   NULL: then h_scale must be 1) -- the beta = 1 addend and the alpha of the GEMM that produced h, applied here instead of
+   by a copy of the addend into the GEMM's output -- and dh (the gradient of the PRE-ACTIVATION: the caller's GEMMs carry
+   h_scale) is also summed into acc_out [n_rows, C] when given (overwritten if acc_first != 0, else added to): the gradient
+   of pre_add over several applications of the layer (the layer-independent term of conv.py:179-180) without add kernels. */
+template <bool DROP>
+int rowln_fwd(const float* h, float h_scale, const float* pre_add, const float* bias, const float* gamma, const float* beta,
+              int64_t n_rows, int32_t C, float eps, float p, const int64_t* seed, float* out, void* stream_) {
+    int rc = check(n_rows, C, p);
+    if (rc) return rc;
+    if (n_rows == 0) return EQH_OK;
+    if (!h || !bias || !gamma || !beta || !out || (!pre_add && h_scale != 1.0f) || (p > 0.f && !seed)) return EQH_ERR_ARG;
+    if (!eqh_aligned16(h) || !eqh_aligned16(bias) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) || !eqh_aligned16(out) ||
+        !eqh_aligned16(pre_add))
+        return EQH_ERR_ALIGN;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return dispatch_nv(C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((k_rowln_fwd<NV, true, DROP>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream,
+                           h, bias, gamma, beta, out, (int)n_rows, (int)C, ln_args<DROP>(eps, p, seed), pre_add, h_scale);
+        EQH_CHECK_LAUNCH();
+        return EQH_OK;
+    });
+}
+
+template <bool DROP>
+int rowln_bwd(const float* h, float h_scale, const float* pre_add, const float* bias, const float* gamma, const float* dy,
+              int64_t n_rows, int32_t C, float eps, float p, const int64_t* seed, float* dh, float* dbias, float* dgamma,
+              float* dbeta, int32_t accumulate, void* workspace, size_t workspace_bytes, float* acc_out, int32_t acc_first,
+              void* stream_) {
+    int rc = check(n_rows, C, p);
+    if (rc) return rc;
+    if (!dbias || !dgamma || !dbeta || (!pre_add && h_scale != 1.0f)) return EQH_ERR_ARG;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n_rows == 0) return accumulate ? EQH_OK : zero3(dbias, dgamma, dbeta, C, stream);
+    if (!h || !bias || !gamma || !dy || !dh || !workspace || (p > 0.f && !seed)) return EQH_ERR_ARG;
+    if (!eqh_aligned16(h) || !eqh_aligned16(dy) || !eqh_aligned16(dh) || !eqh_aligned16(workspace) || !eqh_aligned16(bias) ||
+        !eqh_aligned16(gamma) || !eqh_aligned16(pre_add) || !eqh_aligned16(acc_out))
+        return EQH_ERR_ALIGN;
+    if (workspace_bytes < hg_bias_relu_ln_bwd_workspace_bytes(n_rows, C)) return EQH_ERR_ARG;
+    const int blocks = rowln_blocks(n_rows);
+    float* slab = static_cast<float*>(workspace);
+    return dispatch_nv(C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((k_rowln_bwd<NV, true, DROP>), dim3(blocks), dim3(THREADS), 0, stream, h, bias, gamma, dy,
+                           (const float*)nullptr, dh, slab, (int)n_rows, (int)C, ln_args<DROP>(eps, p, seed), (int64_t)C, acc_out,
+                           (int)acc_first, pre_add, h_scale);
+        EQH_CHECK_LAUNCH();
+        return eqh_reduce_slabs3_async(slab, blocks, 3 * (int64_t)C, dbias, dgamma, dbeta, C, C, accumulate, stream);
+    });
+}
+
+/* Linear -> ReLU -> LayerNorm hidden layer on dense rows, consumed only through a gathered reduction (see k_gather_ln_fwd):
+   out[r] = gamma * reduce_{q in row r} xhat(relu(h[col[q]] + bias)) + beta * (mean ? [deg r > 0] : deg r) */
+template <bool DROP>
+int gather_ln_fwd(const float* h, const float* bias, const float* gamma, const float* beta, const int32_t* rowptr,
+                  const int32_t* col, int64_t n_rows, int32_t C, int32_t mean, float eps, float p, const int64_t* seed,
+                  float* out, void* stream_) {
+    int rc = check(n_rows, C, p);
+    if (rc) return rc;
+    if (n_rows == 0) return EQH_OK;
+    if (!h || !bias || !gamma || !beta || !rowptr || !col || !out || (p > 0.f && !seed)) return EQH_ERR_ARG;
+    if (!eqh_aligned16(h) || !eqh_aligned16(bias) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) || !eqh_aligned16(out))
+        return EQH_ERR_ALIGN;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return dispatch_nv(C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((k_gather_ln_fwd<NV, DROP>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream, h,
+                           bias, rowptr, col, gamma, beta, out, (int)n_rows, (int)C, (int)mean,
+                           ln_args<DROP>(eps, p, seed));
+        EQH_CHECK_LAUNCH();
+        return EQH_OK;
+    });
+}
+
+/* backward: (t_rowptr, t_col) = the TRANSPOSED CSR (rows = rows of h), t_w = per-entry weights 1 / deg(col) for the mean
+   (hg_entry_weights) or NULL for the sum; dout = gradient of the forward output */
+template <bool DROP>
+int gather_ln_bwd(const float* h, const float* bias, const float* gamma, const float* dout, const int32_t* t_rowptr,
+                  const int32_t* t_col, const float* t_w, int64_t n_src_rows, int32_t C, float eps, float p,
+                  const int64_t* seed, float* dh, float* dbias, float* dgamma, float* dbeta, int32_t accumulate,
+                  void* workspace, size_t workspace_bytes, void* stream_) {
+    int rc = check(n_src_rows, C, p);
+    if (rc) return rc;
+    if (!dbias || !dgamma || !dbeta) return EQH_ERR_ARG;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n_src_rows == 0) return accumulate ? EQH_OK : zero3(dbias, dgamma, dbeta, C, stream);
+    if (!h || !bias || !gamma || !dout || !t_rowptr || !t_col || !dh || !workspace || (p > 0.f && !seed)) return EQH_ERR_ARG;
+    if (!eqh_aligned16(h) || !eqh_aligned16(dout) || !eqh_aligned16(dh) || !eqh_aligned16(workspace) ||
+        !eqh_aligned16(bias) || !eqh_aligned16(gamma))
+        return EQH_ERR_ALIGN;
+    if (workspace_bytes < hg_gather_ln_reduce_bwd_workspace_bytes(n_src_rows, C)) return EQH_ERR_ARG;
+    const int blocks = gl_blocks(n_src_rows);
+    float* slab = static_cast<float*>(workspace);
+    return dispatch_nv(C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((k_gather_ln_bwd<NV, DROP>), dim3(blocks), dim3(GL_WAVES * 64), 0, stream, h, bias, gamma, dout,
+                           t_rowptr, t_col, t_w, dh, slab, (int)n_src_rows, (int)C, ln_args<DROP>(eps, p, seed),
+                           gl_rpw(n_src_rows));
+        EQH_CHECK_LAUNCH();
+        return eqh_reduce_slabs3_async(slab, blocks, 3 * (int64_t)C, dbias, dgamma, dbeta, C, C, accumulate, stream);
+    });
 }
 
 }  // namespace
@@ -744,41 +1009,29 @@ extern "C" int hg_incidence_ln_reduce_fwd(const float* pa, const float* qb, cons
                                           const int32_t* ib, const int32_t* rowptr, const int32_t* perm,
                                           const float* gamma, const float* beta, int64_t n_rows,
                                           int32_t C, int32_t mean, float eps, float* out, void* stream_) {
-    int rc = check(n_rows, C);
-    if (rc) return rc;
-    if (n_rows == 0) return EQH_OK;
-    if (!pa || !qb || !ia || !ib || !rowptr || !perm || !gamma || !beta || !out) return EQH_ERR_ARG;
-    if (!eqh_aligned16(pa) || !eqh_aligned16(qb) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) ||
-        !eqh_aligned16(out))
-        return EQH_ERR_ALIGN;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((k_inc_fwd<NV>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream,
-                           pa, qb, ia, ib, rowptr, perm, gamma, beta, out, (int)n_rows, (int)C, (int)mean, eps);
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
-    });
+    return inc_fwd<false>(pa, qb, ia, ib, rowptr, perm, gamma, beta, n_rows, C, mean, eps, 0.f, nullptr, out, stream_);
+}
+
+extern "C" int hg_incidence_ln_reduce_drop_fwd(const float* pa, const float* qb, const int32_t* ia, const int32_t* ib,
+                                               const int32_t* rowptr, const int32_t* perm, const float* gamma,
+                                               const float* beta, int64_t n_rows, int32_t C, int32_t mean, float eps, float p,
+                                               const int64_t* seed, float* out, void* stream_) {
+    return inc_fwd<true>(pa, qb, ia, ib, rowptr, perm, gamma, beta, n_rows, C, mean, eps, p, seed, out, stream_);
 }
 
 extern "C" int hg_incidence_ln_reduce_fwd_col(const float* pa, const float* qb, const int32_t* rowptr, const int32_t* col,
                                               int32_t row_is_a, const float* gamma, const float* beta, int64_t n_rows,
                                               int32_t C, int32_t mean, float eps, float* out, void* stream_) {
-    int rc = check(n_rows, C);
-    if (rc) return rc;
-    if (n_rows == 0) return EQH_OK;
-    if (!pa || !qb || !rowptr || !col || !gamma || !beta || !out) return EQH_ERR_ARG;
-    if (!eqh_aligned16(pa) || !eqh_aligned16(qb) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) ||
-        !eqh_aligned16(out))
-        return EQH_ERR_ALIGN;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((k_inc_fwd_col<NV>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream,
-                           pa, qb, rowptr, col, (int)row_is_a, gamma, beta, out, (int)n_rows, (int)C, (int)mean, eps);
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
-    });
+    return inc_fwd_col<false>(pa, qb, rowptr, col, nullptr, row_is_a, gamma, beta, n_rows, C, mean, eps, 0.f, nullptr, out,
+                              stream_);
+}
+
+extern "C" int hg_incidence_ln_reduce_drop_fwd_col(const float* pa, const float* qb, const int32_t* rowptr,
+                                                   const int32_t* col, const int32_t* perm, int32_t row_is_a,
+                                                   const float* gamma, const float* beta, int64_t n_rows, int32_t C,
+                                                   int32_t mean, float eps, float p, const int64_t* seed, float* out,
+                                                   void* stream_) {
+    return inc_fwd_col<true>(pa, qb, rowptr, col, perm, row_is_a, gamma, beta, n_rows, C, mean, eps, p, seed, out, stream_);
 }
 
 extern "C" size_t hg_incidence_ln_reduce_bwd_workspace_bytes(int64_t n_a_rows, int32_t C) {
@@ -786,6 +1039,12 @@ extern "C" size_t hg_incidence_ln_reduce_bwd_workspace_bytes(int64_t n_a_rows, i
     return (size_t)bwd_blocks(n_a_rows) * (size_t)C * sizeof(float);
 }
 
+extern "C" size_t hg_incidence_ln_reduce_drop_bwd_workspace_bytes(int64_t n_a_rows, int32_t C) {
+    return 2 * hg_incidence_ln_reduce_bwd_workspace_bytes(n_a_rows, C);      // [dgamma | dbeta] per workgroup
+}
+
+// The two per-incidence backwards share the launch only: without dropout d beta is the caller's column sum of ds, the
+// slab holds d gamma alone, and the operands' alignment is the forward's to check.
 extern "C" int hg_incidence_ln_reduce_bwd(const float* pa, const float* qb, const int32_t* ia,
                                           const int32_t* ib, const int32_t* a_rowptr,
                                           const int32_t* a_perm, int64_t n_a_rows,
@@ -801,7 +1060,7 @@ extern "C" int hg_incidence_ln_reduce_bwd(const float* pa, const float* qb, cons
     if (rc) return rc;
     if (!dgamma || !gamma) return EQH_ERR_ARG;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n_a_rows == 0 && n_b_rows == 0) return accumulate ? EQH_OK : eqh_zero_async(dgamma, C, stream);
+    if (n_a_rows == 0 && n_b_rows == 0) return accumulate ? EQH_OK : zero3(dgamma, nullptr, nullptr, C, stream);
     if (!pa || !qb || !ia || !ib || !a_rowptr || !a_perm || !b_rowptr || !b_perm || !okey || !orowptr || !ds ||
         !dpa || !dqb || !workspace)
         return EQH_ERR_ARG;
@@ -809,36 +1068,55 @@ extern "C" int hg_incidence_ln_reduce_bwd(const float* pa, const float* qb, cons
         return EQH_ERR_ALIGN;
     if (workspace_bytes < hg_incidence_ln_reduce_bwd_workspace_bytes(n_a_rows, C)) return EQH_ERR_ARG;
     float* slab = static_cast<float*>(workspace);
-    const int blocks_a = bwd_blocks(n_a_rows);
-    return dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((k_inc_bwd_both<NV>), dim3(blocks_a + bwd_blocks(n_b_rows)), dim3(THREADS), 0, stream, pa, qb,
-                           ia, ib, a_rowptr, a_perm, b_rowptr, b_perm, okey, orowptr, ds, gamma, dpa, dqb, slab,
-                           (int)n_a_rows, (int)n_b_rows, blocks_a, (int)C, (int)mean, eps, bwd_rpw(n_a_rows),
-                           bwd_rpw(n_b_rows));
-        EQH_CHECK_LAUNCH();
-        return eqh_reduce_slabs_async(slab, blocks_a, C, dgamma, stream, accumulate);
-    });
+    rc = launch_inc_bwd<false>(pa, qb, ia, ib, a_rowptr, a_perm, n_a_rows, b_rowptr, b_perm, n_b_rows, okey, orowptr, ds,
+                               gamma, C, mean, ln_args<false>(eps, 0.f, nullptr), dpa, dqb, slab, stream);
+    return rc ? rc : eqh_reduce_slabs_async(slab, bwd_blocks(n_a_rows), C, dgamma, stream, accumulate);
+}
+
+extern "C" int hg_incidence_ln_reduce_drop_bwd(const float* pa, const float* qb, const int32_t* ia, const int32_t* ib,
+                                               const int32_t* a_rowptr, const int32_t* a_perm, int64_t n_a_rows,
+                                               const int32_t* b_rowptr, const int32_t* b_perm, int64_t n_b_rows,
+                                               const int32_t* okey, const int32_t* orowptr, const float* ds,
+                                               const float* gamma, int32_t C, int32_t mean, float eps, float p,
+                                               const int64_t* seed, float* dpa, float* dqb, float* dgamma, float* dbeta,
+                                               int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream_) {
+    int rc = check(n_a_rows, C, p);
+    if (rc) return rc;
+    rc = check(n_b_rows, C, p);
+    if (rc) return rc;
+    if (!dgamma || !dbeta || !gamma) return EQH_ERR_ARG;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n_a_rows == 0 && n_b_rows == 0) return accumulate ? EQH_OK : zero3(dgamma, dbeta, nullptr, C, stream);
+    if (!pa || !qb || !ia || !ib || !a_rowptr || !a_perm || !b_rowptr || !b_perm || !okey || !orowptr || !ds || !dpa || !dqb ||
+        !workspace || (p > 0.f && !seed))
+        return EQH_ERR_ARG;
+    if (!eqh_aligned16(pa) || !eqh_aligned16(qb) || !eqh_aligned16(gamma) || !eqh_aligned16(ds) || !eqh_aligned16(dpa) ||
+        !eqh_aligned16(dqb) || !eqh_aligned16(workspace))
+        return EQH_ERR_ALIGN;
+    if (workspace_bytes < hg_incidence_ln_reduce_drop_bwd_workspace_bytes(n_a_rows, C)) return EQH_ERR_ARG;
+    float* slab = static_cast<float*>(workspace);
+    rc = launch_inc_bwd<true>(pa, qb, ia, ib, a_rowptr, a_perm, n_a_rows, b_rowptr, b_perm, n_b_rows, okey, orowptr, ds,
+                              gamma, C, mean, ln_args<true>(eps, p, seed), dpa, dqb, slab, stream);
+    return rc ? rc
+              : eqh_reduce_slabs3_async(slab, bwd_blocks(n_a_rows), 2 * (int64_t)C, dgamma, dbeta, nullptr, C, C, accumulate,
+                                        stream);
 }
 
 extern "C" int hg_bias_relu_ln_fwd(const float* h, const float* bias, const float* gamma,
                                    const float* beta, int64_t n_rows, int32_t C, float eps, float* out,
                                    void* stream_) {
-    int rc = check(n_rows, C);
-    if (rc) return rc;
-    if (n_rows == 0) return EQH_OK;
-    if (!h || !bias || !gamma || !beta || !out) return EQH_ERR_ARG;
-    if (!eqh_aligned16(h) || !eqh_aligned16(bias) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) ||
-        !eqh_aligned16(out))
-        return EQH_ERR_ALIGN;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((k_rowln_fwd<NV, true>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream, h,
-                           bias, gamma, beta, out, (int)n_rows, (int)C, eps);
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
-    });
+    return rowln_fwd<false>(h, 1.0f, nullptr, bias, gamma, beta, n_rows, C, eps, 0.f, nullptr, out, stream_);
+}
+
+extern "C" int hg_bias_relu_ln_fwd_ex(const float* h, float h_scale, const float* pre_add, const float* bias, const float* gamma,
+                                      const float* beta, int64_t n_rows, int32_t C, float eps, float* out, void* stream_) {
+    return rowln_fwd<false>(h, h_scale, pre_add, bias, gamma, beta, n_rows, C, eps, 0.f, nullptr, out, stream_);
+}
+
+extern "C" int hg_bias_relu_ln_drop_fwd(const float* h, float h_scale, const float* pre_add, const float* bias,
+                                        const float* gamma, const float* beta, int64_t n_rows, int32_t C, float eps, float p,
+                                        const int64_t* seed, float* out, void* stream_) {
+    return rowln_fwd<true>(h, h_scale, pre_add, bias, gamma, beta, n_rows, C, eps, p, seed, out, stream_);
 }
 
 extern "C" size_t hg_bias_relu_ln_bwd_workspace_bytes(int64_t n_rows, int32_t C) {
@@ -846,96 +1124,47 @@ extern "C" size_t hg_bias_relu_ln_bwd_workspace_bytes(int64_t n_rows, int32_t C)
     return (size_t)rowln_blocks(n_rows) * 3 * (size_t)C * sizeof(float);
 }
 
-static int bias_relu_ln_bwd_impl(const float* h, const float* bias, const float* gamma, const float* dy,
-                                 int64_t n_rows, int32_t C, float eps, float* dh, float* dbias, float* dgamma,
-                                 float* dbeta, int32_t accumulate, void* workspace, size_t workspace_bytes,
-                                 float* acc_out, int32_t acc_first, const float* pre_add, float h_scale, void* stream_) {
-    int rc = check(n_rows, C);
-    if (rc) return rc;
-    if (!dbias || !dgamma || !dbeta) return EQH_ERR_ARG;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n_rows == 0) {
-        if (accumulate) return EQH_OK;
-        if (eqh_zero_async(dbias, C, stream) || eqh_zero_async(dgamma, C, stream)) return EQH_ERR_LAUNCH;
-        return eqh_zero_async(dbeta, C, stream);
-    }
-    if (!h || !bias || !gamma || !dy || !dh || !workspace) return EQH_ERR_ARG;
-    if (!eqh_aligned16(h) || !eqh_aligned16(dy) || !eqh_aligned16(dh) || !eqh_aligned16(workspace) ||
-        !eqh_aligned16(bias) || !eqh_aligned16(gamma))
-        return EQH_ERR_ALIGN;
-    if (workspace_bytes < hg_bias_relu_ln_bwd_workspace_bytes(n_rows, C)) return EQH_ERR_ARG;
-    const int blocks = rowln_blocks(n_rows);
-    float* slab = static_cast<float*>(workspace);
-    return dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((k_rowln_bwd<NV, true>), dim3(blocks), dim3(THREADS), 0, stream, h, bias, gamma, dy,
-                           (const float*)nullptr, dh, slab,
-                           (int)n_rows, (int)C, eps, (int64_t)C, acc_out, (int)acc_first, pre_add, h_scale);
-        EQH_CHECK_LAUNCH();
-        return eqh_reduce_slabs3_async(slab, blocks, 3 * (int64_t)C, dbias, dgamma, dbeta, C, C, accumulate, stream);
-    });
+extern "C" size_t hg_bias_relu_ln_drop_bwd_workspace_bytes(int64_t n_rows, int32_t C) {
+    return hg_bias_relu_ln_bwd_workspace_bytes(n_rows, C);
 }
 
 extern "C" int hg_bias_relu_ln_bwd(const float* h, const float* bias, const float* gamma, const float* dy,
                                    int64_t n_rows, int32_t C, float eps, float* dh, float* dbias, float* dgamma,
                                    float* dbeta, int32_t accumulate, void* workspace, size_t workspace_bytes,
                                    void* stream_) {
-    return bias_relu_ln_bwd_impl(h, bias, gamma, dy, n_rows, C, eps, dh, dbias, dgamma, dbeta, accumulate, workspace,
-                                 workspace_bytes, nullptr, 0, nullptr, 1.0f, stream_);
-}
-
-/* Generalised form: the pre-activation is h_scale * h + pre_add[r] + bias (pre_add [n_rows, C] may be NULL: then h_scale
-   must be 1) -- the beta = 1 addend and the alpha of the GEMM that produced h, applied here instead of by a copy of the
-   addend into the GEMM's output -- and dh (the gradient of the PRE-ACTIVATION: the caller's GEMMs carry h_scale) is also
-   summed into acc_out [n_rows, C] when given (overwritten if acc_first != 0, else added to): the gradient of pre_add over
-   several applications of the layer (the layer-independent term of conv.py:179-180) without add kernels. */
-extern "C" int hg_bias_relu_ln_fwd_ex(const float* h, float h_scale, const float* pre_add, const float* bias, const float* gamma,
-                                      const float* beta, int64_t n_rows, int32_t C, float eps, float* out, void* stream_) {
-    int rc = check(n_rows, C);
-    if (rc) return rc;
-    if (n_rows == 0) return EQH_OK;
-    if (!h || !bias || !gamma || !beta || !out || (!pre_add && h_scale != 1.0f)) return EQH_ERR_ARG;
-    if (!eqh_aligned16(h) || !eqh_aligned16(bias) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) || !eqh_aligned16(out) ||
-        !eqh_aligned16(pre_add))
-        return EQH_ERR_ALIGN;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((k_rowln_fwd<NV, true>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream, h,
-                           bias, gamma, beta, out, (int)n_rows, (int)C, eps, pre_add, h_scale);
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
-    });
+    return rowln_bwd<false>(h, 1.0f, nullptr, bias, gamma, dy, n_rows, C, eps, 0.f, nullptr, dh, dbias, dgamma, dbeta,
+                            accumulate, workspace, workspace_bytes, nullptr, 0, stream_);
 }
 
 extern "C" int hg_bias_relu_ln_bwd_ex(const float* h, float h_scale, const float* pre_add, const float* bias, const float* gamma,
                                       const float* dy, int64_t n_rows, int32_t C, float eps, float* dh, float* dbias,
                                       float* dgamma, float* dbeta, int32_t accumulate, void* workspace, size_t workspace_bytes,
                                       float* acc_out, int32_t acc_first, void* stream_) {
+    // (this entry reports a misaligned pre_add / acc_out as EQH_ERR_ARG, ahead of everything else)
     if ((!pre_add && h_scale != 1.0f) || !eqh_aligned16(pre_add) || !eqh_aligned16(acc_out)) return EQH_ERR_ARG;
-    return bias_relu_ln_bwd_impl(h, bias, gamma, dy, n_rows, C, eps, dh, dbias, dgamma, dbeta, accumulate, workspace,
-                                 workspace_bytes, acc_out, acc_first, pre_add, h_scale, stream_);
+    return rowln_bwd<false>(h, h_scale, pre_add, bias, gamma, dy, n_rows, C, eps, 0.f, nullptr, dh, dbias, dgamma, dbeta,
+                            accumulate, workspace, workspace_bytes, acc_out, acc_first, stream_);
 }
 
-/* Linear -> ReLU -> LayerNorm hidden layer on dense rows, consumed only through a gathered reduction (see k_gather_ln_fwd):
-   out[r] = gamma * reduce_{q in row r} xhat(relu(h[col[q]] + bias)) + beta * (mean ? [deg r > 0] : deg r) */
+extern "C" int hg_bias_relu_ln_drop_bwd(const float* h, float h_scale, const float* pre_add, const float* bias,
+                                        const float* gamma, const float* dy, int64_t n_rows, int32_t C, float eps, float p,
+                                        const int64_t* seed, float* dh, float* dbias, float* dgamma, float* dbeta,
+                                        int32_t accumulate, void* workspace, size_t workspace_bytes, float* acc_out,
+                                        int32_t acc_first, void* stream_) {
+    return rowln_bwd<true>(h, h_scale, pre_add, bias, gamma, dy, n_rows, C, eps, p, seed, dh, dbias, dgamma, dbeta,
+                           accumulate, workspace, workspace_bytes, acc_out, acc_first, stream_);
+}
+
 extern "C" int hg_gather_ln_reduce_fwd(const float* h, const float* bias, const float* gamma, const float* beta,
                                        const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t C, int32_t mean,
                                        float eps, float* out, void* stream_) {
-    int rc = check(n_rows, C);
-    if (rc) return rc;
-    if (n_rows == 0) return EQH_OK;
-    if (!h || !bias || !gamma || !beta || !rowptr || !col || !out) return EQH_ERR_ARG;
-    if (!eqh_aligned16(h) || !eqh_aligned16(bias) || !eqh_aligned16(gamma) || !eqh_aligned16(beta) || !eqh_aligned16(out))
-        return EQH_ERR_ALIGN;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((k_gather_ln_fwd<NV>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream, h, bias,
-                           rowptr, col, gamma, beta, out, (int)n_rows, (int)C, (int)mean, eps);
-        EQH_CHECK_LAUNCH();
-        return EQH_OK;
-    });
+    return gather_ln_fwd<false>(h, bias, gamma, beta, rowptr, col, n_rows, C, mean, eps, 0.f, nullptr, out, stream_);
+}
+
+extern "C" int hg_gather_ln_reduce_drop_fwd(const float* h, const float* bias, const float* gamma, const float* beta,
+                                            const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t C,
+                                            int32_t mean, float eps, float p, const int64_t* seed, float* out, void* stream_) {
+    return gather_ln_fwd<true>(h, bias, gamma, beta, rowptr, col, n_rows, C, mean, eps, p, seed, out, stream_);
 }
 
 extern "C" size_t hg_gather_ln_reduce_bwd_workspace_bytes(int64_t n_src_rows, int32_t C) {
@@ -943,35 +1172,25 @@ extern "C" size_t hg_gather_ln_reduce_bwd_workspace_bytes(int64_t n_src_rows, in
     return (size_t)gl_blocks(n_src_rows) * 3 * (size_t)C * sizeof(float);
 }
 
-/* backward: (t_rowptr, t_col) = the TRANSPOSED CSR (rows = rows of h), t_w = per-entry weights 1 / deg(col) for the mean
-   (hg_entry_weights) or NULL for the sum; dout = gradient of the forward output */
+extern "C" size_t hg_gather_ln_reduce_drop_bwd_workspace_bytes(int64_t n_src_rows, int32_t C) {
+    return hg_gather_ln_reduce_bwd_workspace_bytes(n_src_rows, C);
+}
+
 extern "C" int hg_gather_ln_reduce_bwd(const float* h, const float* bias, const float* gamma, const float* dout,
                                        const int32_t* t_rowptr, const int32_t* t_col, const float* t_w, int64_t n_src_rows,
                                        int32_t C, float eps, float* dh, float* dbias, float* dgamma, float* dbeta,
                                        int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream_) {
-    int rc = check(n_src_rows, C);
-    if (rc) return rc;
-    if (!dbias || !dgamma || !dbeta) return EQH_ERR_ARG;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n_src_rows == 0) {
-        if (accumulate) return EQH_OK;
-        if (eqh_zero_async(dbias, C, stream) || eqh_zero_async(dgamma, C, stream)) return EQH_ERR_LAUNCH;
-        return eqh_zero_async(dbeta, C, stream);
-    }
-    if (!h || !bias || !gamma || !dout || !t_rowptr || !t_col || !dh || !workspace) return EQH_ERR_ARG;
-    if (!eqh_aligned16(h) || !eqh_aligned16(dout) || !eqh_aligned16(dh) || !eqh_aligned16(workspace) ||
-        !eqh_aligned16(bias) || !eqh_aligned16(gamma))
-        return EQH_ERR_ALIGN;
-    if (workspace_bytes < hg_gather_ln_reduce_bwd_workspace_bytes(n_src_rows, C)) return EQH_ERR_ARG;
-    const int blocks = gl_blocks(n_src_rows);
-    float* slab = static_cast<float*>(workspace);
-    return dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((k_gather_ln_bwd<NV>), dim3(blocks), dim3(GL_WAVES * 64), 0, stream, h, bias, gamma, dout, t_rowptr,
-                           t_col, t_w, dh, slab, (int)n_src_rows, (int)C, eps, gl_rpw(n_src_rows));
-        EQH_CHECK_LAUNCH();
-        return eqh_reduce_slabs3_async(slab, blocks, 3 * (int64_t)C, dbias, dgamma, dbeta, C, C, accumulate, stream);
-    });
+    return gather_ln_bwd<false>(h, bias, gamma, dout, t_rowptr, t_col, t_w, n_src_rows, C, eps, 0.f, nullptr, dh, dbias,
+                                dgamma, dbeta, accumulate, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int hg_gather_ln_reduce_drop_bwd(const float* h, const float* bias, const float* gamma, const float* dout,
+                                            const int32_t* t_rowptr, const int32_t* t_col, const float* t_w,
+                                            int64_t n_src_rows, int32_t C, float eps, float p, const int64_t* seed, float* dh,
+                                            float* dbias, float* dgamma, float* dbeta, int32_t accumulate, void* workspace,
+                                            size_t workspace_bytes, void* stream_) {
+    return gather_ln_bwd<true>(h, bias, gamma, dout, t_rowptr, t_col, t_w, n_src_rows, C, eps, p, seed, dh, dbias, dgamma,
+                               dbeta, accumulate, workspace, workspace_bytes, stream_);
 }
 
 /* plain LayerNorm over dense rows (the EGNN node_norm, egnn_layer.py:192) on the same row machinery */
@@ -986,7 +1205,7 @@ extern "C" int hg_layer_norm_fwd(const float* x, const float* gamma, const float
     return dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         hipLaunchKernelGGL((k_rowln_fwd<NV, false>), dim3(eqh_grid_for(n_rows, WAVES, 4096)), dim3(THREADS), 0, stream, x,
-                           (const float*)nullptr, gamma, beta, out, (int)n_rows, (int)C, eps);
+                           (const float*)nullptr, gamma, beta, out, (int)n_rows, (int)C, LnArgs<false>{eps});
         EQH_CHECK_LAUNCH();
         return EQH_OK;
     });
@@ -1004,11 +1223,7 @@ extern "C" int hg_layer_norm_bwd(const float* x, const float* gamma, const float
     if (rc) return rc;
     if (!dgamma || !dbeta) return EQH_ERR_ARG;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n_rows == 0) {
-        if (accumulate) return EQH_OK;
-        if (eqh_zero_async(dgamma, C, stream)) return EQH_ERR_LAUNCH;
-        return eqh_zero_async(dbeta, C, stream);
-    }
+    if (n_rows == 0) return accumulate ? EQH_OK : zero3(dgamma, dbeta, nullptr, C, stream);
     if (!x || !gamma || !dy || !dx || !workspace) return EQH_ERR_ARG;
     if (!eqh_aligned16(x) || !eqh_aligned16(dy) || !eqh_aligned16(dx) || !eqh_aligned16(workspace) || !eqh_aligned16(gamma) ||
         !eqh_aligned16(add))
@@ -1021,7 +1236,7 @@ extern "C" int hg_layer_norm_bwd(const float* x, const float* gamma, const float
     return dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         hipLaunchKernelGGL((k_rowln_bwd<NV, false>), dim3(blocks), dim3(THREADS), 0, stream, x, (const float*)nullptr, gamma,
-                           dy, add, dx, slab, (int)n_rows, (int)C, eps, dy_ld);
+                           dy, add, dx, slab, (int)n_rows, (int)C, LnArgs<false>{eps}, dy_ld);
         EQH_CHECK_LAUNCH();
         // the slab's first segment (column sums of dx) has no consumer here; it goes to the discard row.  Never
         // deferred-with-accumulate for that segment's sake: accumulate applies to all three alike, harmlessly.

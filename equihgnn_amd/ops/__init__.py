@@ -64,8 +64,7 @@ from . import mhnn_panel  # noqa: F401
 from .rows import (  # noqa: F401
     _IncidenceLnReduce, _BiasReluLn, _LinearAddReluLn, linear_add_relu_ln, _GatherLnReduce, gather_ln_reduce,
     _BatchNormRows, batch_norm_rows, batch_norm_rows_supported, _LayerNormRows, incidence_ln_reduce, bias_relu_ln,
-    _ResidualMix, residual_mix, layer_norm_rows, FUSED_DROPOUT, _IncidenceLnReduceDrop, _BiasReluLnDrop, _LinearAddReluLnDrop,
-    _GatherLnReduceDrop,
+    _ResidualMix, residual_mix, layer_norm_rows, FUSED_DROPOUT,
 )
 from .egnn import (  # noqa: F401
     _EgnnEdge, _EgnnFeats, egnn_feats, _EgnnPackWeights, egnn_pack_weights, egnn_edge, _EgnnNodeMlp, egnn_node_mlp,

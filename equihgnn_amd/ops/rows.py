@@ -15,9 +15,9 @@ from .products import (mm_nn, mm_nt)
 from .grads import (_wgrad_deferred, _wgrad_ok, colsum, wgrad)
 from .frames import _dropout_seed
 
-# Training dropout of the hidden layers inside the fused row kernels (csrc/conv_dropout.hip): the keep decisions are a
-# hash of (seed, element index), recomputed by the backward.  False: an MLP with an active dropout leaves the fused path
-# and runs ReLU, LayerNorm and F.dropout as ATen launches (layers.MLP.hidden).
+# Training dropout of the hidden layers inside the fused row kernels (the DROP instantiations of csrc/incidence.hip): the
+# keep decisions are a hash of (seed, element index), recomputed by the backward.  False: an MLP with an active dropout
+# leaves the fused path and runs ReLU, LayerNorm and F.dropout as ATen launches (layers.MLP.hidden).
 FUSED_DROPOUT = True
 
 
@@ -57,88 +57,53 @@ def inc_fwd_col_bytes(nnz: int, rows: int, C: int) -> int:
     return 4 * C * (nnz + 2 * rows) + 4 * nnz + 4 * (rows + 1) + 8 * C
 
 
+def _launch(fn: str, *args):
+    hip.check(getattr(hip.lib(), fn)(*args), fn)
+
+
+def _param_grads(ctx_acc, n: int, C: int, device):
+    """Where a backward kernel writes the ``n`` parameter gradients of ``ctx_acc``: (targets, acc, small, o) -- in place
+    into the parameters' accumulators when every one has one (acc), else into the rows of a fresh ``small``."""
+    tg = [_acc_target(q) for q in ctx_acc]
+    acc = all(t is not None for t in tg)   # all accumulate in place: nothing for autograd to add
+    small = None if acc else torch.empty((n, C), dtype=torch.float32, device=device)
+    return tg, acc, small, (tg if acc else list(small))
+
+
 class _IncidenceLnReduce(torch.autograd.Function):
     """S[r] = reduce_{p in row r} LayerNorm(relu(pa[ia[p]] + qb[ib[p]])) — one launch instead of
-    gather, gather, add, ReLU, LayerNorm, segmented reduce (csrc/incidence.hip)."""
+    gather, gather, add, ReLU, LayerNorm, segmented reduce (csrc/incidence.hip).
+    ``p`` > 0: dropout behind the LayerNorm, S[r] = reduce keep[p] * LN(..), the decision of incidence p, channel c being
+    element p * C + c (hg_incidence_ln_reduce_drop_*).  That backward kernel yields d beta too (a mask sits between beta
+    and the sum)."""
 
     @staticmethod
     def forward(ctx, pa, qb, gamma, beta, ia32, ib32, csr_a: CSR, csr_b: CSR, out_csr: CSR, okey32, mean, eps,
-                acc_params):
+                acc_params, p=0.0, seed=None):
         _require_gpu(pa, "incidence_ln_reduce")
         pa, qb, gamma, beta = _f32c(pa), _f32c(qb), _f32c(gamma), _f32c(beta)
         C = pa.shape[1]
+        drop = p > 0.0
+        if drop and seed is None:
+            seed = _dropout_seed(pa.device, p)
+        dargs = (p, _ptr(seed)) if drop else ()
         out = torch.empty((out_csr.n_rows, C), dtype=torch.float32, device=pa.device)
+        tail = (_ptr(gamma), _ptr(beta), out_csr.n_rows, C, 1 if mean else 0, float(eps), *dargs, _ptr(out),
+                _stream(pa.device))
         if okey32 is ia32 or okey32 is ib32:
-            # the output row is one operand's own index: (rowptr, col) of the output CSR says it all
-            timed("k_inc_fwd_col", inc_fwd_col_bytes(out_csr.nnz, out_csr.n_rows, C), lambda: hip.check(hip.lib().hg_incidence_ln_reduce_fwd_col(
-                _ptr(pa), _ptr(qb), _ptr(out_csr.rowptr), _ptr(out_csr.col), 1 if okey32 is ia32 else 0, _ptr(gamma),
-                _ptr(beta), out_csr.n_rows, C, 1 if mean else 0, float(eps), _ptr(out), _stream(pa.device)),
-                "hg_incidence_ln_reduce_fwd_col"))
+            # the output row is one operand's own index: (rowptr, col) of the output CSR says it all (the dropout
+            # decisions belong to the incidences' positions: perm too)
+            fn = "hg_incidence_ln_reduce_drop_fwd_col" if drop else "hg_incidence_ln_reduce_fwd_col"
+            timed("k_inc_drop_fwd_col" if drop else "k_inc_fwd_col",
+                  inc_fwd_col_bytes(out_csr.nnz, out_csr.n_rows, C) + (4 * out_csr.nnz if drop else 0),
+                  lambda: _launch(fn, _ptr(pa), _ptr(qb), _ptr(out_csr.rowptr),
+                                  _ptr(out_csr.col), *((_ptr(out_csr.perm),) if drop else ()), 1 if okey32 is ia32 else 0,
+                                  *tail))
         else:
-            timed("k_inc_fwd", inc_fwd_bytes(out_csr.nnz, out_csr.n_rows, C), lambda: hip.check(hip.lib().hg_incidence_ln_reduce_fwd(
-                _ptr(pa), _ptr(qb), _ptr(ia32), _ptr(ib32), _ptr(out_csr.rowptr), _ptr(out_csr.perm), _ptr(gamma),
-                _ptr(beta), out_csr.n_rows, C, 1 if mean else 0, float(eps), _ptr(out), _stream(pa.device)),
-                "hg_incidence_ln_reduce_fwd"))
-        ctx.save_for_backward(pa, qb, gamma)
-        ctx.meta = (ia32, ib32, csr_a, csr_b, out_csr, okey32, mean, eps)
-        ctx.acc = acc_params
-        return out
-
-    @staticmethod
-    def backward(ctx, ds):
-        pa, qb, gamma = ctx.saved_tensors
-        ia32, ib32, csr_a, csr_b, out_csr, okey32, mean, eps = ctx.meta
-        ds = _f32c(ds)
-        C = pa.shape[1]
-        dev = pa.device
-        dpa, dqb = torch.empty_like(pa), torch.empty_like(qb)
-        g_acc, b_acc = (_acc_target(p) for p in ctx.acc)
-        dgamma = g_acc if g_acc is not None else torch.empty_like(gamma)
-        L = hip.lib()
-        ws_bytes = L.hg_incidence_ln_reduce_bwd_workspace_bytes(csr_a.n_rows, C)
-        ws = _workspace(ws_bytes, dev)
-        # algorithmic bytes: each operand side walks every incidence once and gathers, per incidence, the OTHER
-        # operand's row and the output-gradient row, reads its own row once and writes its own gradient row:
-        # 4C (4 nnz + 2 (Ra + Rb)) + five index words per incidence and side + both rowptrs
-        nnz_ = csr_a.nnz
-        timed("k_inc_bwd_both", 4 * C * (4 * nnz_ + 2 * (csr_a.n_rows + csr_b.n_rows)) + 2 * 20 * nnz_
-              + 4 * (csr_a.n_rows + csr_b.n_rows + 2),
-              lambda: hip.check(L.hg_incidence_ln_reduce_bwd(
-                  _ptr(pa), _ptr(qb), _ptr(ia32), _ptr(ib32), _ptr(csr_a.rowptr), _ptr(csr_a.perm), csr_a.n_rows,
-                  _ptr(csr_b.rowptr), _ptr(csr_b.perm), csr_b.n_rows, _ptr(okey32), _ptr(out_csr.rowptr), _ptr(ds),
-                  _ptr(gamma), C, 1 if mean else 0, float(eps), _ptr(dpa), _ptr(dqb), _ptr(dgamma),
-                  1 if g_acc is not None else 0, _ptr(ws), ws_bytes, _stream(dev)), "hg_incidence_ln_reduce_bwd"))
-        # d beta = sum_r w_r ds[r], w_r = [row non-empty] (mean) or the row length (sum)
-        dbeta = colsum(ds, out_csr.rowptr, 1 if mean else 2, into=b_acc)
-        return (dpa, dqb, None if g_acc is not None else dgamma, dbeta) + (None,) * 9
-
-
-class _IncidenceLnReduceDrop(torch.autograd.Function):
-    """_IncidenceLnReduce with dropout behind the LayerNorm: S[r] = reduce_{p in row r} keep[p] * LN(relu(pa[ia[p]] +
-    qb[ib[p]])), the decision of incidence p, channel c being element p * C + c (hg_incidence_ln_reduce_drop_*).  The
-    backward kernel yields d beta too (a mask sits between beta and the sum)."""
-
-    @staticmethod
-    def forward(ctx, pa, qb, gamma, beta, ia32, ib32, csr_a: CSR, csr_b: CSR, out_csr: CSR, okey32, mean, eps,
-                acc_params, p, seed):
-        _require_gpu(pa, "incidence_ln_reduce")
-        pa, qb, gamma, beta = _f32c(pa), _f32c(qb), _f32c(gamma), _f32c(beta)
-        C = pa.shape[1]
-        seed = seed if seed is not None else _dropout_seed(pa.device, p)
-        out = torch.empty((out_csr.n_rows, C), dtype=torch.float32, device=pa.device)
-        L = hip.lib()
-        if okey32 is ia32 or okey32 is ib32:
-            timed("k_inc_drop_fwd_col", inc_fwd_col_bytes(out_csr.nnz, out_csr.n_rows, C) + 4 * out_csr.nnz,
-                  lambda: hip.check(L.hg_incidence_ln_reduce_drop_fwd_col(
-                      _ptr(pa), _ptr(qb), _ptr(out_csr.rowptr), _ptr(out_csr.col), _ptr(out_csr.perm),
-                      1 if okey32 is ia32 else 0, _ptr(gamma), _ptr(beta), out_csr.n_rows, C, 1 if mean else 0, float(eps),
-                      p, _ptr(seed), _ptr(out), _stream(pa.device)), "hg_incidence_ln_reduce_drop_fwd_col"))
-        else:
-            timed("k_inc_drop_fwd", inc_fwd_bytes(out_csr.nnz, out_csr.n_rows, C), lambda: hip.check(
-                L.hg_incidence_ln_reduce_drop_fwd(
-                    _ptr(pa), _ptr(qb), _ptr(ia32), _ptr(ib32), _ptr(out_csr.rowptr), _ptr(out_csr.perm), _ptr(gamma),
-                    _ptr(beta), out_csr.n_rows, C, 1 if mean else 0, float(eps), p, _ptr(seed), _ptr(out),
-                    _stream(pa.device)), "hg_incidence_ln_reduce_drop_fwd"))
+            fn = "hg_incidence_ln_reduce_drop_fwd" if drop else "hg_incidence_ln_reduce_fwd"
+            timed("k_inc_drop_fwd" if drop else "k_inc_fwd", inc_fwd_bytes(out_csr.nnz, out_csr.n_rows, C),
+                  lambda: _launch(fn, _ptr(pa), _ptr(qb), _ptr(ia32), _ptr(ib32),
+                                  _ptr(out_csr.rowptr), _ptr(out_csr.perm), *tail))
         ctx.save_for_backward(pa, qb, gamma)
         ctx.meta = (ia32, ib32, csr_a, csr_b, out_csr, okey32, mean, eps, p, seed)
         ctx.acc = acc_params
@@ -152,91 +117,116 @@ class _IncidenceLnReduceDrop(torch.autograd.Function):
         C = pa.shape[1]
         dev = pa.device
         dpa, dqb = torch.empty_like(pa), torch.empty_like(qb)
-        tg = [_acc_target(q) for q in ctx.acc]
-        acc = all(t is not None for t in tg)
-        small = None if acc else torch.empty((2, C), dtype=torch.float32, device=dev)
-        o = tg if acc else list(small)
-        L = hip.lib()
-        ws_bytes = L.hg_incidence_ln_reduce_drop_bwd_workspace_bytes(csr_a.n_rows, C)
-        ws = _workspace(ws_bytes, dev)
+        head = (_ptr(pa), _ptr(qb), _ptr(ia32), _ptr(ib32), _ptr(csr_a.rowptr), _ptr(csr_a.perm), csr_a.n_rows,
+                _ptr(csr_b.rowptr), _ptr(csr_b.perm), csr_b.n_rows, _ptr(okey32), _ptr(out_csr.rowptr), _ptr(ds),
+                _ptr(gamma), C, 1 if mean else 0, float(eps))
+        # algorithmic bytes: each operand side walks every incidence once and gathers, per incidence, the OTHER
+        # operand's row and the output-gradient row, reads its own row once and writes its own gradient row:
+        # 4C (4 nnz + 2 (Ra + Rb)) + five index words per incidence and side + both rowptrs
         nnz_ = csr_a.nnz
-        timed("k_inc_drop_bwd_both", 4 * C * (4 * nnz_ + 2 * (csr_a.n_rows + csr_b.n_rows)) + 2 * 20 * nnz_
-              + 4 * (csr_a.n_rows + csr_b.n_rows + 2),
-              lambda: hip.check(L.hg_incidence_ln_reduce_drop_bwd(
-                  _ptr(pa), _ptr(qb), _ptr(ia32), _ptr(ib32), _ptr(csr_a.rowptr), _ptr(csr_a.perm), csr_a.n_rows,
-                  _ptr(csr_b.rowptr), _ptr(csr_b.perm), csr_b.n_rows, _ptr(okey32), _ptr(out_csr.rowptr), _ptr(ds),
-                  _ptr(gamma), C, 1 if mean else 0, float(eps), p, _ptr(seed), _ptr(dpa), _ptr(dqb), _ptr(o[0]), _ptr(o[1]),
-                  1 if acc else 0, _ptr(ws), ws_bytes, _stream(dev)), "hg_incidence_ln_reduce_drop_bwd"))
-        if acc:
-            return (dpa, dqb) + (None,) * 13
-        return (dpa, dqb, *_hand_out(list(small), tg)) + (None,) * 11
+        nbytes = 4 * C * (4 * nnz_ + 2 * (csr_a.n_rows + csr_b.n_rows)) + 2 * 20 * nnz_ + 4 * (csr_a.n_rows + csr_b.n_rows + 2)
+        L = hip.lib()
+        if p > 0.0:
+            tg, acc, small, o = _param_grads(ctx.acc, 2, C, dev)
+            ws_bytes = L.hg_incidence_ln_reduce_drop_bwd_workspace_bytes(csr_a.n_rows, C)
+            ws = _workspace(ws_bytes, dev)
+            timed("k_inc_drop_bwd_both", nbytes, lambda: _launch(
+                "hg_incidence_ln_reduce_drop_bwd", *head, p, _ptr(seed), _ptr(dpa), _ptr(dqb), _ptr(o[0]), _ptr(o[1]),
+                1 if acc else 0, _ptr(ws), ws_bytes, _stream(dev)))
+            dgamma, dbeta = (None, None) if acc else _hand_out(list(small), tg)
+        else:
+            g_acc, b_acc = (_acc_target(q) for q in ctx.acc)
+            dgamma = g_acc if g_acc is not None else torch.empty_like(gamma)
+            ws_bytes = L.hg_incidence_ln_reduce_bwd_workspace_bytes(csr_a.n_rows, C)
+            ws = _workspace(ws_bytes, dev)
+            timed("k_inc_bwd_both", nbytes, lambda: _launch(
+                "hg_incidence_ln_reduce_bwd", *head, _ptr(dpa), _ptr(dqb), _ptr(dgamma), 1 if g_acc is not None else 0,
+                _ptr(ws), ws_bytes, _stream(dev)))
+            if g_acc is not None:
+                dgamma = None
+            # d beta = sum_r w_r ds[r], w_r = [row non-empty] (mean) or the row length (sum)
+            dbeta = colsum(ds, out_csr.rowptr, 1 if mean else 2, into=b_acc)
+        return (dpa, dqb, dgamma, dbeta) + (None,) * 11
 
 
-def _rowln_drop_bwd(ctx_acc, h, a, c, bias, gamma, dy, eps, p, seed, fan):
-    """The backward launch shared by _BiasReluLnDrop and _LinearAddReluLnDrop: (dpre, acc, small, targets)."""
+def _rowln_bwd(ctx_acc, h, a, c, bias, gamma, dy, eps, fan, p, seed, ex):
+    """The backward launch of _BiasReluLn and _LinearAddReluLn: (gradient of the pre-activation, the (dbias, dgamma, dbeta)
+    for autograd -- None where accumulated in place).  ``ex``: the entry that takes the scale ``a``, the addend ``c`` and
+    the GradFan (with ``p`` > 0 there is only that form)."""
     R, C = h.shape
     dpre = torch.empty_like(h)
     L = hip.lib()
-    ws_bytes = L.hg_bias_relu_ln_drop_bwd_workspace_bytes(R, C)
+    ws_bytes = (L.hg_bias_relu_ln_drop_bwd_workspace_bytes if p > 0.0 else L.hg_bias_relu_ln_bwd_workspace_bytes)(R, C)
     ws = _workspace(ws_bytes, h.device)
-    tg = [_acc_target(q) for q in ctx_acc]
-    acc = all(t is not None for t in tg)
-    small = None if acc else torch.empty((3, C), dtype=torch.float32, device=h.device)
-    o = tg if acc else list(small)
-    if fan is not None and fan.buf is None:
+    tg, acc, small, o = _param_grads(ctx_acc, 3, C, h.device)
+    outs = (_ptr(dpre), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), 1 if acc else 0, _ptr(ws), ws_bytes)
+    if fan is not None and fan.buf is None:     # dpre is also the gradient of the layer's fanned-out addend: summed in the kernel
         fan.buf = torch.empty_like(h)
-    hip.check(L.hg_bias_relu_ln_drop_bwd(_ptr(h), a, _ptr(c), _ptr(bias), _ptr(gamma), _ptr(dy), R, C, eps, p, _ptr(seed),
-                                         _ptr(dpre), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), 1 if acc else 0, _ptr(ws), ws_bytes,
-                                         _ptr(fan.buf) if fan is not None else None,
-                                         1 if (fan is not None and fan.n == 0) else 0, _stream(h.device)),
-              "hg_bias_relu_ln_drop_bwd")
+    fanned = (_ptr(fan.buf) if fan is not None else None, 1 if (fan is not None and fan.n == 0) else 0)
+    if p > 0.0:
+        _launch("hg_bias_relu_ln_drop_bwd", _ptr(h), a, _ptr(c), _ptr(bias), _ptr(gamma), _ptr(dy), R, C, eps, p, _ptr(seed),
+                *outs, *fanned, _stream(h.device))
+    elif ex:
+        _launch("hg_bias_relu_ln_bwd_ex", _ptr(h), a, _ptr(c), _ptr(bias), _ptr(gamma), _ptr(dy), R, C, eps, *outs, *fanned,
+                _stream(h.device))
+    else:
+        _launch("hg_bias_relu_ln_bwd", _ptr(h), _ptr(bias), _ptr(gamma), _ptr(dy), R, C, eps, *outs, _stream(h.device))
     if fan is not None:
         fan.n += 1
-    return dpre, acc, small, tg
+    return dpre, ((None,) * 3 if acc else tuple(_hand_out(list(small), tg)))
 
 
-class _BiasReluLnDrop(torch.autograd.Function):
-    """dropout_p(LayerNorm(relu(h + bias))) over dense rows in one launch each way (hg_bias_relu_ln_drop_*); the decision of
-    element [r, c] is that of flat index r * C + c."""
+class _BiasReluLn(torch.autograd.Function):
+    """LayerNorm(relu(h + bias)) over dense rows in one launch; the backward returns dh and, from the
+    same pass, the bias / gamma / beta gradients (csrc/incidence.hip).  ``p`` > 0: dropout_p of the result in the same
+    launch each way (hg_bias_relu_ln_drop_*); the decision of element [r, c] is that of flat index r * C + c."""
 
     @staticmethod
-    def forward(ctx, h, bias, gamma, beta, eps, acc_params, fan, p, seed):
+    def forward(ctx, h, bias, gamma, beta, eps, acc_params, fan=None, p=0.0, seed=None):
         _require_gpu(h, "bias_relu_ln")
         h, bias, gamma, beta = _f32c(h), _f32c(bias), _f32c(gamma), _f32c(beta)
         R, C = h.shape
-        seed = seed if seed is not None else _dropout_seed(h.device, p)
+        if p > 0.0 and seed is None:
+            seed = _dropout_seed(h.device, p)
         out = torch.empty_like(h)
-        hip.check(hip.lib().hg_bias_relu_ln_drop_fwd(_ptr(h), 1.0, None, _ptr(bias), _ptr(gamma), _ptr(beta), R, C, float(eps),
-                                                     p, _ptr(seed), _ptr(out), _stream(h.device)), "hg_bias_relu_ln_drop_fwd")
+        if p > 0.0:
+            _launch("hg_bias_relu_ln_drop_fwd", _ptr(h), 1.0, None, _ptr(bias), _ptr(gamma), _ptr(beta), R, C, float(eps), p,
+                    _ptr(seed), _ptr(out), _stream(h.device))
+        else:
+            _launch("hg_bias_relu_ln_fwd", _ptr(h), _ptr(bias), _ptr(gamma), _ptr(beta), R, C, float(eps), _ptr(out),
+                    _stream(h.device))
         ctx.save_for_backward(h, bias, gamma)
         ctx.meta = (float(eps), fan, p, seed)
-        ctx.acc = acc_params
+        ctx.acc = acc_params  # the Parameter objects (their accumulators are looked up at backward time)
         return out
 
     @staticmethod
     def backward(ctx, dy):
         h, bias, gamma = ctx.saved_tensors
         eps, fan, p, seed = ctx.meta
-        dh, acc, small, tg = _rowln_drop_bwd(ctx.acc, h, 1.0, None, bias, gamma, _f32c(dy), eps, p, seed, fan)
-        if acc:
-            return (dh,) + (None,) * 8
-        return (dh, *_hand_out(list(small), tg)) + (None,) * 5
+        dh, grads = _rowln_bwd(ctx.acc, h, 1.0, None, bias, gamma, _f32c(dy), eps, fan, p, seed, ex=fan is not None)
+        return (dh, *grads) + (None,) * 5
 
 
-class _LinearAddReluLnDrop(torch.autograd.Function):
-    """dropout_p(LayerNorm(relu(scale * (x @ W.T) + c + bias))): _LinearAddReluLn on the dropout kernels."""
+class _LinearAddReluLn(torch.autograd.Function):
+    """LayerNorm(relu(scale * (x @ W.T) + c + bias)): the GEMM writes x @ W.T, the addend c (beta = 1 in _LinearAddC, which
+    costs a copy of c into the GEMM's output per call) and the scale enter in the LayerNorm kernel
+    (hg_bias_relu_ln_fwd_ex / _bwd_ex; with ``p`` > 0 the dropout kernels, see _BiasReluLn).  Backward: the kernel returns
+    the gradient of the pre-activation; the two GEMMs take ``scale`` as their alpha; c's gradient goes to its GradFan
+    (summed over the applications) or to autograd."""
 
     @staticmethod
-    def forward(ctx, x, weight, c, scale, bias, gamma, beta, eps, fan, acc_params, p, seed):
+    def forward(ctx, x, weight, c, scale, bias, gamma, beta, eps, fan, acc_params, p=0.0, seed=None):
         _require_gpu(x, "linear_add_relu_ln")
         x, c, bias, gamma, beta = _f32c(x), _f32c(c), _f32c(bias), _f32c(gamma), _f32c(beta)
         h = mm_nt(x, weight)
         R, C = h.shape
-        seed = seed if seed is not None else _dropout_seed(x.device, p)
+        if p > 0.0 and seed is None:
+            seed = _dropout_seed(x.device, p)
+        fn, dargs = ("hg_bias_relu_ln_drop_fwd", (p, _ptr(seed))) if p > 0.0 else ("hg_bias_relu_ln_fwd_ex", ())
         out = torch.empty_like(h)
-        hip.check(hip.lib().hg_bias_relu_ln_drop_fwd(_ptr(h), float(scale), _ptr(c), _ptr(bias), _ptr(gamma), _ptr(beta), R, C,
-                                                     float(eps), p, _ptr(seed), _ptr(out), _stream(x.device)),
-                  "hg_bias_relu_ln_drop_fwd")
+        _launch(fn, _ptr(h), float(scale), _ptr(c), _ptr(bias), _ptr(gamma), _ptr(beta), R, C, float(eps),
+                *dargs, _ptr(out), _stream(x.device))
         ctx.save_for_backward(x, weight, h, c, bias, gamma)
         ctx.meta = (float(scale), float(eps), fan, p, seed)
         ctx.acc = acc_params
@@ -246,7 +236,7 @@ class _LinearAddReluLnDrop(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight, h, c, bias, gamma = ctx.saved_tensors
         a, eps, fan, p, seed = ctx.meta
-        dpre, acc, small, tg = _rowln_drop_bwd(ctx.acc, h, a, c, bias, gamma, _f32c(dy), eps, p, seed, fan)
+        dpre, grads = _rowln_bwd(ctx.acc, h, a, c, bias, gamma, _f32c(dy), eps, fan, p, seed, ex=True)
         dx = mm_nn(dpre, weight, alpha=a) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
@@ -262,201 +252,44 @@ class _LinearAddReluLnDrop(torch.autograd.Function):
             else:
                 dw = torch.addmm(weight, dpre.t(), x, beta=0.0, alpha=a)
         dc = dpre if (fan is None and ctx.needs_input_grad[2]) else None
-        if acc:
-            return (dx, dw, dc) + (None,) * 9
-        return (dx, dw, dc, None, *_hand_out(list(small), tg)) + (None,) * 5
-
-
-class _BiasReluLn(torch.autograd.Function):
-    """LayerNorm(relu(h + bias)) over dense rows in one launch; the backward returns dh and, from the
-    same pass, the bias / gamma / beta gradients (csrc/incidence.hip)."""
-
-    @staticmethod
-    def forward(ctx, h, bias, gamma, beta, eps, acc_params, fan=None):
-        _require_gpu(h, "bias_relu_ln")
-        h, bias, gamma, beta = _f32c(h), _f32c(bias), _f32c(gamma), _f32c(beta)
-        R, C = h.shape
-        out = torch.empty_like(h)
-        hip.check(hip.lib().hg_bias_relu_ln_fwd(_ptr(h), _ptr(bias), _ptr(gamma), _ptr(beta), R, C, float(eps),
-                                                _ptr(out), _stream(h.device)), "hg_bias_relu_ln_fwd")
-        ctx.save_for_backward(h, bias, gamma)
-        ctx.eps = eps
-        ctx.acc = acc_params  # the Parameter objects (their accumulators are looked up at backward time)
-        ctx.fan = fan
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        h, bias, gamma = ctx.saved_tensors
-        dy = _f32c(dy)
-        R, C = h.shape
-        dh = torch.empty_like(h)
-        L = hip.lib()
-        ws_bytes = L.hg_bias_relu_ln_bwd_workspace_bytes(R, C)
-        ws = _workspace(ws_bytes, h.device)
-        tg = [_acc_target(p) for p in ctx.acc]
-        acc = all(t is not None for t in tg)   # all three accumulate in place: nothing for autograd to add
-        small = None if acc else torch.empty((3, C), dtype=torch.float32, device=h.device)
-        o = tg if acc else list(small)
-        fan = ctx.fan
-        if fan is not None:     # dh is also the gradient of the fanned-out addend of this layer's input: summed in the kernel
-            if fan.buf is None:
-                fan.buf = torch.empty_like(h)
-            hip.check(L.hg_bias_relu_ln_bwd_ex(_ptr(h), 1.0, None, _ptr(bias), _ptr(gamma), _ptr(dy), R, C, float(ctx.eps), _ptr(dh),
-                                               _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), 1 if acc else 0, _ptr(ws), ws_bytes,
-                                               _ptr(fan.buf), 1 if fan.n == 0 else 0, _stream(h.device)),
-                      "hg_bias_relu_ln_bwd_ex")
-            fan.n += 1
-        else:
-            hip.check(L.hg_bias_relu_ln_bwd(_ptr(h), _ptr(bias), _ptr(gamma), _ptr(dy), R, C, float(ctx.eps), _ptr(dh),
-                                            _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), 1 if acc else 0, _ptr(ws), ws_bytes,
-                                            _stream(h.device)), "hg_bias_relu_ln_bwd")
-        if acc:
-            return dh, None, None, None, None, None, None
-        return (dh, *_hand_out(list(small), tg), None, None, None)
-
-
-class _LinearAddReluLn(torch.autograd.Function):
-    """LayerNorm(relu(scale * (x @ W.T) + c + bias)): the GEMM writes x @ W.T, the addend c (beta = 1 in _LinearAddC, which
-    costs a copy of c into the GEMM's output per call) and the scale enter in the LayerNorm kernel
-    (hg_bias_relu_ln_fwd_ex / _bwd_ex).  Backward: the kernel returns the gradient of the pre-activation; the two GEMMs
-    take ``scale`` as their alpha; c's gradient goes to its GradFan (summed over the applications) or to autograd."""
-
-    @staticmethod
-    def forward(ctx, x, weight, c, scale, bias, gamma, beta, eps, fan, acc_params):
-        _require_gpu(x, "linear_add_relu_ln")
-        x, c, bias, gamma, beta = _f32c(x), _f32c(c), _f32c(bias), _f32c(gamma), _f32c(beta)
-        h = mm_nt(x, weight)
-        R, C = h.shape
-        out = torch.empty_like(h)
-        hip.check(hip.lib().hg_bias_relu_ln_fwd_ex(_ptr(h), float(scale), _ptr(c), _ptr(bias), _ptr(gamma), _ptr(beta), R, C,
-                                                   float(eps), _ptr(out), _stream(x.device)), "hg_bias_relu_ln_fwd_ex")
-        ctx.save_for_backward(x, weight, h, c, bias, gamma)
-        ctx.meta = (float(scale), float(eps), fan)
-        ctx.acc = acc_params
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight, h, c, bias, gamma = ctx.saved_tensors
-        a, eps, fan = ctx.meta
-        dy = _f32c(dy)
-        R, C = h.shape
-        dpre = torch.empty_like(h)
-        L = hip.lib()
-        ws_bytes = L.hg_bias_relu_ln_bwd_workspace_bytes(R, C)
-        ws = _workspace(ws_bytes, h.device)
-        tg = [_acc_target(p) for p in ctx.acc]
-        acc = all(t is not None for t in tg)
-        small = None if acc else torch.empty((3, C), dtype=torch.float32, device=h.device)
-        o = tg if acc else list(small)
-        if fan is not None and fan.buf is None:
-            fan.buf = torch.empty_like(h)
-        hip.check(L.hg_bias_relu_ln_bwd_ex(_ptr(h), a, _ptr(c), _ptr(bias), _ptr(gamma), _ptr(dy), R, C, eps, _ptr(dpre),
-                                           _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), 1 if acc else 0, _ptr(ws), ws_bytes,
-                                           _ptr(fan.buf) if fan is not None else None, 1 if (fan is not None and fan.n == 0) else 0,
-                                           _stream(h.device)), "hg_bias_relu_ln_bwd_ex")
-        if fan is not None:
-            fan.n += 1
-        dx = mm_nn(dpre, weight, alpha=a) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1]:
-            gbuf = getattr(weight, "_eqh_gbuf", None)
-            if gbuf is not None and _wgrad_deferred(dpre, x, a, gbuf):
-                pass
-            elif gbuf is not None and _wgrad_ok(dpre, x):
-                wgrad(dpre, x, a, into=gbuf)
-            elif gbuf is not None:
-                gbuf.addmm_(dpre.t(), x, alpha=a)
-            elif _wgrad_ok(dpre, x):
-                dw = wgrad(dpre, x, a)
-            else:
-                dw = torch.addmm(weight, dpre.t(), x, beta=0.0, alpha=a)
-        dc = dpre if (fan is None and ctx.needs_input_grad[2]) else None
-        if acc:
-            return dx, dw, dc, None, None, None, None, None, None, None
-        return (dx, dw, dc, None, *_hand_out(list(small), tg), None, None, None)
+        return (dx, dw, dc, None, *grads) + (None,) * 5
 
 
 def linear_add_relu_ln(x, weight, c, scale, bias, gamma, beta, eps: float = 1e-5, fan=None, p: float = 0.0, seed=None):
     """bias_relu_ln(linear_add(x, weight, c, scale), bias, gamma, beta) with the addend and the scale applied inside the
     LayerNorm kernel (2-D fp32 x, c on the GPU); see _LinearAddReluLn.  ``p``, ``seed``: dropout behind the LayerNorm, see
     bias_relu_ln."""
-    p, drop = _drop_route(p, "linear_add_relu_ln")
+    p, _ = _drop_route(p, "linear_add_relu_ln")
     if p >= 1.0:
         return _Zeros.apply((x.shape[0], weight.shape[0]), x, weight, c, bias, gamma, beta)
     if torch.is_grad_enabled() and weight.requires_grad and weight.is_leaf and not hasattr(weight, "_eqh_transient"):
         LINEAR_PARAMS[id(weight)] = weight
     _note_acc(bias, gamma, beta)
-    if drop:
-        return _LinearAddReluLnDrop.apply(x, weight, c, scale, bias, gamma, beta, eps, fan, (bias, gamma, beta), p, seed)
-    return _LinearAddReluLn.apply(x, weight, c, scale, bias, gamma, beta, eps, fan, (bias, gamma, beta))
+    return _LinearAddReluLn.apply(x, weight, c, scale, bias, gamma, beta, eps, fan, (bias, gamma, beta), p, seed)
 
 
 class _GatherLnReduce(torch.autograd.Function):
     """out[r] = gamma * reduce_{q in row r of csr} xhat(relu(h[csr.col[q]] + bias)) + beta * [..]: the hidden layer of an
     MLP on dense rows followed by the gathered reduction that is its only consumer, one launch each way
-    (hg_gather_ln_reduce_*; csrc/incidence.hip)."""
+    (hg_gather_ln_reduce_*; csrc/incidence.hip).  ``p`` > 0: dropout behind the LayerNorm, decided per SOURCE row (element
+    src * C + c): dropout of the [N, C] hidden tensor followed by the gathered reduction, without that tensor
+    (hg_gather_ln_reduce_drop_*)."""
 
     @staticmethod
-    def forward(ctx, h, bias, gamma, beta, csr, csr_t, mean, eps, acc_params):
+    def forward(ctx, h, bias, gamma, beta, csr, csr_t, mean, eps, acc_params, p=0.0, seed=None):
         _require_gpu(h, "gather_ln_reduce")
         h, bias, gamma, beta = _f32c(h), _f32c(bias), _f32c(gamma), _f32c(beta)
         R, C = h.shape
         if csr_t.n_rows != R:
             raise ValueError("gather_ln_reduce: the transposed CSR must have one row per row of h")
+        if p > 0.0 and seed is None:
+            seed = _dropout_seed(h.device, p)
+        fn, dargs = ("hg_gather_ln_reduce_drop_fwd", (p, _ptr(seed))) if p > 0.0 else ("hg_gather_ln_reduce_fwd", ())
         out = torch.empty((csr.n_rows, C), dtype=torch.float32, device=h.device)
-        timed("k_gather_ln_fwd", segment_reduce_bytes(csr.nnz, csr.n_rows, C, True, True, False),
-              lambda: hip.check(hip.lib().hg_gather_ln_reduce_fwd(_ptr(h), _ptr(bias), _ptr(gamma), _ptr(beta),
-                                                                  _ptr(csr.rowptr), _ptr(csr.col), csr.n_rows, C, int(mean),
-                                                                  float(eps), _ptr(out), _stream(h.device)),
-                                "hg_gather_ln_reduce_fwd"))
-        ctx.save_for_backward(h, bias, gamma)
-        ctx.eps, ctx.acc, ctx.csr_t = eps, acc_params, csr_t
-        ctx.ew = entry_weights(csr_t, csr) if mean else None    # once per batch (cached on the CSR)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        h, bias, gamma = ctx.saved_tensors
-        dout = _f32c(dout)
-        R, C = h.shape
-        t = ctx.csr_t
-        dh = torch.empty_like(h)
-        L = hip.lib()
-        ws_bytes = L.hg_gather_ln_reduce_bwd_workspace_bytes(R, C)
-        ws = _workspace(ws_bytes, h.device)
-        tg = [_acc_target(p) for p in ctx.acc]
-        acc = all(x is not None for x in tg)
-        small = None if acc else torch.empty((3, C), dtype=torch.float32, device=h.device)
-        o = tg if acc else list(small)
-        timed("k_gather_ln_bwd", segment_reduce_bytes(t.nnz, R, C, True, True, False) + 4 * t.nnz + 4 * C * R,
-              lambda: hip.check(L.hg_gather_ln_reduce_bwd(_ptr(h), _ptr(bias), _ptr(gamma), _ptr(dout), _ptr(t.rowptr),
-                                                          _ptr(t.col), _ptr(ctx.ew), R, C, float(ctx.eps), _ptr(dh),
-                                                          _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), 1 if acc else 0, _ptr(ws),
-                                                          ws_bytes, _stream(h.device)), "hg_gather_ln_reduce_bwd"))
-        if acc:
-            return (dh,) + (None,) * 8
-        return (dh, *_hand_out(list(small), tg), None, None, None, None, None)
-
-
-class _GatherLnReduceDrop(torch.autograd.Function):
-    """_GatherLnReduce with dropout behind the LayerNorm, decided per SOURCE row (element src * C + c): dropout of the [N, C]
-    hidden tensor followed by the gathered reduction, without that tensor (hg_gather_ln_reduce_drop_*)."""
-
-    @staticmethod
-    def forward(ctx, h, bias, gamma, beta, csr, csr_t, mean, eps, acc_params, p, seed):
-        _require_gpu(h, "gather_ln_reduce")
-        h, bias, gamma, beta = _f32c(h), _f32c(bias), _f32c(gamma), _f32c(beta)
-        R, C = h.shape
-        if csr_t.n_rows != R:
-            raise ValueError("gather_ln_reduce: the transposed CSR must have one row per row of h")
-        seed = seed if seed is not None else _dropout_seed(h.device, p)
-        out = torch.empty((csr.n_rows, C), dtype=torch.float32, device=h.device)
-        timed("k_gather_ln_drop_fwd", segment_reduce_bytes(csr.nnz, csr.n_rows, C, True, True, False),
-              lambda: hip.check(hip.lib().hg_gather_ln_reduce_drop_fwd(
-                  _ptr(h), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(csr.rowptr), _ptr(csr.col), csr.n_rows, C, int(mean),
-                  float(eps), p, _ptr(seed), _ptr(out), _stream(h.device)), "hg_gather_ln_reduce_drop_fwd"))
+        timed("k_gather_ln_drop_fwd" if p > 0.0 else "k_gather_ln_fwd",
+              segment_reduce_bytes(csr.nnz, csr.n_rows, C, True, True, False),
+              lambda: _launch(fn, _ptr(h), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(csr.rowptr),
+                              _ptr(csr.col), csr.n_rows, C, int(mean), float(eps), *dargs, _ptr(out), _stream(h.device)))
         ctx.save_for_backward(h, bias, gamma)
         ctx.meta = (eps, csr_t, p, seed)
         ctx.acc = acc_params
@@ -471,33 +304,27 @@ class _GatherLnReduceDrop(torch.autograd.Function):
         R, C = h.shape
         dh = torch.empty_like(h)
         L = hip.lib()
-        ws_bytes = L.hg_gather_ln_reduce_drop_bwd_workspace_bytes(R, C)
+        fn, dargs = ("hg_gather_ln_reduce_drop_bwd", (p, _ptr(seed))) if p > 0.0 else ("hg_gather_ln_reduce_bwd", ())
+        ws_bytes = (L.hg_gather_ln_reduce_drop_bwd_workspace_bytes if p > 0.0 else L.hg_gather_ln_reduce_bwd_workspace_bytes)(R, C)
         ws = _workspace(ws_bytes, h.device)
-        tg = [_acc_target(q) for q in ctx.acc]
-        acc = all(x is not None for x in tg)
-        small = None if acc else torch.empty((3, C), dtype=torch.float32, device=h.device)
-        o = tg if acc else list(small)
-        timed("k_gather_ln_drop_bwd", segment_reduce_bytes(t.nnz, R, C, True, True, False) + 4 * t.nnz + 4 * C * R,
-              lambda: hip.check(L.hg_gather_ln_reduce_drop_bwd(
-                  _ptr(h), _ptr(bias), _ptr(gamma), _ptr(dout), _ptr(t.rowptr), _ptr(t.col), _ptr(ctx.ew), R, C, float(eps), p,
-                  _ptr(seed), _ptr(dh), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), 1 if acc else 0, _ptr(ws), ws_bytes,
-                  _stream(h.device)), "hg_gather_ln_reduce_drop_bwd"))
-        if acc:
-            return (dh,) + (None,) * 10
-        return (dh, *_hand_out(list(small), tg)) + (None,) * 7
+        tg, acc, small, o = _param_grads(ctx.acc, 3, C, h.device)
+        timed("k_gather_ln_drop_bwd" if p > 0.0 else "k_gather_ln_bwd",
+              segment_reduce_bytes(t.nnz, R, C, True, True, False) + 4 * t.nnz + 4 * C * R,
+              lambda: _launch(fn, _ptr(h), _ptr(bias), _ptr(gamma), _ptr(dout), _ptr(t.rowptr),
+                              _ptr(t.col), _ptr(ctx.ew), R, C, float(eps), *dargs, _ptr(dh), _ptr(o[0]), _ptr(o[1]),
+                              _ptr(o[2]), 1 if acc else 0, _ptr(ws), ws_bytes, _stream(h.device)))
+        return (dh, *((None,) * 3 if acc else _hand_out(list(small), tg))) + (None,) * 7
 
 
 def gather_ln_reduce(h, bias, gamma, beta, csr: CSR, csr_t: CSR, reduce: str = "mean", eps: float = 1e-5, p: float = 0.0,
                      seed=None):
     """reduce_gathered(bias_relu_ln(h, bias, gamma, beta), csr, csr_t, reduce) in one launch each way (2-D h).  ``p``,
     ``seed``: dropout of the hidden rows (decided per source row, before the gather), see bias_relu_ln."""
-    p, drop = _drop_route(p, "gather_ln_reduce")
+    p, _ = _drop_route(p, "gather_ln_reduce")
     if p >= 1.0:
         return _Zeros.apply((csr.n_rows, h.shape[1]), h, bias, gamma, beta)
     _note_acc(bias, gamma, beta)
-    if drop:
-        return _GatherLnReduceDrop.apply(h, bias, gamma, beta, csr, csr_t, reduce == "mean", eps, (bias, gamma, beta), p, seed)
-    return _GatherLnReduce.apply(h, bias, gamma, beta, csr, csr_t, reduce == "mean", eps, (bias, gamma, beta))
+    return _GatherLnReduce.apply(h, bias, gamma, beta, csr, csr_t, reduce == "mean", eps, (bias, gamma, beta), p, seed)
 
 
 class _BatchNormRows(torch.autograd.Function):
@@ -607,15 +434,12 @@ def incidence_ln_reduce(pa, qb, gamma, beta, ia32, ib32, csr_a: CSR, csr_b: CSR,
     """reduce_{p in out row} LayerNorm(relu(pa[ia[p]] + qb[ib[p]])); csr_a / csr_b are the incidence
     CSRs keyed by ia / ib (needed by the backward), out_csr the one keyed by okey32.  ``p``, ``seed``: dropout of the
     per-incidence hidden rows, decided per incidence (its position in ia32 / ib32), see bias_relu_ln."""
-    p, drop = _drop_route(p, "incidence_ln_reduce")
+    p, _ = _drop_route(p, "incidence_ln_reduce")
     if p >= 1.0:
         return _Zeros.apply((out_csr.n_rows, pa.shape[1]), pa, qb, gamma, beta)
     _note_acc(gamma, beta)
-    if drop:
-        return _IncidenceLnReduceDrop.apply(pa, qb, gamma, beta, ia32, ib32, csr_a, csr_b, out_csr, okey32,
-                                            reduce == "mean", eps, (gamma, beta), p, seed)
     return _IncidenceLnReduce.apply(pa, qb, gamma, beta, ia32, ib32, csr_a, csr_b, out_csr, okey32,
-                                    reduce == "mean", eps, (gamma, beta))
+                                    reduce == "mean", eps, (gamma, beta), p, seed)
 
 
 def bias_relu_ln(h, bias, gamma, beta, eps: float = 1e-5, fan=None, p: float = 0.0, seed=None):
@@ -623,13 +447,11 @@ def bias_relu_ln(h, bias, gamma, beta, eps: float = 1e-5, fan=None, p: float = 0
     ``p`` > 0: dropout_p of the result in the same launch (mlp.py:97), keep = 0 or 1 / (1 - p) from the hash of (seed,
     element index) -- ``seed``: an int64 tensor of one element on the device, or None for a draw from the pool of
     ops.dropout_seeds.  p = 0 is the call without the argument; p >= 1 gives zeros."""
-    p, drop = _drop_route(p, "bias_relu_ln")
+    p, _ = _drop_route(p, "bias_relu_ln")
     if p >= 1.0:
         return _Zeros.apply(tuple(h.shape), h, bias, gamma, beta)
     _note_acc(bias, gamma, beta)
-    if drop:
-        return _BiasReluLnDrop.apply(h, bias, gamma, beta, eps, (bias, gamma, beta), fan, p, seed)
-    return _BiasReluLn.apply(h, bias, gamma, beta, eps, (bias, gamma, beta), fan)
+    return _BiasReluLn.apply(h, bias, gamma, beta, eps, (bias, gamma, beta), fan, p, seed)
 
 
 class _ResidualMix(torch.autograd.Function):

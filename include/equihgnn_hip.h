@@ -662,7 +662,7 @@ int hg_gather_ln_reduce_bwd(const float* h, const float* bias, const float* gamm
                             int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * The three hidden-layer kernels above with the training dropout of mlp.py:97 behind the LayerNorm (csrc/conv_dropout.hip):
+ * The three hidden-layer kernels above with the training dropout of mlp.py:97 behind the LayerNorm (the DROP instantiations of csrc/incidence.hip):
  *   keep = 0 or 1 / (1 - p), decided by the hash of (*seed, element index) of csrc/drop_hash.h, as in the faf_* entries:
  *   seed is a DEVICE pointer (a new value per hipGraph replay), 0 <= p < 1 (else EQH_ERR_ARG), the realised drop
  *   probability is round(p 2^16) / 2^16.  No mask is stored: every backward recomputes the decisions from the same seed.

@@ -1,4 +1,4 @@
-"""Host-side checks of the conv-tail dropout (no GPU): the entry points of csrc/conv_dropout.hip are declared and
+"""Host-side checks of the conv-tail dropout (no GPU): the *_drop_* entry points of csrc/incidence.hip are declared and
 exported, validate their arguments before any launch, the package switch reaches its owner, and the operators handle the
 ends of the probability range before they touch a device."""
 import ctypes

@@ -1,4 +1,4 @@
-"""Training dropout of the hypergraph convs on the fused row kernels (csrc/conv_dropout.hip, ops/rows.py, layers.py,
+"""Training dropout of the hypergraph convs on the fused row kernels (csrc/incidence.hip, ops/rows.py, layers.py,
 models.py): the dropout forms of bias_relu_ln / linear_add_relu_ln, gather_ln_reduce and incidence_ln_reduce against float64,
 the properties of the hashed masks, p = 0 left as it was, and the layers / models in training mode with p > 0.
 

@@ -4,7 +4,7 @@ bench.py).  Prints ONE JSON line and writes it to ``--out`` (default profiles/co
 
 * the replayed training step (GraphedTrainStep; QM9-like, batch 256, hidden 256) of ``egnn_equihnns`` and ``mhnnm`` in three
   variants -- ``p0`` (dropout 0: the headline's path), ``p0.1_fused`` (dropout 0.1, ``ops.FUSED_DROPOUT = True``: the hidden
-  layers' dropout inside the row kernels, csrc/conv_dropout.hip) and ``p0.1_aten`` (dropout 0.1 with the switch off: ReLU,
+  layers' dropout inside the row kernels, csrc/incidence.hip) and ``p0.1_aten`` (dropout 0.1 with the switch off: ReLU,
   LayerNorm and F.dropout as ATen launches on materialised rows, the path before the switch existed).  One model and one
   trainer per variant, fed copies of the same resident batches; after a warm-up the variants run in interleaved blocks of
   ``--steps`` steps on a host clock around a device synchronise.  The switch is set ahead of every block, so a capture that
