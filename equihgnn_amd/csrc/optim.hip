@@ -8,6 +8,11 @@
 //   The learning rate and the step counter live in device memory, so a captured hipGraph keeps working
 //   when a scheduler changes the rate; the counter is advanced by the last workgroup to finish (a ticket
 //   in the state block), after every workgroup has read it.
+// eqh_grad_sumsq + eqh_adam_step_clip: the same update behind torch.nn.utils.clip_grad_norm_ (norm_type 2,
+//   error_if_nonfinite False) of grad * grad_scale.  A first launch leaves one double partial of sum g^2 per workgroup;
+//   the update (k_adam<true>) sums them in a fixed order in front of its bias corrections -- the kernel boundary is the
+//   ordering between the two stages, no ticket, no fence, no atomics -- and folds min(1, max_norm / (norm + 1e-6)) into
+//   the gradient scale.  Workgroup 0 keeps a 4-float readout {norm, coef, running max of norm, steps with coef < 1}.
 // eqh_copy_many: up to 64 small device-to-device copies in one launch (gradients that autograd allocated,
 //   packed into the flat gradient buffer).
 #include "common.h"
@@ -20,9 +25,62 @@ struct AdamState {       // device memory, 16 bytes, zero-initialised by the cal
     unsigned int pad;
 };
 
+// The sum-of-squares pass: SQ_U quads per thread and trip, as k_adam's load (all loads of a trip requested before the
+// first is used), at most SQ_GRID workgroups, g * g accumulated in double.  Every workgroup of the grid writes its slot,
+// also one that found no element: the workspace is never cleared.
+constexpr int SQ_U = 4;
+constexpr int SQ_GRID = 256;
+static inline int sumsq_grid(int64_t n) { return eqh_grid_for(n >> 2, 256 * SQ_U, SQ_GRID); }
+
+__global__ void __launch_bounds__(256)
+k_sumsq(const float* __restrict__ g, int64_t n, double* __restrict__ partials) {
+    const int64_t n4 = n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x * SQ_U;
+    double acc[SQ_U];
+#pragma unroll
+    for (int u = 0; u < SQ_U; ++u) acc[u] = 0.0;
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x * SQ_U + threadIdx.x; i0 < n4; i0 += stride) {
+        float4 gg[SQ_U];
+#pragma unroll
+        for (int u = 0; u < SQ_U; ++u) {
+            const int64_t i = i0 + (int64_t)u * blockDim.x;
+            gg[u] = i < n4 ? reinterpret_cast<const float4*>(g)[i] : f4_zero();
+        }
+#pragma unroll
+        for (int u = 0; u < SQ_U; ++u) {
+            const double x = gg[u].x, y = gg[u].y, z = gg[u].z, w = gg[u].w;
+            acc[u] = fma(w, w, fma(z, z, fma(y, y, fma(x, x, acc[u]))));
+        }
+    }
+    if (blockIdx.x == 0 && 4 * n4 + threadIdx.x < n) {  // ragged tail (n not a multiple of 4; all of it when n < 4)
+        const double x = g[4 * n4 + threadIdx.x];
+        acc[0] = fma(x, x, acc[0]);
+    }
+    // fixed order: the thread's accumulators as a tree, the wavefront by halving distances, the four wavefronts in turn
+    double s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+#pragma unroll
+    for (int off = EQH_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off);
+    __shared__ double s_wave[256 / EQH_WAVE];
+    if ((threadIdx.x & (EQH_WAVE - 1)) == 0) s_wave[threadIdx.x / EQH_WAVE] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+}
+
+// What stands where k_adam's `float gscale` stood: for CLIP = false that float alone (same size, same offset: the
+// unclipped kernel keeps its argument block), for CLIP = true the clip's arguments behind it.
+template <bool CLIP> struct ClipArgs { float gscale; };
+template <> struct ClipArgs<true> {
+    float gscale;
+    float max_norm;
+    const double* partials;   // n_partials doubles of k_sumsq
+    float* readout;           // {norm before clipping, coef, running max of norm, steps with coef < 1}
+    int n_partials;
+};
+
+template <bool CLIP>
 __global__ void __launch_bounds__(256)
 k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-       const float* __restrict__ lr_ptr, float beta1, float beta2, float eps, float wd, float gscale,
+       const float* __restrict__ lr_ptr, float beta1, float beta2, float eps, float wd, ClipArgs<CLIP> ca,
        AdamState* __restrict__ st, int zero_grad, float* __restrict__ zero_also, int64_t zero_also_n) {
     // AD_U quads per thread and pass, all sixteen 16-byte loads of a pass requested before anything else -- before the bias
     // corrections are worked out, too (the step counter's load, two powf and a barrier otherwise sit in front of every memory
@@ -47,15 +105,42 @@ k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, floa
     };
     load(i0);
     // the bias corrections once per workgroup (two powf per THREAD were most of the kernel's instructions)
-    __shared__ float s_corr[2];
+    __shared__ float s_corr[CLIP ? 3 : 2];
     if (threadIdx.x == 0) {
         const float t = (float)(st->step + 1);
         s_corr[0] = *lr_ptr / (1.0f - powf(beta1, t));
         s_corr[1] = sqrtf(1.0f - powf(beta2, t));
     }
+    if constexpr (CLIP) {
+        // the second stage of the norm, by the first wavefront of EVERY workgroup in one fixed order (so all of them scale
+        // by the same bits): lane l sums partials l, l + 64, ..., then the lanes by halving distances
+        if (threadIdx.x < EQH_WAVE) {
+            double s = 0.0;
+            for (int k = threadIdx.x; k < ca.n_partials; k += EQH_WAVE) s += ca.partials[k];
+#pragma unroll
+            for (int off = EQH_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off);
+            if (threadIdx.x == 0) {
+                // clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max = 1); a NaN coef stays NaN, as torch.clamp keeps it
+                const float total_norm = (float)(sqrt(s) * (double)ca.gscale);
+                float coef = ca.max_norm / (total_norm + 1e-6f);
+                coef = coef > 1.0f ? 1.0f : coef;
+                s_corr[2] = ca.gscale * coef;
+                if (blockIdx.x == 0) {
+                    float* r = ca.readout;
+                    const float seen = r[2], clipped = r[3];
+                    r[0] = total_norm;
+                    r[1] = coef;
+                    r[2] = total_norm > seen ? total_norm : seen;
+                    r[3] = coef < 1.0f ? clipped + 1.0f : clipped;
+                }
+            }
+        }
+    }
     __syncthreads();
     const float step_size = s_corr[0];
     const float bc2_sqrt = s_corr[1];
+    float gscale = ca.gscale;
+    if constexpr (CLIP) gscale = s_corr[2];
     for (; i0 < n4; i0 += stride) {
 #pragma unroll
         for (int u = 0; u < AD_U; ++u) {
@@ -156,22 +241,60 @@ extern "C" int eqh_mse_fwd_bwd(const float* pred, const float* target, int32_t n
     return EQH_OK;
 }
 
-extern "C" int eqh_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                             const float* lr, float beta1, float beta2, float eps, float weight_decay,
-                             float grad_scale, void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n,
-                             void* stream_) {
+// eqh_adam_step (CLIP = false) and eqh_adam_step_clip (CLIP = true): one set of argument checks, one launch
+template <bool CLIP>
+static int adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr, float beta1,
+                     float beta2, float eps, float weight_decay, ClipArgs<CLIP> ca, void* state, int32_t zero_grad,
+                     float* zero_also, int64_t zero_also_n, void* stream_) {
     if (n < 0 || !lr || !state) return EQH_ERR_ARG;
+    if constexpr (CLIP) {
+        if (!ca.partials || !ca.readout || !(ca.max_norm > 0.f)) return EQH_ERR_ARG;
+    }
     if (n == 0) return EQH_OK;
     if (!param || !grad || !exp_avg || !exp_avg_sq) return EQH_ERR_ARG;
     if (zero_also_n < 0 || (zero_also_n > 0 && !zero_also) || (zero_also_n & 3) || !eqh_aligned16(zero_also)) return EQH_ERR_ARG;
     if (!eqh_aligned16(param) || !eqh_aligned16(grad) || !eqh_aligned16(exp_avg) || !eqh_aligned16(exp_avg_sq) ||
         ((uintptr_t)state & 7))
         return EQH_ERR_ALIGN;
-    hipLaunchKernelGGL(k_adam, dim3(eqh_grid_for(n / 16 + 1, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(stream_),
-                       param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, grad_scale,
+    if constexpr (CLIP) {
+        if (((uintptr_t)ca.partials & 7) || !eqh_aligned16(ca.readout)) return EQH_ERR_ALIGN;
+    }
+    hipLaunchKernelGGL(k_adam<CLIP>, dim3(eqh_grid_for(n / 16 + 1, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(stream_),
+                       param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, ca,
                        static_cast<AdamState*>(state), (int)zero_grad, zero_also, zero_also_n);
     EQH_CHECK_LAUNCH();
     return EQH_OK;
+}
+
+extern "C" int eqh_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                             const float* lr, float beta1, float beta2, float eps, float weight_decay,
+                             float grad_scale, void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n,
+                             void* stream_) {
+    return adam_step<false>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                            ClipArgs<false>{grad_scale}, state, zero_grad, zero_also, zero_also_n, stream_);
+}
+
+extern "C" size_t eqh_grad_sumsq_workspace_bytes(int64_t n) {
+    return n < 0 ? 0 : (size_t)sumsq_grid(n) * sizeof(double);
+}
+
+extern "C" int eqh_grad_sumsq(const float* grad, int64_t n, void* partials, void* stream_) {
+    if (n < 0 || !partials || (n > 0 && !grad)) return EQH_ERR_ARG;
+    if (!eqh_aligned16(grad) || ((uintptr_t)partials & 7)) return EQH_ERR_ALIGN;
+    hipLaunchKernelGGL(k_sumsq, dim3(sumsq_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream_), grad, n,
+                       static_cast<double*>(partials));
+    EQH_CHECK_LAUNCH();
+    return EQH_OK;
+}
+
+extern "C" int eqh_adam_step_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                  const float* lr, float beta1, float beta2, float eps, float weight_decay,
+                                  float grad_scale, void* state, int32_t zero_grad, float* zero_also,
+                                  int64_t zero_also_n, const void* partials, float max_norm, float* readout,
+                                  void* stream_) {
+    return adam_step<true>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                           ClipArgs<true>{grad_scale, max_norm, static_cast<const double*>(partials), readout, sumsq_grid(n)},
+                           state, zero_grad, zero_also, zero_also_n, stream_);
 }
 
 extern "C" int eqh_copy_many(int32_t count, const float* const* src, float* const* dst, const int64_t* n,

@@ -426,9 +426,14 @@ class FitResult:
 class Fitter:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  std: Optional[float] = None, patience_lr: int = 10, patience_stop: int = 50,
-                 step_factory: Callable = TrainStep, metric_seed: int = 0):
+                 step_factory: Callable = TrainStep, metric_seed: int = 0, clip_gnorm: Optional[float] = None):
+        """``clip_gnorm``: global-norm gradient clipping in the training step (the reference's ``--clip_gnorm``, which its
+        Trainer never receives: off by default).  Handed to ``step_factory`` only when given, so a factory without the
+        keyword keeps working; each epoch's history row then carries ``grad_norm_max`` and ``clipped_steps``."""
         self.model, self.lr, self.std = model, lr, std
-        self.step = step_factory(model, lr=lr, weight_decay=weight_decay)
+        self.clip_gnorm = clip_gnorm
+        extra = {} if clip_gnorm is None else {"clip_gnorm": clip_gnorm}
+        self.step = step_factory(model, lr=lr, weight_decay=weight_decay, **extra)
         self.metrics = BootstrapMetrics(50, metric_seed)
         self.patience_lr, self.patience_stop = patience_lr, patience_stop
         self.sched = None
@@ -486,6 +491,11 @@ class Fitter:
             lr_now = self.step.opt.param_groups[0]["lr"] if self.step.opt is not None else self.lr
             res.history.append({"epoch": epoch, "train_loss": tot / max(n, 1), "lr": float(lr_now),
                                 **{"val_" + k: v for k, v in val.items()}})
+            readout = getattr(self.step, "grad_norm", None) if self.clip_gnorm is not None else None
+            if readout is not None:         # ONE read of the step's readout per epoch, then its running pair starts again
+                _, _, seen, clipped = readout.tolist()
+                readout[2:].zero_()
+                res.history[-1].update(grad_norm_max=seen, clipped_steps=int(clipped))
             if self.sched is not None:
                 self.sched.step(val["mae_mean"])
             if val["mae_mean"] < res.best_val_mae:     # ModelCheckpoint(save_top_k=1) + EarlyStopping

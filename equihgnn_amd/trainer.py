@@ -54,10 +54,16 @@ class TrainStep:
     with the CPU oracle, the GPU path with the HIP models)."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
-                 broadcast_from_rank0: bool = True, on_batch: Optional[Callable] = None):
+                 broadcast_from_rank0: bool = True, on_batch: Optional[Callable] = None,
+                 clip_gnorm: Optional[float] = None):
+        """``clip_gnorm``: clip the rank-averaged gradient by its global L2 norm before the update
+        (``torch.nn.utils.clip_grad_norm_``; the reference's ``--clip_gnorm``, main.py:175, which its Trainer never
+        receives -- so the default, and the reference's behaviour, is off)."""
         self.model = model
         self.lr, self.wd = lr, weight_decay
         self.on_batch = on_batch
+        self.clip_gnorm = None if clip_gnorm is None else float(clip_gnorm)
+        self.grad_norm: Optional[torch.Tensor] = None   # {norm before clipping, coef, running max of norm, clipped steps}
         self.flat: Optional[FlatGradients] = None
         self.opt: Optional[torch.optim.Optimizer] = None
         if broadcast_from_rank0 and _world() > 1:  # DDP broadcasts rank 0's parameters at wrap time
@@ -89,8 +95,25 @@ class TrainStep:
             loss = F.mse_loss(self.model(data), data.y)
             loss.backward()
         self.flat.all_reduce_mean()
+        if self.clip_gnorm is not None:
+            self._clip()
         self.opt.step()
         return loss.detach()
+
+    @torch.no_grad()
+    def _clip(self):
+        """clip_grad_norm_(norm_type=2, error_if_nonfinite=False) of the flat buffer, which the averaged gradient of every
+        live parameter tiles exactly: torch's own norm over the per-parameter views, ONE in-place scaling of the buffer, and
+        the readout kept on its device (no sync here; whoever reads ``grad_norm`` pays for it)."""
+        total = torch.nn.utils.get_total_norm([p.grad for p in self.flat.params], 2.0)
+        coef = torch.clamp(self.clip_gnorm / (total + 1e-6), max=1.0)
+        self.flat.flat.mul_(coef)
+        if self.grad_norm is None:
+            self.grad_norm = torch.zeros(4, dtype=torch.float32, device=self.flat.flat.device)
+        r = self.grad_norm
+        r[0], r[1] = total, coef
+        r[2] = torch.where(total > r[2], total.to(r.dtype), r[2])
+        r[3] += (coef < 1.0).to(r.dtype)
 
     def sync_buffers(self):
         """DDP's per-forward buffer broadcast (BatchNorm running stats of ``mhnnm``)."""
@@ -104,10 +127,22 @@ class FlatAdam(torch.optim.Optimizer):
     kernel instead of the multi-tensor kernel's one block per 64 Ki elements (12 us against 46 us for the
     2.6 M parameters of egnn_equihnns).  Learning rate and step counter live in device memory, so a
     captured hipGraph follows a scheduler (``sync_lr`` before each replay); ``grad_scale`` folds the
-    1 / world_size of the gradient average into the update."""
+    1 / world_size of the gradient average into the update.
 
-    def __init__(self, param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_(.., max_grad_norm)`` of ``grad * grad_scale`` inside the step, without
+    a host round trip: ``step()`` then makes two launches on the optimiser's stream, both capturable -- eqh_grad_sumsq (per
+    workgroup partial sums of squares, in double) and eqh_adam_step_clip (sums them, scales the gradient by
+    min(1, max / (norm + 1e-6)), updates).  The threshold is FIXED at construction: it is a kernel argument of a captured
+    graph, which a replay does not read again.  ``grad_norm``: 4 floats on the device, {norm before clipping, coef, running
+    maximum of the norm, number of steps with coef < 1}; the kernel keeps the last two running, the reader zeroes them.
+    ``None`` (default): one eqh_adam_step call, as before, and ``grad_norm`` is ``None``."""
+
+    def __init__(self, param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         super().__init__([param], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"FlatAdam: max_grad_norm must be positive (got {max_grad_norm})")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None
         self.grad_scale = 1.0
         self.zero_grad_in_step = False      # clear the flat gradient inside the update kernel (GraphedTrainStep)
         self.zero_also = None               # callable -> a second buffer the update clears (the owner's MergedScratch)
@@ -118,6 +153,11 @@ class FlatAdam(torch.optim.Optimizer):
         st["step_block"] = torch.zeros(2, dtype=torch.int64, device=param.device)   # {step, ticket}
         st["lr"] = torch.tensor([float(lr)], dtype=torch.float32, device=param.device)
         self._lr_dev = float(lr)
+        if self.max_grad_norm is not None:
+            from . import hip
+            nbytes = hip.lib().eqh_grad_sumsq_workspace_bytes(param.numel())
+            st["clip_partials"] = torch.empty(nbytes // 8, dtype=torch.float64, device=param.device)   # never cleared
+            self.grad_norm = torch.zeros(4, dtype=torch.float32, device=param.device)
 
     def sync_lr(self):
         """Mirror param_groups[0]['lr'] (what schedulers write) into the device scalar; outside capture."""
@@ -135,12 +175,18 @@ class FlatAdam(torch.optim.Optimizer):
         st = self.state[p]
         b1, b2 = g["betas"]
         zs = self.zero_also() if (self.zero_grad_in_step and self.zero_also is not None) else None
-        hip.check(hip.lib().eqh_adam_step(ops._ptr(p.data), ops._ptr(p.grad), ops._ptr(st["exp_avg"]),
-                                          ops._ptr(st["exp_avg_sq"]), p.numel(), ops._ptr(st["lr"]), b1, b2, g["eps"],
-                                          g["weight_decay"], self.grad_scale, ops._ptr(st["step_block"]),
-                                          1 if self.zero_grad_in_step else 0,
-                                          ops._ptr(zs) if zs is not None else None, zs.numel() if zs is not None else 0,
-                                          ops._stream(p.device)), "eqh_adam_step")
+        stream = ops._stream(p.device)
+        args = (ops._ptr(p.data), ops._ptr(p.grad), ops._ptr(st["exp_avg"]), ops._ptr(st["exp_avg_sq"]), p.numel(),
+                ops._ptr(st["lr"]), b1, b2, g["eps"], g["weight_decay"], self.grad_scale, ops._ptr(st["step_block"]),
+                1 if self.zero_grad_in_step else 0, ops._ptr(zs) if zs is not None else None,
+                zs.numel() if zs is not None else 0)
+        if self.max_grad_norm is None:
+            hip.check(hip.lib().eqh_adam_step(*args, stream), "eqh_adam_step")
+            return
+        partials = ops._ptr(st["clip_partials"])
+        hip.check(hip.lib().eqh_grad_sumsq(ops._ptr(p.grad), p.numel(), partials, stream), "eqh_grad_sumsq")
+        hip.check(hip.lib().eqh_adam_step_clip(*args, partials, self.max_grad_norm, ops._ptr(self.grad_norm), stream),
+                  "eqh_adam_step_clip")
 
 
 def with_next(batches):
@@ -184,8 +230,12 @@ class GraphedTrainStep:
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, collective: bool = True, keep_grads: bool = False,
-                 force_collective: bool = False, graph_collective: bool = True):
-        """``collective=False``: a rank-local trainer inside a multi-rank job (no broadcast, no all-reduce) -- what a
+                 force_collective: bool = False, graph_collective: bool = True, clip_gnorm: Optional[float] = None):
+        """``clip_gnorm``: clip the gradient by its global L2 norm inside the captured step (``FlatAdam(max_grad_norm=..)``:
+        one more launch in front of the update, behind the all-reduce -- in the one graph in "in_graph" mode, in ``g_opt`` in
+        "split" mode); the norm is that of ``gflat * grad_scale``, the rank-averaged gradient, so every rank scales alike.
+        Fixed at construction (a kernel argument of the captured graphs).  ``None``: no clipping, the launch list of before.
+        ``collective=False``: a rank-local trainer inside a multi-rank job (no broadcast, no all-reduce) -- what a
         measurement on ONE rank needs while the other ranks wait at a barrier.  ``keep_grads``: leave the gradients of the
         last step readable in ``p.grad`` after ``step()`` (tests); by default the update kernel clears the flat gradient
         buffer as it consumes it -- optimizer.zero_grad() without the fill launch at the head of every replayed step.
@@ -193,6 +243,7 @@ class GraphedTrainStep:
         process group has ONE rank -- how the path is exercised on a one-GPU box.  ``graph_collective=False``: never
         capture the collective (always graph A -> eager all-reduce -> graph B)."""
         self.model, self.lr, self.wd = model, lr, weight_decay
+        self.clip_gnorm = clip_gnorm
         self.collective = collective
         self.keep_grads = keep_grads
         self.force_collective = bool(force_collective) and collective and dist.is_available() and dist.is_initialized()
@@ -451,7 +502,7 @@ class GraphedTrainStep:
         self._buffer_restore(snap)             # discovery + probe passes were not steps
         loss = self._fwd_bwd(data)
         # Adam is elementwise: one update over the flat tensor equals the per-parameter updates
-        self.opt = FlatAdam(self.pflat, lr=self.lr, weight_decay=self.wd)
+        self.opt = FlatAdam(self.pflat, lr=self.lr, weight_decay=self.wd, max_grad_norm=self.clip_gnorm)
         self.opt.zero_grad_in_step = not self.keep_grads
         self.opt.zero_also = lambda: self.scratch.buf
         if self._multi():
@@ -682,6 +733,13 @@ class GraphedTrainStep:
         ready = ops.StreamEvent() if light else None
         return {"staged": staged, "g_index": g_index, "ix_staged": ix_staged, "live": live, "dsts": dsts, "srcs": srcs,
                 "stream": stream, "free": free, "ready": None, "ready_ev": ready, "holds": None, "light": light}
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """With ``clip_gnorm``: the update kernel's readout, 4 floats on the device -- {norm of the averaged gradient before
+        clipping, coef, running maximum of the norm, number of clipped steps}; zero the last two to restart them.  Reading
+        the property does not synchronise; ``None`` without clipping or before the first step."""
+        return self.opt.grad_norm if self.opt is not None else None
 
     @property
     def index_prefetch(self) -> bool:

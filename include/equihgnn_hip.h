@@ -47,6 +47,24 @@ int eqh_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, 
                   const float* lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                   void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n, void* stream);
 int eqh_copy_many(int32_t count, const float* const* src, float* const* dst, const int64_t* n, void* stream);
+/* The same update behind torch.nn.utils.clip_grad_norm_(max_norm, norm_type = 2, error_if_nonfinite = False) of
+ * grad * grad_scale, in two launches and without a host round trip (both capturable):
+ *   eqh_grad_sumsq: sum of grad[i]^2 accumulated in double, one double partial per workgroup of a fixed grid into
+ *     `partials` (8-byte aligned, eqh_grad_sumsq_workspace_bytes(n) bytes; every slot is written on every launch, the
+ *     workspace needs no clearing); no atomics, bitwise reproducible;
+ *   eqh_adam_step_clip: eqh_adam_step's arguments, then the partials of eqh_grad_sumsq over the SAME grad and n, the
+ *     threshold max_norm > 0 and `readout`, a 16-byte aligned device block of 4 floats.  The kernel sums the partials in
+ *     a fixed order, forms total_norm = sqrt(sum) * grad_scale and coef = max_norm / (total_norm + 1e-6) clamped from
+ *     above at 1 (a NaN coef stays NaN), and updates from coef * grad_scale * grad (+ weight_decay * p: the decay stays
+ *     behind the clip).  readout = {total_norm before clipping, coef, running maximum of total_norm, number of steps with
+ *     coef < 1}: the first two are overwritten by every step, the last two are updated by the kernel and reset (zeroed)
+ *     by the caller. */
+size_t eqh_grad_sumsq_workspace_bytes(int64_t n);
+int eqh_grad_sumsq(const float* grad, int64_t n, void* partials, void* stream);
+int eqh_adam_step_clip(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                       const float* lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                       void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n,
+                       const void* partials, float max_norm, float* readout, void* stream);
 /* Mean-squared-error loss of main.py:36,49-63 and its gradient in one launch: loss[0] = mean((pred - target)^2)
  * over n values, grad[i] = 2 (pred[i] - target[i]) / n.  n <= 65536 (one workgroup; a batch of molecules). */
 int eqh_mse_fwd_bwd(const float* pred, const float* target, int32_t n, float* loss, float* grad, void* stream);
