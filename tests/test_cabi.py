@@ -197,6 +197,102 @@ def test_argument_validation_without_gpu():
                 assert call(0, C) == hip.EQH_OK, (name, C)
 
 
+def test_se3t_argument_validation_without_gpu():
+    """The se3t_* entries refuse in the order of csrc/se3t.hip: extents and shapes (st_pair_check), then null pointers, then
+    alignment, then the pooled form's own conditions -- all before a launch.  Every call below is refused by a check that
+    comes before any launch; ``held`` is an address that is never read (each call that names it is refused first)."""
+    from equihgnn_amd import hip
+
+    L = hip.lib()
+    ARG, RANGE, ALIGN, OK = hip.EQH_ERR_ARG, hip.EQH_ERR_RANGE, hip.EQH_ERR_ALIGN, hip.EQH_OK
+    buf = ctypes.create_string_buffer(256)
+    held = (ctypes.addressof(buf) + 15) & ~15
+    big = 2 ** 31
+
+    def fwd(h=held, G=held, GB=held, coef=held, cstride=34, rowptr=held, perm=held, N=4, E=64, MO=3, Q=9, O=64, meanw=None, K=16,
+            out=held, accumulate=0, ws=None, ws_bytes=0):
+        return L.se3t_pair_fwd(h, G, GB, coef, cstride, rowptr, perm, N, E, MO, Q, O, meanw, K, out, accumulate, ws, ws_bytes, None)
+
+    def bwd(h=held, G=held, coef=held, cstride=34, rowptr=held, perm=held, N=4, E=64, MO=3, Q=9, O=64, dout=held, meanw=None,
+            K=16, dh=held, dG=held, dGB=held):
+        return L.se3t_pair_bwd(h, G, coef, cstride, rowptr, perm, N, E, MO, Q, O, dout, meanw, K, dh, dG, dGB, None)
+
+    for f in (fwd, bwd):
+        for bad in (dict(MO=2), dict(MO=0), dict(Q=2), dict(Q=27), dict(cstride=26), dict(MO=1, Q=3, cstride=2), dict(K=0),
+                    dict(K=17), dict(N=big), dict(E=big), dict(N=-1), dict(E=-1)):
+            assert f(**bad) == ARG, (f.__name__, bad)
+        for O in (8, 24, 1040, 0):
+            assert f(O=O) == RANGE, (f.__name__, O)
+        assert f(O=1040, MO=2) == ARG, f.__name__                      # the shape is looked at before the width
+        assert f(N=0, E=0) == OK and f(N=0, E=0, O=1024, MO=1, Q=1, cstride=1, K=1) == OK, f.__name__
+    assert fwd(E=0) == OK
+    for name in ("h", "G", "GB", "coef", "rowptr", "perm", "out"):
+        assert fwd(**{name: None}) == ARG, name
+    for name in ("h", "G", "coef", "rowptr", "perm", "dout", "dh", "dG", "dGB"):
+        assert bwd(**{name: None}) == ARG, name
+        assert bwd(E=0, **{name: None}) == ARG, name                   # (no edges, some atoms: dG and dGB are still written)
+    for name in ("h", "G", "GB", "out"):
+        for shift in (4, 8, 12):
+            assert fwd(**{name: held + shift}) == ALIGN, (name, shift)
+    for name in ("G", "dout"):
+        assert bwd(**{name: held + 4}) == ALIGN, name
+    assert fwd(h=None, G=held + 4) == ARG                               # a null pointer is refused before the alignment
+    # the pooled form: E = N K, a workspace of se3t_pair_fwd_workspace_bytes; accumulate only with it
+    need = L.se3t_pair_fwd_workspace_bytes(64, 3, 64, 1)
+    assert need == 64 * 3 * 64 * 4 and L.se3t_pair_fwd_workspace_bytes(64, 3, 64, 0) == 0
+    assert fwd(accumulate=1) == ARG
+    assert fwd(meanw=held, E=63, ws=held, ws_bytes=need) == ARG and bwd(meanw=held, E=63) == ARG
+    assert fwd(meanw=held, K=8, ws=held, ws_bytes=need) == ARG
+    assert fwd(meanw=held, ws=None, ws_bytes=need) == ARG
+    assert fwd(meanw=held, ws=held + 4, ws_bytes=need) == ARG
+    assert fwd(meanw=held, ws=held, ws_bytes=need - 1) == ARG and fwd(meanw=held, ws=held, ws_bytes=0) == ARG
+    assert fwd(meanw=held, accumulate=1, ws=held, ws_bytes=need - 4) == ARG
+
+    def attn_fwd(N=4, K=16, M=3, null=None):
+        p = [None if i == null else held for i in range(8)]
+        return L.se3t_attn_fwd(*p[:6], N, K, M, 0.25, p[6], p[7], None)
+
+    def attn_bwd(N=4, K=16, M=3, null=None):
+        p = [None if i == null else held for i in range(12)]
+        return L.se3t_attn_bwd(*p[:7], N, K, M, 0.25, *p[7:], None)
+
+    for f, n_ptr in ((attn_fwd, 8), (attn_bwd, 12)):
+        for bad in (dict(M=2), dict(M=0), dict(K=17), dict(K=0), dict(N=-1), dict(N=big)):
+            assert f(**bad) == ARG, (f.__name__, bad)
+        assert f(N=0) == OK, f.__name__
+        for i in range(n_ptr):
+            assert f(null=i) == ARG, (f.__name__, i)
+
+    assert L.se3t_norm_fwd(held, held, 4, 3, 0, 1e-12, held, None) == ARG
+    assert L.se3t_norm_fwd(held, held, 4, 2, 64, 1e-12, held, None) == ARG
+    assert L.se3t_norm_fwd(held, held, -1, 3, 64, 1e-12, held, None) == ARG
+    assert L.se3t_norm_fwd(None, None, 0, 3, 64, 1e-12, None, None) == OK
+    for i in range(3):
+        p = [None if j == i else held for j in range(3)]
+        assert L.se3t_norm_fwd(p[0], p[1], 4, 3, 64, 1e-12, p[2], None) == ARG, i
+    need = L.se3t_norm_bwd_workspace_bytes(37, 1024)
+    assert need >= 1024 * 4 and need % (1024 * 4) == 0 and L.se3t_norm_bwd_workspace_bytes(37, 0) == 0
+
+    def norm_bwd(R=37, M=3, C=1024, null=None, ws_bytes=need):
+        p = [None if i == null else held for i in range(6)]              # x, scale, dy, dx, dscale, workspace
+        return L.se3t_norm_bwd(p[0], p[1], p[2], R, M, C, 1e-12, p[3], p[4], p[5], ws_bytes, None)
+
+    for bad in (dict(C=0), dict(M=2), dict(R=-1), dict(ws_bytes=need - 1), dict(ws_bytes=0)):
+        assert norm_bwd(**bad) == ARG, bad
+    for i in range(6):
+        assert norm_bwd(null=i) == ARG, i
+
+    def basis(N=4, K=16, null=None):
+        p = [None if i == null else held for i in range(7)]              # pos, nbr, qtab, dist, maskf, meanw, basis
+        return L.se3t_edge_basis(p[0], p[1], N, K, 5.0, p[2], p[3], p[4], p[5], p[6], None)
+
+    for bad in (dict(K=17), dict(K=0), dict(N=-1), dict(N=big)):
+        assert basis(**bad) == ARG, bad
+    assert basis(N=0) == OK
+    for i in range(7):
+        assert basis(null=i) == ARG, i
+
+
 def test_visnet_rejects_unsupported_widths():
     from equihgnn_amd.visnet import ViS_MP, ViSNet
 
