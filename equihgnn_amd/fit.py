@@ -93,6 +93,53 @@ class BootstrapMetrics:
                 "mse_mean": float(mse.mean()), "mse_std": float(mse.std())}
 
 
+class DeviceBootstrapMetrics:
+    """``BootstrapMetrics`` with the sums in device memory: ``update`` is one kernel launch behind the forward that produced
+    ``pred`` (``ops.bootstrap_update``: no read, no weight matrix -- the Poisson(1) weight of an element is a hash of the seed,
+    the element's position since ``reset`` and the copy), ``compute`` is ONE device-to-host copy of 3 x 64 doubles.  Rank
+    ``r`` resamples with ``seed + r``.  The resamples are not those of the host class's torch generator, and ``update``
+    takes the scale as an argument (the kernel forms ``pred * scale`` and ``target * scale`` in fp32, as the caller of the
+    host class does).  CPU tensors raise ``ValueError``: the host class is the CPU path."""
+
+    def __init__(self, num_bootstraps: int = 50, seed: int = 0):
+        from . import ops
+        if not 1 <= num_bootstraps <= ops.BOOTSTRAP_SLOTS:
+            raise ValueError(f"DeviceBootstrapMetrics: 1..{ops.BOOTSTRAP_SLOTS} bootstrap copies (got {num_bootstraps})")
+        self.nb, self.seed = num_bootstraps, int(seed)
+        self.acc: Optional[torch.Tensor] = None     # [3, 64] float64 on the device of the first update
+        self.position = 0                           # elements seen since reset(): the next update's first position
+        self.reads = 0                              # device-to-host copies made by compute()
+
+    def reset(self):
+        if self.acc is not None:
+            self.acc.zero_()
+        self.position = 0
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor, scale: float = 1.0):
+        from . import ops
+        if not (pred.is_cuda and target.is_cuda):
+            raise ValueError("DeviceBootstrapMetrics: predictions and targets live on a GPU (BootstrapMetrics is the CPU path)")
+        if self.acc is None or self.acc.device != pred.device:
+            self.acc = torch.zeros(3, ops.BOOTSTRAP_SLOTS, dtype=torch.float64, device=pred.device)
+        rank = dist.get_rank() if _world() > 1 else 0
+        ops.bootstrap_update(pred, target, scale, self.nb, self.seed + rank, self.position, self.acc)
+        self.position += pred.numel()
+
+    def compute(self) -> Dict[str, float]:
+        if self.acc is None:
+            pack = torch.zeros(3, self.nb, dtype=torch.float64)
+        else:
+            pack = self.acc.clone()
+            if _world() > 1:  # sync_dist=True
+                dist.all_reduce(pack)
+            pack = pack[:, :self.nb].cpu()
+            self.reads += 1
+        a, s, c = pack
+        mae, mse = a / c.clamp(min=1), s / c.clamp(min=1)
+        return {"mae_mean": float(mae.mean()), "mae_std": float(mae.std()),
+                "mse_mean": float(mse.mean()), "mse_std": float(mse.std())}
+
+
 # ------------------------------------------------------------------------------------------------
 # loaders
 # ------------------------------------------------------------------------------------------------
@@ -411,6 +458,26 @@ def _real(out, data):
     return (out, data.y) if not nb else (out[:nb], data.y[:nb])
 
 
+def _loader_capacity(loader) -> int:
+    """How many molecules one pass of ``loader`` yields on this rank, if the loader says (else 0: the table grows)."""
+    for name in ("store", "mols"):
+        items = getattr(loader, name, None)
+        if items is not None:
+            world = max(1, int(getattr(loader, "world", 1)))
+            return (len(items) + world - 1) // world
+    return 0
+
+
+def _grown(table, filled: int, need: int, hint: int, device):
+    """The test table [2, capacity] float32 on the device, with room for ``need`` columns: allocated once from the loader's
+    own count where it gives one, else doubled (a device-to-device copy of what is filled) when a batch does not fit."""
+    cap = max(need, hint, 1024 if table is None else 2 * table.shape[1])
+    new = torch.empty(2, cap, dtype=torch.float32, device=device)
+    if table is not None and filled:
+        new[:, :filled].copy_(table[:, :filled])
+    return new
+
+
 # ------------------------------------------------------------------------------------------------
 # the fit / test loop
 # ------------------------------------------------------------------------------------------------
@@ -426,15 +493,27 @@ class FitResult:
 class Fitter:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  std: Optional[float] = None, patience_lr: int = 10, patience_stop: int = 50,
-                 step_factory: Callable = TrainStep, metric_seed: int = 0, clip_gnorm: Optional[float] = None):
+                 step_factory: Callable = TrainStep, metric_seed: int = 0, clip_gnorm: Optional[float] = None,
+                 device_metrics: bool = False):
         """``clip_gnorm``: global-norm gradient clipping in the training step (the reference's ``--clip_gnorm``, which its
         Trainer never receives: off by default).  Handed to ``step_factory`` only when given, so a factory without the
-        keyword keeps working; each epoch's history row then carries ``grad_norm_max`` and ``clipped_steps``."""
+        keyword keeps working; each epoch's history row then carries ``grad_norm_max`` and ``clipped_steps``.
+        ``device_metrics``: keep the epoch's loss sum, the bootstrap MAE / MSE sums and the test table in device memory and
+        read each once per epoch / pass, instead of per batch (a GPU model only; ``ValueError`` otherwise).  The step is then
+        built with ``loss_readout=True`` and ``metrics`` is a ``DeviceBootstrapMetrics``: ``train_loss`` is the same number,
+        the bootstrap resamples are other draws of the same distribution.  ``host_reads`` counts the device-to-host reads
+        this object has issued, with the option on or off."""
         self.model, self.lr, self.std = model, lr, std
         self.clip_gnorm = clip_gnorm
+        self.device_metrics = bool(device_metrics)
+        self.host_reads = 0
         extra = {} if clip_gnorm is None else {"clip_gnorm": clip_gnorm}
+        if self.device_metrics:
+            if not all(p.is_cuda for p in model.parameters()) or next(model.parameters(), None) is None:
+                raise ValueError("Fitter(device_metrics=True) keeps its sums in device memory: the model must be on a GPU")
+            extra["loss_readout"] = True
         self.step = step_factory(model, lr=lr, weight_decay=weight_decay, **extra)
-        self.metrics = BootstrapMetrics(50, metric_seed)
+        self.metrics = (DeviceBootstrapMetrics if self.device_metrics else BootstrapMetrics)(50, metric_seed)
         self.patience_lr, self.patience_stop = patience_lr, patience_stop
         self.sched = None
         self.eval_step = None           # GraphedEvalStep, built at the first evaluation of a graphed fit (see _predict)
@@ -459,9 +538,26 @@ class Fitter:
         with torch.no_grad():
             for data in loader:
                 out, y = _real(self._predict(data), data)
-                self.metrics.update(out * scale, y * scale)
+                self._update_metrics(out, y, scale)
         self.model.train()
-        return self.metrics.compute()
+        return self._compute_metrics()
+
+    def _update_metrics(self, out, y, scale):
+        if self.device_metrics:
+            self.metrics.update(out, y, scale)
+        else:
+            self.metrics.update(out * scale, y * scale)
+            self.host_reads += int(out.is_cuda) + int(y.is_cuda)     # (BootstrapMetrics.update moves both to the host)
+
+    def _compute_metrics(self) -> Dict[str, float]:
+        before = getattr(self.metrics, "reads", 0)
+        val = self.metrics.compute()
+        self.host_reads += getattr(self.metrics, "reads", 0) - before
+        return val
+
+    def _loss_to_host(self, loss) -> float:
+        self.host_reads += int(loss.is_cuda)
+        return float(loss)
 
     def fit(self, train_loader, valid_loader, epochs: int) -> FitResult:
         try:
@@ -476,14 +572,22 @@ class Fitter:
         bad = 0
         for epoch in range(epochs):
             tot, n = 0.0, 0
+            # device_metrics: the step adds its loss to its own ``loss_sum`` (loss_readout); nothing is read per batch, so the
+            # host goes on to stage batch t + 1 while step t runs
+            keep = (lambda loss: 0.0) if self.device_metrics else self._loss_to_host
             if isinstance(self.step, GraphedTrainStep):     # one batch of look-ahead: the next batch's index is built beside this step
                 for data, nxt in with_next(train_loader):
-                    tot += float(self.step.step(data, nxt))
+                    tot += keep(self.step.step(data, nxt))
                     n += 1
             else:
                 for data in train_loader:
-                    tot += float(self.step.step(data))
+                    tot += keep(self.step.step(data))
                     n += 1
+            if self.device_metrics and n:       # ONE read of {sum, count} per epoch, then the pair starts again
+                tot, seen = self.step.loss_sum.tolist()
+                self.host_reads += 1
+                self.step.loss_sum.zero_()
+                n = int(seen)
             if self.sched is None and self.step.opt is not None:  # built lazily with the optimiser
                 self.sched = torch.optim.lr_scheduler.ReduceLROnPlateau(
                     self.step.opt, mode="min", factor=0.1, patience=self.patience_lr, min_lr=self.lr * 1e-5)
@@ -494,6 +598,7 @@ class Fitter:
             readout = getattr(self.step, "grad_norm", None) if self.clip_gnorm is not None else None
             if readout is not None:         # ONE read of the step's readout per epoch, then its running pair starts again
                 _, _, seen, clipped = readout.tolist()
+                self.host_reads += int(readout.is_cuda)
                 readout[2:].zero_()
                 res.history[-1].update(grad_norm_max=seen, clipped_steps=int(clipped))
             if self.sched is not None:
@@ -517,17 +622,32 @@ class Fitter:
         self.metrics.reset()
         scale = self.std if self.std else 1.0
         preds, truth = [], []
+        table, filled = None, 0     # device_metrics: both columns in ONE device buffer [2, capacity], moved to the host once
         try:
             with torch.no_grad():
                 for data in test_loader:
                     out, y = _real(self._predict(data), data)
-                    self.metrics.update(out * scale, y * scale)
+                    self._update_metrics(out, y, scale)
+                    if self.device_metrics:
+                        k = out.numel()
+                        if table is None or filled + k > table.shape[1]:
+                            table = _grown(table, filled, filled + k, _loader_capacity(test_loader), out.device)
+                        table[0, filled:filled + k].copy_(out.detach().reshape(-1), non_blocking=True)
+                        table[1, filled:filled + k].copy_(y.detach().reshape(-1), non_blocking=True)
+                        filled += k
+                        continue
                     preds.append(out.detach().float().cpu())
                     truth.append(y.detach().float().cpu())
+                    self.host_reads += int(out.is_cuda) + int(y.is_cuda)
         finally:
             if hasattr(test_loader, "close"):       # (one pass only: drop the epoch a BucketedLoader started ahead)
                 test_loader.close()
-        p, t = torch.cat(preds), torch.cat(truth)
+        if self.device_metrics:
+            host = torch.empty(2, 0) if table is None else table[:, :filled].cpu()
+            self.host_reads += int(table is not None)
+            p, t = host[0], host[1]
+        else:
+            p, t = torch.cat(preds), torch.cat(truth)
         if _world() > 1:  # self.all_gather(preds)
             gp = [None] * _world()
             gt = [None] * _world()
@@ -535,4 +655,4 @@ class Fitter:
             dist.all_gather_object(gt, t)
             p, t = torch.cat(gp), torch.cat(gt)
         self.model.train()
-        return {"test_" + k: v for k, v in self.metrics.compute().items()}, np.stack((p.numpy(), t.numpy()), 1)
+        return {"test_" + k: v for k, v in self._compute_metrics().items()}, np.stack((p.numpy(), t.numpy()), 1)

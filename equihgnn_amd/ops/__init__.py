@@ -21,6 +21,7 @@ One module per subsystem; everything is re-exported here, so cal
   gnn2d    2-D baselines: graph index (edge CSRs, bond codes), GIN / GCN edge messages, mean pool
   frames   FAFormer: frame-averaged SwiGLU pieces, edge hidden layer, row dots, gates, attention sums, eigh3
   visnet   ViSNet: per-molecule radius graph and slot geometry, neighbour / edge embedding, ViS_MP message and edge update
+  metrics  an epoch's loss sum and bootstrap MAE / MSE sums kept on the device, the host twin of their Poisson weights
 
 Module-level switches (``ops.GEMM_TILE``, ``ops.TIMELINE``, ``ops.KNN_GRID_MIN_POINTS``, ...) are read by the
 submodule that owns them; assigning them on this package forwards the value there (_OpsModule below).
@@ -96,6 +97,7 @@ from .gnn2d import GraphIndex, edge_msg, mean_pool  # noqa: F401
 from .visnet import (  # noqa: F401
     RadiusGraph, radius_graph, vis_neighbor_sum, vis_edge_embed, vis_attn, vis_vec_msg, vis_edge_update,
 )
+from .metrics import BOOTSTRAP_SLOTS, bootstrap_update, loss_accumulate, bootstrap_weights_host  # noqa: F401
 
 # switches that tests / tools / bench.py set as ``ops.NAME = value``: owner module of each
 _SWITCH_OWNER = {

@@ -55,11 +55,15 @@ class TrainStep:
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, on_batch: Optional[Callable] = None,
-                 clip_gnorm: Optional[float] = None):
+                 clip_gnorm: Optional[float] = None, loss_readout: bool = False):
         """``clip_gnorm``: clip the rank-averaged gradient by its global L2 norm before the update
         (``torch.nn.utils.clip_grad_norm_``; the reference's ``--clip_gnorm``, main.py:175, which its Trainer never
-        receives -- so the default, and the reference's behaviour, is off)."""
+        receives -- so the default, and the reference's behaviour, is off).  ``loss_readout``: keep {sum, count} of the
+        steps' losses in ``loss_sum``, 2 doubles on the model's device (a GPU), added to by one launch behind every step's
+        backward; the reader zeroes it.  Off: nothing is allocated or launched."""
         self.model = model
+        self.loss_readout = bool(loss_readout)
+        self.loss_sum: Optional[torch.Tensor] = None    # {sum of the steps' losses, number of steps}, float64, on the device
         self.lr, self.wd = lr, weight_decay
         self.on_batch = on_batch
         self.clip_gnorm = None if clip_gnorm is None else float(clip_gnorm)
@@ -94,6 +98,8 @@ class TrainStep:
             self.flat.zero_()
             loss = F.mse_loss(self.model(data), data.y)
             loss.backward()
+        if self.loss_readout:
+            _accumulate_loss(self, loss)
         self.flat.all_reduce_mean()
         if self.clip_gnorm is not None:
             self._clip()
@@ -120,6 +126,17 @@ class TrainStep:
         if _world() > 1:
             for b in self.model.buffers():
                 dist.broadcast(b.data, src=0)
+
+
+def _accumulate_loss(step, loss):
+    """``loss_readout``: one step's loss into the step object's ``loss_sum`` (allocated at the first step), by an ordinary
+    stream-ordered launch behind the step, never a node of a captured graph (the graphs' launch lists stay as they are)."""
+    from . import ops
+    if step.loss_sum is None:
+        if not loss.is_cuda:
+            raise ValueError("loss_readout keeps the loss sum in device memory: the model must be on a GPU")
+        step.loss_sum = torch.zeros(2, dtype=torch.float64, device=loss.device)
+    ops.loss_accumulate(loss, step.loss_sum)
 
 
 class FlatAdam(torch.optim.Optimizer):
@@ -230,8 +247,14 @@ class GraphedTrainStep:
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, collective: bool = True, keep_grads: bool = False,
-                 force_collective: bool = False, graph_collective: bool = True, clip_gnorm: Optional[float] = None):
-        """``clip_gnorm``: clip the gradient by its global L2 norm inside the captured step (``FlatAdam(max_grad_norm=..)``:
+                 force_collective: bool = False, graph_collective: bool = True, clip_gnorm: Optional[float] = None,
+                 loss_readout: bool = False):
+        """``loss_readout``: keep {sum, count} of the steps' losses in ``loss_sum`` (2 doubles on the device): behind every
+        step -- the eager bootstrap step, a capture step, a calibration step, a replay -- ``step()`` issues one ordinary
+        launch that adds the step's loss scalar to it (``ops.loss_accumulate``), stream-ordered behind the replay.  It is no
+        node of the captured graphs: their launch lists, and what ``step()`` returns, are those of before.  Whoever reads
+        ``loss_sum`` zeroes it (``Fitter`` does, once per epoch).  Off: nothing is allocated or launched.
+        ``clip_gnorm``: clip the gradient by its global L2 norm inside the captured step (``FlatAdam(max_grad_norm=..)``:
         one more launch in front of the update, behind the all-reduce -- in the one graph in "in_graph" mode, in ``g_opt`` in
         "split" mode); the norm is that of ``gflat * grad_scale``, the rank-averaged gradient, so every rank scales alike.
         Fixed at construction (a kernel argument of the captured graphs).  ``None``: no clipping, the launch list of before.
@@ -244,6 +267,8 @@ class GraphedTrainStep:
         capture the collective (always graph A -> eager all-reduce -> graph B)."""
         self.model, self.lr, self.wd = model, lr, weight_decay
         self.clip_gnorm = clip_gnorm
+        self.loss_readout = bool(loss_readout)
+        self.loss_sum: Optional[torch.Tensor] = None    # {sum of the steps' losses, number of steps}, float64, on the device
         self.collective = collective
         self.keep_grads = keep_grads
         self.force_collective = bool(force_collective) and collective and dist.is_available() and dist.is_initialized()
@@ -864,7 +889,10 @@ class GraphedTrainStep:
         batch of look-ahead, ``with_next``): its per-batch index is then built beside this step instead of at the head of
         the next one.  Numerically the two forms are the same step."""
         if self.live is None:
-            return self._bootstrap(data)
+            loss = self._bootstrap(data)
+            if self.loss_readout:
+                _accumulate_loss(self, loss)
+            return loss
         key = self._key(data)
         if self.prefetch_policy == "auto" and self.calibration is None:
             self._calibrate(key)
@@ -906,6 +934,8 @@ class GraphedTrainStep:
         if slot["opt"] is not None:
             dist.all_reduce(self.gflat, op=dist.ReduceOp.SUM)
             slot["opt"].replay()
+        if self.loss_readout:
+            _accumulate_loss(self, slot["loss"])     # (the replay's static loss scalar, read before the next replay writes it)
         if next_data is not None:
             nslot = self.slots.get(self._key(next_data))
             npf = nslot.get("prefetch") if nslot is not None else None

@@ -68,6 +68,27 @@ int eqh_adam_step_clip(float* param, float* grad, float* exp_avg, float* exp_avg
 /* Mean-squared-error loss of main.py:36,49-63 and its gradient in one launch: loss[0] = mean((pred - target)^2)
  * over n values, grad[i] = 2 (pred[i] - target[i]) / n.  n <= 65536 (one workgroup; a batch of molecules). */
 int eqh_mse_fwd_bwd(const float* pred, const float* target, int32_t n, float* loss, float* grad, void* stream);
+/* An epoch's loss and bootstrap metrics kept in device memory and read once per epoch (main.py:37-42,65-76,90-110:
+ * BootStrapper(MeanAbsoluteError / MeanSquaredError, num_bootstraps = 50), Poisson(1) resampling of every update).
+ *   eqh_bootstrap_update: one batch of n predictions / targets into `acc`, [3, 64] doubles (rows sum w |e|, sum w e^2,
+ *     sum w; column = bootstrap copy), 8-byte aligned, zeroed by the caller at reset and only added to here; columns at or
+ *     past `copies` (1..64) are not touched.  e = (double)(pred[i] * scale) - (double)(target[i] * scale), the products in
+ *     fp32; w = the Poisson(1) draw of (seed, position0 + i, copy) -- a pure function of the three (csrc/poisson_hash.h: two
+ *     splitmix64 finalisers, 32 uniform bits inverted through the CDF quantised to 2^-32, values 0..13), so the caller
+ *     advances position0 by n from update to update and no weight matrix exists anywhere.  An element whose weight is 0
+ *     is skipped (its NaN, if it is one, stays out of that copy).  One workgroup per copy, sums in double in a fixed
+ *     order, one writer per slot: no atomics, bitwise reproducible.  n == 0: EQH_OK, nothing launched.  acc null, n < 0,
+ *     copies outside 1..64, position0 < 0, or pred / target null with n > 0: EQH_ERR_ARG, nothing launched.  position0 is
+ *     passed BY VALUE: a captured launch would repeat it on every replay, so do not capture this call.
+ *   eqh_loss_accumulate: acc[0] += (double)loss[0], acc[1] += 1 (acc: 2 doubles, 8-byte aligned): the sum and count of a
+ *     training pass's loss scalars, issued behind each step.  A null pointer: EQH_ERR_ARG.
+ *     (`acc` is declared void*, as eqh_grad_sumsq's partials: the binding reader knows no double.)
+ *   eqh_bootstrap_weights_host: HOST function, no GPU call: out[copy * n + i] = the weight eqh_bootstrap_update gives
+ *     element i in `copy` (out: copies * n int32 in host memory).  Same argument checks. */
+int eqh_bootstrap_update(const float* pred, const float* target, int64_t n, float scale, int32_t copies, int64_t seed,
+                         int64_t position0, void* acc, void* stream);
+int eqh_loss_accumulate(const float* loss, void* acc, void* stream);
+int eqh_bootstrap_weights_host(int64_t seed, int64_t position0, int64_t n, int32_t copies, int32_t* out);
 
 /* Deferred gradient reductions.  Several backward kernels end in a fixed-order reduction of per-workgroup
  * partial slabs into a parameter gradient; with accumulate != 0 that gradient is only read by the
