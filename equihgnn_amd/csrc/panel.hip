@@ -348,6 +348,23 @@ __device__ __forceinline__ void rt_zero(RowTile<C, NW>& t) {
 #pragma unroll
     for (int j = 0; j < PnShape<C, NW>::NJ; ++j) t.v[j] = f4_zero();
 }
+// Training dropout (rowln.h: Keep; the DROP forms of k_conv_f3 / k_conv_b3): the keep-scales of row `row` of a [., C] tensor,
+// elements row * C + c, for the lane's float4 group j of the row-tile layout ...
+template <int C, int NW>
+__device__ __forceinline__ float4 rt_keep(const Keep<true>& kp, int64_t row, int c4, int j) {
+    float4 k = make_float4(1.f, 1.f, 1.f, 1.f);
+    keep_scale4(kp.key, (uint64_t)row * (uint64_t)C + (uint64_t)(4 * Geo<NW>::LPR * j + c4), kp.threshold, kp.inv_keep, k);
+    return k;
+}
+// ... and t *= keep[row]: the mask behind a LayerNorm, or ahead of its backward
+template <int C, int NW>
+__device__ __forceinline__ void rt_mask(const Keep<true>& kp, int64_t row, int c4, RowTile<C, NW>& t) {
+#pragma unroll
+    for (int j = 0; j < PnShape<C, NW>::NJ; ++j) {
+        const float4 k = rt_keep<C, NW>(kp, row, c4, j);
+        t.v[j].x *= k.x; t.v[j].y *= k.y; t.v[j].z *= k.z; t.v[j].w *= k.w;
+    }
+}
 
 // xhat(relu(pre + bias)) of a row: the shared first half of the LayerNorm forward and backward (mlp.py:93-97): two-pass mean /
 // variance, correctly rounded sqrt and division (the arithmetic per element of rowln.h; only the order of the row sums differs)
@@ -583,10 +600,15 @@ __device__ __forceinline__ void rt_gather_sum(const float* __restrict__ src, con
 // behind the mean: the per-incidence hidden layer of W2 and the hyperedge -> node mean; the arithmetic of k_inc_fwd_col,
 // incidence.hip) for the rows of the tile, in the row-tile layout: a LayerNorm per incidence costs a lane NJ float4 of work
 // and 2 log2(LPR) DPP steps, for all RPW rows of the wavefront at once.
-template <int C, int NW>
+// DROP: s[v] = (1 / deg v) sum_e keep . (gamma xhat + beta) -- with a mask between beta and the sum, gamma and beta no longer
+// factor out of the mean.  The decision belongs to the incidence: entry q of the CSR is element perm[q] * C + c (perm: its
+// position in the lists the CSR was built from; k_inc_fwd_col's and the incidence backward's element, incidence.hip).  A
+// site with p = 0 (threshold 0) keeps everything and may come without perm.
+template <int C, int NW, bool DROP = false>
 __device__ __forceinline__ void rt_incidence_mean(const float* __restrict__ pa, const float* __restrict__ qb, const int* __restrict__ rowptr,
                                                   const int* __restrict__ col, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                  float eps, const RtPos<NW>& P, RowTile<C, NW>& s) {
+                                                  float eps, const RtPos<NW>& P, RowTile<C, NW>& s, const Keep<true>* kp = nullptr,
+                                                  const int* __restrict__ perm = nullptr) {
     constexpr int NJ = PnShape<C, NW>::NJ, LPR = Geo<NW>::LPR, U = 2;
     int beg = 0, end = 0;
     if (P.live) {
@@ -596,13 +618,20 @@ __device__ __forceinline__ void rt_incidence_mean(const float* __restrict__ pa, 
     RowTile<C, NW> own, acc;
     rt_load<C, NW>(own, pa, C, P.rowc, P.c4);
     rt_zero<C, NW>(acc);
+    [[maybe_unused]] RowTile<C, NW> dgam, dbet;      // DROP: applied per incidence
+    if constexpr (DROP) {
+        rt_load_vec<C, NW>(dgam, gamma, P.c4);
+        rt_load_vec<C, NW>(dbet, beta, P.c4);
+    }
     for (int i0 = 0; __builtin_amdgcn_ballot_w64(beg + i0 < end) != 0ull; i0 += U) {
         int idx[U];
+        [[maybe_unused]] int inc[U];                 // DROP: the incidence's position
         RowTile<C, NW> d[U];
 #pragma unroll
         for (int t = 0; t < U; ++t) {
             const int q = beg + i0 + t;
             idx[t] = q < end ? col[q] : -1;
+            if constexpr (DROP) inc[t] = (q < end && perm) ? perm[q] : 0;
         }
 #pragma unroll
         for (int t = 0; t < U; ++t)
@@ -616,13 +645,29 @@ __device__ __forceinline__ void rt_incidence_mean(const float* __restrict__ pa, 
             float rstd;
             rt_xhat<C, NW>(own, d[t], eps, x, pos, rstd);        // (every lane of the wavefront takes part in the DPP sums)
             if (idx[t] >= 0) {
+                if constexpr (DROP) {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) f4_add(acc.v[j], x.v[j]);
+                    for (int j = 0; j < NJ; ++j) {
+                        const float4 k = rt_keep<C, NW>(*kp, inc[t], P.c4, j);
+                        acc.v[j].x = fmaf(k.x, fmaf(dgam.v[j].x, x.v[j].x, dbet.v[j].x), acc.v[j].x);
+                        acc.v[j].y = fmaf(k.y, fmaf(dgam.v[j].y, x.v[j].y, dbet.v[j].y), acc.v[j].y);
+                        acc.v[j].z = fmaf(k.z, fmaf(dgam.v[j].z, x.v[j].z, dbet.v[j].z), acc.v[j].z);
+                        acc.v[j].w = fmaf(k.w, fmaf(dgam.v[j].w, x.v[j].w, dbet.v[j].w), acc.v[j].w);
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) f4_add(acc.v[j], x.v[j]);
+                }
             }
         }
     }
     const int deg = end - beg;
     const float den = deg > 1 ? (float)deg : 1.0f;
+    if constexpr (DROP) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) s.v[j] = make_float4(acc.v[j].x / den, acc.v[j].y / den, acc.v[j].z / den, acc.v[j].w / den);
+        return;
+    }
     const float bscale = deg > 0 ? 1.0f : 0.0f;
     RowTile<C, NW> gv, bv;
     rt_load_vec<C, NW>(gv, gamma, P.c4);
@@ -995,6 +1040,16 @@ struct ConvPanelArgs {
     int wplanes;                    // planes of every weight image of the launch
 };
 
+// The DROP forms of k_conv_f3 / k_conv_b3 take the two dropout sites BEHIND the block above: the kernels without the flag keep
+// their argument block and their instruction stream.
+struct ConvPanelDropArgs : ConvPanelArgs {
+    LnArgs<true> inc;               // F3's incidence prologue: element perm[q] * C + c (eps unused: eps_inc)
+    LnArgs<true> ln;                // the LayerNorm of F3 / B3: element row * C + c (eps unused: eps)
+};
+template <bool DROP> struct CpArgsOf { using type = ConvPanelArgs; };
+template <> struct CpArgsOf<true> { using type = ConvPanelDropArgs; };
+template <bool DROP> using CpArgs = typename CpArgsOf<DROP>::type;
+
 // ---- F1: X -> h1 (raw), h1n = LN1(relu(h1 + b1a)), pa -------------------------------------------------------------------------
 // the A image holds X's panel; w_a = W1a image (x W^T), w_b = W2v image
 template <int C, int NW, int NP>
@@ -1098,8 +1153,11 @@ PN_KERNEL(NW) k_conv_f2(const ConvPanelArgs p) {
 // incidence LayerNorm, out6 = s (written); in1 = cw, w0 = w23 image, b0/g0/be0 = b3a, gamma3, beta3, w1 = W3b image,
 // bias_out = b3b, relu; out0 = u, out1 = x3, out2 = Xn;
 // tail: w2 = W1a image, w3 = W2v image, b1/g1/be1 = b1a, gamma1, beta1, out3 = h1, out4 = h1n, out5 = pa
-template <int C, int NW, int NP>
-PN_KERNEL(NW) k_conv_f3(const ConvPanelArgs p) {
+// DROP (MHNNConv with an active dropout, conv.py:87-101 + mlp.py:97; no tail): the prologue's per-incidence hidden layer is
+// masked per incidence (p.inc), x3 per row element (p.ln) -- the masked x3 is what is stored (the last Linear's weight-gradient
+// operand) and multiplied; u stays unmasked
+template <int C, int NW, int NP, bool DROP = false>
+PN_KERNEL(NW) k_conv_f3(const CpArgs<DROP> p) {
     using S = PnShape<C, NW>;
     __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
@@ -1115,7 +1173,12 @@ PN_KERNEL(NW) k_conv_f3(const ConvPanelArgs p) {
     rt_load<C, NW>(cw, p.in1, C, P.rowc, P.c4);
     __builtin_amdgcn_sched_barrier(0);
     if (p.rowptr) {
-        rt_incidence_mean<C, NW>(p.in0, p.in2, p.rowptr, p.col, p.g_inc, p.be_inc, p.eps_inc, P, t);
+        if constexpr (DROP) {
+            const Keep<true> kp(p.inc);
+            rt_incidence_mean<C, NW, true>(p.in0, p.in2, p.rowptr, p.col, p.g_inc, p.be_inc, p.eps_inc, P, t, &kp, p.inc.perm);
+        } else {
+            rt_incidence_mean<C, NW>(p.in0, p.in2, p.rowptr, p.col, p.g_inc, p.be_inc, p.eps_inc, P, t);
+        }
         if (P.live) rt_store<C, NW>(t, p.out6, C, P.row, P.c4);
     } else {
         rt_load<C, NW>(t, p.in0, C, P.rowc, P.c4);
@@ -1148,6 +1211,10 @@ PN_KERNEL(NW) k_conv_f3(const ConvPanelArgs p) {
             t.v[j] = make_float4(fmaf(p.scale, t.v[j].x, cw.v[j].x), fmaf(p.scale, t.v[j].y, cw.v[j].y), fmaf(p.scale, t.v[j].z, cw.v[j].z),
                                  fmaf(p.scale, t.v[j].w, cw.v[j].w));
         rt_ln_fwd<C, NW>(t, bv, gv, bev, p.eps, x3);
+        if constexpr (DROP) {
+            const Keep<true> kp(p.ln);
+            rt_mask<C, NW>(kp, P.row, P.c4, x3);
+        }
         if (P.live) {
             rt_store<C, NW>(t, p.out0, C, P.row, P.c4);
             rt_store<C, NW>(x3, p.out1, C, P.row, P.c4);
@@ -1174,20 +1241,26 @@ PN_KERNEL(NW) k_conv_f3(const ConvPanelArgs p) {
             if (p.relu) { t.v[j].x = fmaxf(t.v[j].x, 0.f); t.v[j].y = fmaxf(t.v[j].y, 0.f); t.v[j].z = fmaxf(t.v[j].z, 0.f); t.v[j].w = fmaxf(t.v[j].w, 0.f); }
         }
         if (P.live) rt_store<C, NW>(t, p.out2, C, P.row, P.c4);
-        if (p.tail) rt_a_put<C, NW, S::KS, NP>(t, s_img, P.lrow, P.c);
+        if constexpr (!DROP) {
+            if (p.tail) rt_a_put<C, NW, S::KS, NP>(t, s_img, P.lrow, P.c);
+        }
     }
     PN_STAMP(8);
-    if (!p.tail) return;
-    __syncthreads();
-    stage_f1<C, NW, NP>(p, s_img, s_stg, s_stg2, p.w2, p.w3, p.b1, p.g1, p.be1, p.out3, p.out4, p.out5, P, wave, lane, mul);
-    PN_STAMP(9);
+    if constexpr (!DROP) {
+        if (!p.tail) return;
+        __syncthreads();
+        stage_f1<C, NW, NP>(p, s_img, s_stg, s_stg2, p.w2, p.w3, p.b1, p.g1, p.be1, p.out3, p.out4, p.out5, P, wave, lane, mul);
+        PN_STAMP(9);
+    }
 }
 
 // ---- B3: dXn -> g = dXn * [Xn > 0], dx3 = g W3b, dpre = LN3bwd(u + b3a; dx3), ds = scale * dpre w23 --------------------------
 // Shared by k_conv_b3 (rows from memory) and the tail of k_conv_b1 (rows = the dX it has just formed, in registers).
 // w_a = W3b image (dy W), w_b = w23 image (dy W); slab = [d b3a | d gamma3 | d beta3] of this workgroup; acc_out += dpre
-template <int C, int NW, int NP>
-__device__ __forceinline__ void stage_b3(const ConvPanelArgs& p, uint4* __restrict__ s_img, float* __restrict__ s_stg, RowTile<C, NW>& t,
+// DROP: dx3 is masked by the keep decisions of the forward's x3 (p.ln: element row * C + c, recomputed) ahead of the LayerNorm
+// backward; d gamma3 / d beta3 are sums over the masked rows
+template <int C, int NW, int NP, bool DROP = false>
+__device__ __forceinline__ void stage_b3(const CpArgs<DROP>& p, uint4* __restrict__ s_img, float* __restrict__ s_stg, RowTile<C, NW>& t,
                                          const float* xmask, const uint4* w_a, const uint4* w_b, const float* u_pre, const float* b3a,
                                          const float* g3, float* g_out, float* dpre_out, float* ds_out, float* slab, float* acc_out,
                                          int acc_first, const RtPos<NW>& P, int wave, int lane, bool mul) {
@@ -1231,6 +1304,10 @@ __device__ __forceinline__ void stage_b3(const ConvPanelArgs& p, uint4* __restri
         rt_load<C, NW>(t, s_stg, PN_STG_LD, P.lrow, P.c4);
         rt_load_vec<C, NW>(bv, b3a, P.c4);
         rt_load_vec<C, NW>(gv, g3, P.c4);
+        if constexpr (DROP) {
+            const Keep<true> kp(p.ln);
+            rt_mask<C, NW>(kp, P.row, P.c4, t);
+        }
         rt_ln_bwd<C, NW>(upre, bv, gv, t, p.eps, P.live, dpre, a_db, a_dg, a_dbeta);
         if (P.live) {
             rt_store<C, NW>(dpre, dpre_out, C, P.row, P.c4);
@@ -1267,8 +1344,8 @@ __device__ __forceinline__ void stage_b3(const ConvPanelArgs& p, uint4* __restri
 
 // in0 = dXn (ld0), in1 = Xn or null, w0 = W3b image, w1 = w23 image, in2 = u, b0/g0 = b3a, gamma3;
 // out0 = g (when in1), out1 = dpre, out2 = ds, slab, acc_out (+= dpre; overwritten when acc_first)
-template <int C, int NW, int NP>
-PN_KERNEL(NW) k_conv_b3(const ConvPanelArgs p) {
+template <int C, int NW, int NP, bool DROP = false>
+PN_KERNEL(NW) k_conv_b3(const CpArgs<DROP> p) {
     using S = PnShape<C, NW>;
     __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
@@ -1277,8 +1354,8 @@ PN_KERNEL(NW) k_conv_b3(const ConvPanelArgs p) {
     const bool mul = wave < S::NT;
     RowTile<C, NW> t;
     rt_load<C, NW>(t, p.in0, p.ld0, P.rowc, P.c4);
-    stage_b3<C, NW, NP>(p, s_img, s_stg, t, p.in1, p.w0, p.w1, p.in2, p.b0, p.g0, p.out0, p.out1, p.out2, p.slab, p.acc_out, p.acc_first, P,
-                    wave, lane, mul);
+    stage_b3<C, NW, NP, DROP>(p, s_img, s_stg, t, p.in1, p.w0, p.w1, p.in2, p.b0, p.g0, p.out0, p.out1, p.out2, p.slab, p.acc_out,
+                              p.acc_first, P, wave, lane, mul);
 }
 
 // ---- B1: dh1[v] = LN1bwd(h1[v] + b1a; sum_e dhbar[e] / deg e), dX = [dh1 | dpa] . [W1a ; W2v]  [tail: B3 of the application before]
@@ -1583,14 +1660,8 @@ inline bool pn_mode(int32_t products, int32_t planes, int& np, int& ip) {
         else X(8, 1);                  \
     } while (0)
 
-}  // namespace
-
-extern "C" size_t hg_conv_panel_slab_bytes(int64_t rows, int32_t C) {
-    if (rows < 0 || C <= 0) return 0;
-    return (size_t)((rows + PN_ROWS - 1) / PN_ROWS) * 3 * (size_t)C * sizeof(float);
-}
-
-extern "C" int hg_conv_panel(int32_t stage, const HgConvPanel* q, void* stream_) {
+// hg_conv_panel (drop == NULL) and hg_conv_panel_drop (F3 / B3, validated by the entry): one validation, one dispatch
+int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* drop, void* stream_) {
     if (!q) return EQH_ERR_ARG;
     const int C = q->C;
     int np, ip;
@@ -1616,6 +1687,12 @@ extern "C" int hg_conv_panel(int32_t stage, const HgConvPanel* q, void* stream_)
     a.signal = stage == HG_CONV_F2 ? q->signal : nullptr;
     a.wplanes = ip;
     if (a.ld0 & 3) return EQH_ERR_ALIGN;
+    ConvPanelDropArgs ad{};
+    if (drop) {
+        static_cast<ConvPanelArgs&>(ad) = a;
+        ad.inc = ln_args<true>(q->eps_inc, drop->p_inc, drop->seed_inc, drop->perm);
+        ad.ln = ln_args<true>(q->eps, drop->p, drop->seed);
+    }
     const int blocks = (int)((q->rows + PN_ROWS - 1) / PN_ROWS);
     const int nw = pn_waves(np);
     const dim3 grid(blocks), block(64 * nw);
@@ -1624,21 +1701,23 @@ extern "C" int hg_conv_panel(int32_t stage, const HgConvPanel* q, void* stream_)
     auto f1_ok = [&](const void* wa, const void* wb, const void* b, const void* g, const void* be, const void* o0, const void* o1, const void* o2) {
         return need({wa, wb, b, g, be, o0, o1, o2});
     };
-#define PN_LAUNCH_W(K, NW_, NP_)                                                                          \
+    // (A: the argument block; the trailing arguments: further template arguments of K -- `true` for a DROP form)
+#define PN_LAUNCH_W(K, A, NW_, NP_, ...)                                                                  \
     do {                                                                                                  \
-        if (C == 256) hipLaunchKernelGGL((K<256, NW_, NP_>), grid, block, 0, stream, a);                  \
-        else if (C == 128) hipLaunchKernelGGL((K<128, NW_, NP_>), grid, block, 0, stream, a);             \
-        else hipLaunchKernelGGL((K<64, NW_, NP_>), grid, block, 0, stream, a);                            \
+        if (C == 256) hipLaunchKernelGGL((K<256, NW_, NP_, ##__VA_ARGS__>), grid, block, 0, stream, A);   \
+        else if (C == 128) hipLaunchKernelGGL((K<128, NW_, NP_, ##__VA_ARGS__>), grid, block, 0, stream, A); \
+        else hipLaunchKernelGGL((K<64, NW_, NP_, ##__VA_ARGS__>), grid, block, 0, stream, A);             \
     } while (0)
-#define PN_LAUNCH(K)                                                                                      \
+#define PN_LAUNCH_A(K, A, ...)                                                                            \
     do {                                                                                                  \
         if (np == 6) {                                                                                    \
-            if (nw == 8) PN_LAUNCH_W(K, 8, 6);                                                            \
-            else PN_LAUNCH_W(K, 4, 6);                                                                    \
-        } else if (np == 3) PN_LAUNCH_W(K, 8, 3);                                                         \
-        else PN_LAUNCH_W(K, 8, 1);                                                                        \
+            if (nw == 8) PN_LAUNCH_W(K, A, 8, 6, ##__VA_ARGS__);                                          \
+            else PN_LAUNCH_W(K, A, 4, 6, ##__VA_ARGS__);                                                  \
+        } else if (np == 3) PN_LAUNCH_W(K, A, 8, 3, ##__VA_ARGS__);                                       \
+        else PN_LAUNCH_W(K, A, 8, 1, ##__VA_ARGS__);                                                      \
         EQH_CHECK_LAUNCH();                                                                               \
     } while (0)
+#define PN_LAUNCH(K) PN_LAUNCH_A(K, a)
     switch (stage) {
         case HG_CONV_F1:
             if (!q->in0 || !f1_ok(q->w0, q->w1, q->b0, q->g0, q->be0, q->out0, q->out1, q->out2)) return EQH_ERR_ARG;
@@ -1652,12 +1731,14 @@ extern "C" int hg_conv_panel(int32_t stage, const HgConvPanel* q, void* stream_)
             if (!need({q->in0, q->in1, q->w0, q->b0, q->g0, q->be0, q->w1, q->bias_out, q->out0, q->out1, q->out2})) return EQH_ERR_ARG;
             if (q->rowptr && !need({q->in2, q->col, q->g_inc, q->be_inc, q->out6})) return EQH_ERR_ARG;
             if (q->tail && !f1_ok(q->w2, q->w3, q->b1, q->g1, q->be1, q->out3, q->out4, q->out5)) return EQH_ERR_ARG;
-            PN_LAUNCH(k_conv_f3);
+            if (drop) PN_LAUNCH_A(k_conv_f3, ad, true);
+            else PN_LAUNCH(k_conv_f3);
             return EQH_OK;
         case HG_CONV_B3: {
             if (!need({q->in0, q->w0, q->w1, q->in2, q->b0, q->g0, q->out1, q->out2, q->slab, q->dbias, q->dgamma, q->dbeta})) return EQH_ERR_ARG;
             if (q->in1 && !q->out0) return EQH_ERR_ARG;
-            PN_LAUNCH(k_conv_b3);
+            if (drop) PN_LAUNCH_A(k_conv_b3, ad, true);
+            else PN_LAUNCH(k_conv_b3);
             return eqh_reduce_slabs3_async(q->slab, blocks, 3 * (int64_t)C, q->dbias, q->dgamma, q->dbeta, C, C, q->accumulate, stream);
         }
         case HG_CONV_B1: {
@@ -1689,7 +1770,28 @@ extern "C" int hg_conv_panel(int32_t stage, const HgConvPanel* q, void* stream_)
             return EQH_ERR_ARG;
     }
 #undef PN_LAUNCH
+#undef PN_LAUNCH_A
 #undef PN_LAUNCH_W
+}
+
+}  // namespace
+
+extern "C" size_t hg_conv_panel_slab_bytes(int64_t rows, int32_t C) {
+    if (rows < 0 || C <= 0) return 0;
+    return (size_t)((rows + PN_ROWS - 1) / PN_ROWS) * 3 * (size_t)C * sizeof(float);
+}
+
+extern "C" int hg_conv_panel(int32_t stage, const HgConvPanel* q, void* stream_) { return conv_panel_launch(stage, q, nullptr, stream_); }
+
+// The DROP forms of F3 / B3 (no tail).  A site with p = 0 runs with threshold 0: it keeps everything.
+extern "C" int hg_conv_panel_drop(int32_t stage, const HgConvPanel* q, const HgConvDrop* drop, void* stream_) {
+    if (!q || !drop) return EQH_ERR_ARG;
+    for (const float p : {drop->p_inc, drop->p})
+        if (!(p >= 0.f) || !(p < 1.f)) return EQH_ERR_ARG;
+    if ((stage != HG_CONV_F3 && stage != HG_CONV_B3) || q->tail) return EQH_ERR_ARG;
+    if (drop->p_inc > 0.f && (stage != HG_CONV_F3 || !q->rowptr || !drop->perm || !drop->seed_inc)) return EQH_ERR_ARG;
+    if (drop->p > 0.f && !drop->seed) return EQH_ERR_ARG;
+    return conv_panel_launch(stage, q, drop, stream_);
 }
 
 // ---- a SUM of products over different row blocks of the same rows: out = sum_g A_g W_g + D, g < NG <= 3 -------------------------

@@ -60,7 +60,7 @@ from .conv_stack import (  # noqa: F401
     conv_stack_supported, merged_conv_stack, _MergedConvStack,
 )
 from . import conv_stack  # noqa: F401
-from .mhnn_panel import (mhnn_conv_panel, mhnn_panel_supported, panel_multi, panel_sum, merged_scope)  # noqa: F401
+from .mhnn_panel import (mhnn_conv_panel, mhnn_panel_supported, panel_multi, panel_sum, merged_scope, PANEL_DROPOUT)  # noqa: F401
 from . import mhnn_panel  # noqa: F401
 from .rows import (  # noqa: F401
     _IncidenceLnReduce, _BiasReluLn, _LinearAddReluLn, linear_add_relu_ln, _GatherLnReduce, gather_ln_reduce,
@@ -108,6 +108,7 @@ _SWITCH_OWNER = {
     "TIMELINE": "_base",
     "SIGNAL": "_base",
     "NODE_LN_FOLD": "egnn",
+    "PANEL_DROPOUT": "mhnn_panel",
     "USE_GEOM": "frames",
     "USE_WGRAD_KERNEL": "grads",
     "USE_X6": "products",
@@ -122,7 +123,7 @@ _SWITCH_OWNER = {
 
 # (module objects by name: the package attributes ``linear`` etc. are the re-exported FUNCTIONS)
 _SUBMODULES = tuple(_importlib.import_module(f"{__name__}.{_n}") for _n in (
-    "_base", "aggregate", "products", "grads", "linears", "rows", "egnn", "readout", "se3", "frames"))
+    "_base", "aggregate", "products", "grads", "linears", "rows", "egnn", "readout", "se3", "frames", "mhnn_panel"))
 
 
 class _OpsModule(_types.ModuleType):

@@ -17,6 +17,12 @@ five panel launches instead of ~30 library-GEMM / row-kernel / ATen launches, an
 incidence backward launches and five accumulating products; weight / bias / LayerNorm-vector gradients join the step's
 batched launches exactly as the merged MHNNSConv stack's do (ops/conv_stack.py).
 
+Training dropout (mlp.py:97, behind each MLP's LayerNorm, i.e. in front of its last Linear: the merged products w12 / w34 and
+their bias terms hold unchanged) rides the same launches: W1 and W3, the per-incidence hidden layers [nnz, C], are masked in
+F3's prologue (element = incidence position * C + c), W2 and W4, the row hidden layers [M, C] / [N, C], in F3's LayerNorm
+epilogue and B3's LayerNorm backward (element = row * C + c); the incidence backward is the row kernels' dropout form.  One
+seed per site with p > 0, drawn in the order W1, W2, W3, W4; no mask is stored.
+
 Part of equihgnn_amd.ops (host-side operators over libequihgnn_hip.so; no CPU fallback).
 """
 from __future__ import annotations
@@ -29,7 +35,9 @@ import threading
 import torch
 
 from .. import hip
-from ._base import (LINEAR_PARAMS, _acc_target, _f32c, _note_acc, _ptr, _require_gpu, _stream, _workspace, timed)
+from . import rows as _rows
+from ._base import (LINEAR_PARAMS, _acc_target, _f32c, _hand_out, _note_acc, _ptr, _require_gpu, _stream, _workspace, timed)
+from .frames import _dropout_seed
 from .grads import (_linear_weight_grad, colsum)
 from .conv_stack import (_sum_opt, _wgrad_scaled)
 from .panel import (_image_planes, _products, backward_as_forward, conv_panel, conv_panel_slab, panel_pack, panel_planes,
@@ -37,6 +45,9 @@ from .panel import (_image_planes, _products, backward_as_forward, conv_panel, c
 from .rows import inc_fwd_col_bytes
 
 USE_MHNN_PANEL = not os.environ.get("EQH_NO_MHNN_PANEL")     # tests / A-B runs switch the panel path of MHNNConv off
+# An active training dropout stays on the panel path (the DROP forms of HG_CONV_F3 / HG_CONV_B3, hg_conv_panel_drop).  False --
+# or ops.FUSED_DROPOUT False, or a probability >= 1: the layer leaves the panels for the row kernels, as it did before.
+PANEL_DROPOUT = True
 
 
 def panel_multi(a, C, items, rows=None, products=None):
@@ -81,8 +92,9 @@ def mhnn_panel_supported(X, E, conv) -> bool:
         return False
     C = X.shape[-1]
     ok = (X.is_cuda and X.dim() == 2 and E.dim() == 2 and X.dtype == torch.float32 and E.dtype == torch.float32 and panel_supported(C)
-          and E.shape[1] == C and X.shape[0] > 0 and E.shape[0] > 0 and conv.aggr == "mean"
-          and not (conv.training and conv.dropout > 0))
+          and E.shape[1] == C and X.shape[0] > 0 and E.shape[0] > 0 and conv.aggr == "mean")
+    if ok and conv.training and conv.dropout > 0:
+        ok = _rows.FUSED_DROPOUT and PANEL_DROPOUT and all(w.drop_p < 1.0 for w in ws)
     for w in ws:
         ok = ok and len(w.lins) == 2 and not w.InputNorm and isinstance(w.normalizations[1], torch.nn.LayerNorm) \
             and w.lins[0].weight.shape == (C, 2 * C) and w.lins[1].weight.shape == (C, C)
@@ -102,7 +114,7 @@ def _pack_items(C, W1a, W2a, W2b, W3a, W4a, W4b, w12, w34, need_grad):
 class _MHNNConvPanel(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, E, W1a, b1a, g1, be1, W2a, b2a, g2, be2, W2b, b2b, W3a, b3a, g3, be3, W4a, b4a, g4, be4, W4b, b4b,
-                w12, v12, w34, v34, ix, eps, packed=None):
+                w12, v12, w34, v34, ix, eps, packed=None, drop_p=(0.0, 0.0, 0.0, 0.0)):
         _require_gpu(X, "mhnn_conv_panel")
         X, E = _f32c(X), _f32c(E)
         N, C = X.shape
@@ -127,17 +139,20 @@ class _MHNNConvPanel(torch.autograd.Function):
         timed("k_panel_multi", flops(M, 2), lambda: panel_multi(E, C, [(iW1e, b1a, None, None, qb1), (iW2e, v12, rw_e, None, cwE)]))
         s_e, u_e, x3_e, En = new(M), new(M), new(M), new(M)
         by_e, by_v = ix.by_e, ix.by_v
+        # dropout: one seed per site with p > 0, in the order W1, W2, W3, W4 (None for a site without)
+        p1, p2, p3, p4 = (float(q) for q in drop_p)
+        sd1, sd2, sd3, sd4 = (_dropout_seed(dev, q) for q in (p1, p2, p3, p4))
         timed("k_conv_f3", flops(M, 2), lambda: conv_panel(
             hip.HG_CONV_F3, M, C, dev, eps=eps[1], scale=1.0, relu=False, tail=False, in0=qb1, in2=pa1, rowptr=by_e.rowptr, col=by_e.col,
             g_inc=g1, be_inc=be1, eps_inc=eps[0], out6=s_e, in1=cwE, w0=iw12, b0=b2a, g0=g2, be0=be2, w1=iW2b, bias_out=b2b, out0=u_e,
-            out1=x3_e, out2=En))
+            out1=x3_e, out2=En, drop=(p1, sd1, by_e.perm, p2, sd2)))
         qb3 = new(M)
         timed("k_panel_multi", flops(M, 1), lambda: panel_multi(En, C, [(iW3e, b3a, None, None, qb3)]))
         s_v, u_v, x3_v, Xn = new(N), new(N), new(N), new(N)
         timed("k_conv_f3", flops(N, 2), lambda: conv_panel(
             hip.HG_CONV_F3, N, C, dev, eps=eps[3], scale=1.0, relu=False, tail=False, in0=pa3, in2=qb3, rowptr=by_v.rowptr, col=by_v.col,
             g_inc=g3, be_inc=be3, eps_inc=eps[2], out6=s_v, in1=cwX, w0=iw34, b0=b4a, g0=g4, be0=be4, w1=iW4b, bias_out=b4b, out0=u_v,
-            out1=x3_v, out2=Xn))
+            out1=x3_v, out2=Xn, drop=(p3, sd3, by_v.perm, p4, sd4)))
         if need_grad:
             # En is an OUTPUT that the backward pass reads (dW3a): saved through save_for_backward, so that an in-place
             # operation on the returned E' (an inplace activation, dropout_) trips autograd's version check instead of
@@ -146,6 +161,7 @@ class _MHNNConvPanel(torch.autograd.Function):
             ctx.rows = (pa1, pa3, qb1, qb3, s_e, u_e, x3_e, s_v, u_v, x3_v)
             ctx.imgs = imgs[10:]
             ctx.meta = (ix, eps)
+            ctx.drop = ((p1, sd1), (p2, sd2), (p3, sd3), (p4, sd4))
             ctx.params = (b1a, g1, be1, b2a, g2, be2, b2b, b3a, g3, be3, b4a, g4, be4, b4b, v12, v34)
         return Xn, En
 
@@ -156,6 +172,7 @@ class _MHNNConvPanel(torch.autograd.Function):
         pa1, pa3, qb1, qb3, s_e, u_e, x3_e, s_v, u_v, x3_v = ctx.rows
         iW4b_n, iw34_n, iW3e_n, iW2b_n, iw12_n, iW2e_n, iW1e_n, iW4x_n, iW3x_n, iW1x_n = ctx.imgs
         ix, eps = ctx.meta
+        (p1, sd1), (p2, sd2), (p3, sd3), (p4, sd4) = ctx.drop
         p_b1a, p_g1, p_be1, p_b2a, p_g2, p_be2, p_b2b, p_b3a, p_g3, p_be3, p_b4a, p_g4, p_be4, p_b4b, p_v12, p_v34 = ctx.params
         N, C = X.shape
         M = E.shape[0]
@@ -174,28 +191,44 @@ class _MHNNConvPanel(torch.autograd.Function):
             small = torch.empty((3, C), dtype=torch.float32, device=dev)
             return list(small), False, small
 
-        def b3(rows, dy, iWb, iwm, u, b_a, gam, params):
+        def b3(rows, dy, iWb, iwm, u, b_a, gam, params, p, seed):
             dpre, ds = new(rows), new(rows)
             o, acc, small = vec3(params)
             dy = _f32c(dy)
             timed("k_conv_b3", flops(rows, 2), lambda: conv_panel(
                 hip.HG_CONV_B3, rows, C, dev, eps=eps_mlp[0], scale=1.0, acc_first=True, accumulate=acc, in0=dy, ld0=dy.stride(0), w0=iWb,
                 w1=iwm, in2=u, b0=b_a, g0=gam, out1=dpre, out2=ds, slab=conv_panel_slab(rows, C, dev), dbias=o[0], dgamma=o[1],
-                dbeta=o[2]))
+                dbeta=o[2], drop=(0.0, None, None, p, seed)))
             return dpre, ds, (None, None, None) if acc else tuple(small)
 
-        def inc_bwd(pa, qb, ds, gam, p_gam, p_bet, out_csr, okey, eps_):
+        def inc_bwd(pa, qb, ds, gam, p_gam, p_bet, out_csr, okey, eps_, p, seed):
             dpa, dqb = new(N), new(M)
+            nnz = by_v.nnz
+            head = (_ptr(pa), _ptr(qb), _ptr(ix.v32), _ptr(ix.e32), _ptr(by_v.rowptr), _ptr(by_v.perm), N, _ptr(by_e.rowptr),
+                    _ptr(by_e.perm), M, _ptr(okey), _ptr(out_csr.rowptr), _ptr(ds), _ptr(gam), C, 1, float(eps_))
+            if p > 0.0:
+                # the dropout form recomputes the prologue's decisions and yields d beta itself (a mask sits between beta and
+                # the mean: no column sum of ds); its workspace holds [d gamma | d beta] per workgroup
+                tg = [_acc_target(p_gam), _acc_target(p_bet)]
+                acc = all(t is not None for t in tg)
+                small = None if acc else torch.empty((2, C), dtype=torch.float32, device=dev)
+                o = tg if acc else list(small)
+                ws_bytes = L_.hg_incidence_ln_reduce_drop_bwd_workspace_bytes(N, C)
+                ws = _workspace(ws_bytes, dev)
+                timed("k_inc_drop_bwd_both", 4 * C * (4 * nnz + 2 * (N + M)) + 2 * 20 * nnz + 4 * (N + M + 2),
+                      lambda: hip.check(L_.hg_incidence_ln_reduce_drop_bwd(
+                          *head, p, _ptr(seed), _ptr(dpa), _ptr(dqb), _ptr(o[0]), _ptr(o[1]), 1 if acc else 0, _ptr(ws), ws_bytes,
+                          _stream(dev)), "hg_incidence_ln_reduce_drop_bwd"))
+                dg, dbeta = (None, None) if acc else _hand_out(list(small), tg)
+                return dpa, dqb, dg, dbeta
             g_acc = _acc_target(p_gam)
             dg = g_acc if g_acc is not None else torch.empty(C, dtype=torch.float32, device=dev)
             ws_bytes = L_.hg_incidence_ln_reduce_bwd_workspace_bytes(N, C)
             ws = _workspace(ws_bytes, dev)
-            nnz = by_v.nnz
             timed("k_inc_bwd_both", 4 * C * (4 * nnz + 2 * (N + M)) + 2 * 20 * nnz + 4 * (N + M + 2),
                   lambda: hip.check(L_.hg_incidence_ln_reduce_bwd(
-                      _ptr(pa), _ptr(qb), _ptr(ix.v32), _ptr(ix.e32), _ptr(by_v.rowptr), _ptr(by_v.perm), N, _ptr(by_e.rowptr),
-                      _ptr(by_e.perm), M, _ptr(okey), _ptr(out_csr.rowptr), _ptr(ds), _ptr(gam), C, 1, float(eps_), _ptr(dpa), _ptr(dqb),
-                      _ptr(dg), 1 if g_acc is not None else 0, _ptr(ws), ws_bytes, _stream(dev)), "hg_incidence_ln_reduce_bwd"))
+                      *head, _ptr(dpa), _ptr(dqb), _ptr(dg), 1 if g_acc is not None else 0, _ptr(ws), ws_bytes, _stream(dev)),
+                      "hg_incidence_ln_reduce_bwd"))
             dbeta = colsum(ds, out_csr.rowptr, 1, into=_acc_target(p_bet))
             return dpa, dqb, (None if g_acc is not None else dg), dbeta
 
@@ -204,14 +237,14 @@ class _MHNNConvPanel(torch.autograd.Function):
         # ---- W4 (node rows): X' = W4b LN4(relu(s_v w34^T + cwX + b4a)) + b4b ------------------------------------------------
         eps_mlp = (eps[3],)
         dXn = _f32c(dXn)
-        dpre_v, ds_v, (db4a, dg4, dbe4) = b3(N, dXn, iW4b_n, iw34_n, u_v, b4a, g4, (p_b4a, p_g4, p_be4))
+        dpre_v, ds_v, (db4a, dg4, dbe4) = b3(N, dXn, iW4b_n, iw34_n, u_v, b4a, g4, (p_b4a, p_g4, p_be4), p4, sd4)
         acc_w("W4b", _linear_weight_grad(W4b, None, None, dXn, x3_v))
         db4b = colsum(dXn, into=_acc_target(p_b4b))
         acc_w("w34", _wgrad_scaled(w34, dpre_v, s_v, 1.0))
         acc_w("W4a", _linear_weight_grad(W4a, 0, C, dpre_v, X))
         dv34 = colsum(dpre_v, by_v.rowptr, 1, into=_acc_target(p_v34))
         # ---- message 3: s_v <- (pa3, qb3) -----------------------------------------------------------------------------------------
-        dpa3, dqb3, dg3, dbe3 = inc_bwd(pa3, qb3, ds_v, g3, p_g3, p_be3, by_v, ix.v32, eps[2])
+        dpa3, dqb3, dg3, dbe3 = inc_bwd(pa3, qb3, ds_v, g3, p_g3, p_be3, by_v, ix.v32, eps[2], p3, sd3)
         acc_w("W3a", _linear_weight_grad(W3a, C, 2 * C, dqb3, En))
         acc_w("W3a", _linear_weight_grad(W3a, 0, C, dpa3, X))
         db3a = colsum(dqb3, into=_acc_target(p_b3a))
@@ -221,14 +254,14 @@ class _MHNNConvPanel(torch.autograd.Function):
         timed("k_panel_multi", flops(M, 1), lambda: panel_multi(dqb3, C, [(iW3e_n, None, None, dEn_c, dEt)]))
         # ---- W2 (hyperedge rows) ------------------------------------------------------------------------------------------------------
         eps_mlp = (eps[1],)
-        dpre_e, ds_e, (db2a, dg2, dbe2) = b3(M, dEt, iW2b_n, iw12_n, u_e, b2a, g2, (p_b2a, p_g2, p_be2))
+        dpre_e, ds_e, (db2a, dg2, dbe2) = b3(M, dEt, iW2b_n, iw12_n, u_e, b2a, g2, (p_b2a, p_g2, p_be2), p2, sd2)
         acc_w("W2b", _linear_weight_grad(W2b, None, None, dEt, x3_e))
         db2b = colsum(dEt, into=_acc_target(p_b2b))
         acc_w("w12", _wgrad_scaled(w12, dpre_e, s_e, 1.0))
         acc_w("W2a", _linear_weight_grad(W2a, 0, C, dpre_e, E))
         dv12 = colsum(dpre_e, by_e.rowptr, 1, into=_acc_target(p_v12))
         # ---- message 1: s_e <- (pa1, qb1) -----------------------------------------------------------------------------------------
-        dpa1, dqb1, dg1, dbe1 = inc_bwd(pa1, qb1, ds_e, g1, p_g1, p_be1, by_e, ix.e32, eps[0])
+        dpa1, dqb1, dg1, dbe1 = inc_bwd(pa1, qb1, ds_e, g1, p_g1, p_be1, by_e, ix.e32, eps[0], p1, sd1)
         acc_w("W1a", _linear_weight_grad(W1a, C, 2 * C, dqb1, E))
         acc_w("W1a", _linear_weight_grad(W1a, 0, C, dpa1, X))
         db1a = colsum(dqb1, into=_acc_target(p_b1a))
@@ -253,7 +286,7 @@ class _MHNNConvPanel(torch.autograd.Function):
             timed("k_panel_multi", flops(N, 1), lambda: panel_multi(dpa3, C, [(iW3x_n, None, None, t1, t2)]))
             timed("k_panel_multi", flops(N, 1), lambda: panel_multi(dpa1, C, [(iW1x_n, None, None, t2, dX)]))
         return (dX, dE, dW.get("W1a"), db1a, dg1, dbe1, dW.get("W2a"), db2a, dg2, dbe2, dW.get("W2b"), db2b, dW.get("W3a"), db3a, dg3,
-                dbe3, dW.get("W4a"), db4a, dg4, dbe4, dW.get("W4b"), db4b, dW.get("w12"), dv12, dW.get("w34"), dv34, None, None, None)
+                dbe3, dW.get("W4a"), db4a, dg4, dbe4, dW.get("W4b"), db4b, dW.get("w12"), dv12, dW.get("w34"), dv34, None, None, None, None)
 
 
 def _merged_items(conv, C):
@@ -361,4 +394,4 @@ def mhnn_conv_panel(conv, X, E, ix):
                                 n2.weight, n2.bias, W2.lins[1].weight, W2.lins[1].bias, W3.lins[0].weight, W3.lins[0].bias, n3.weight,
                                 n3.bias, W4.lins[0].weight, W4.lins[0].bias, n4.weight, n4.bias, W4.lins[1].weight, W4.lins[1].bias,
                                 w12, v12, w34, v34, ix, (float(n1.eps), float(n2.eps), float(n3.eps), float(n4.eps)),
-                                _packed_in_scope(conv) if pre is not None else None)
+                                _packed_in_scope(conv) if pre is not None else None, tuple(w.drop_p for w in (W1, W2, W3, W4)))

@@ -199,9 +199,12 @@ _CP_PTRS = ("in0", "in1", "in2", "in3", "rowptr", "col", "wq", "w0", "w1", "w2",
 
 def conv_panel(stage: int, rows: int, C: int, device, eps: float = 1e-5, scale: float = 1.0, relu: bool = False,
                acc_first: bool = False, tail: bool = False, accumulate: bool = False, ld0: int = 0, eps_inc: float = 1e-5,
-               products=None, **tensors):
+               products=None, drop=None, **tensors):
     """One hg_conv_panel stage (include/equihgnn_hip.h lists the operands of each); ``tensors``: name -> device tensor or None.
-    ``products``: 6, 3 or 1 partial products per fp32 product (default: the current mode's)."""
+    ``products``: 6, 3 or 1 partial products per fp32 product (default: the current mode's).
+    ``drop`` = (p_inc, seed_inc, perm, p, seed): training dropout of HG_CONV_F3 / HG_CONV_B3 (hg_conv_panel_drop) -- p_inc, an
+    int64 seed tensor on the device and the CSR's perm for F3's incidence prologue, p and its seed for the stage's LayerNorm.
+    With both probabilities 0 this is the call without the argument."""
     a = hip.HgConvPanel()
     a.products = _products(products)
     a.planes = _image_planes(f"conv_panel(stage {stage})", *((tensors.get(k), K, N) for k, (K, N) in _stage_images(stage, C).items()))
@@ -212,6 +215,14 @@ def conv_panel(stage: int, rows: int, C: int, device, eps: float = 1e-5, scale: 
             raise TypeError(f"conv_panel: unknown operand {k}")
         if t is not None:
             setattr(a, k, t.data_ptr())
+    if drop is not None and (float(drop[0]) != 0.0 or float(drop[3]) != 0.0):
+        d = hip.HgConvDrop()
+        d.p_inc, d.p = float(drop[0]), float(drop[3])
+        for k, t in (("seed_inc", drop[1]), ("perm", drop[2]), ("seed", drop[4])):
+            if t is not None:
+                setattr(d, k, t.data_ptr())
+        hip.check(hip.lib().hg_conv_panel_drop(stage, a, d, _stream(device)), f"hg_conv_panel_drop(stage {stage})")
+        return
     hip.check(hip.lib().hg_conv_panel(stage, a, _stream(device)), f"hg_conv_panel(stage {stage})")
 
 

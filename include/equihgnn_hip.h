@@ -305,6 +305,23 @@ typedef struct {
 } HgConvPanel;
 size_t hg_conv_panel_slab_bytes(int64_t rows, int32_t C);
 int hg_conv_panel(int32_t stage, const HgConvPanel* args, void* stream);
+/* HG_CONV_F3 / HG_CONV_B3 with the training dropout of mlp.py:97 behind their LayerNorms (MHNNConv, conv.py:87-101, on the
+ * panels): keep = 0 or 1 / (1 - p) from the hash of (seed in device memory, element index), as the *_drop_* row entries below;
+ * no mask is stored, B3 recomputes the decisions of its F3.
+ *   p_inc, seed_inc, perm   F3's incidence prologue (needs args->rowptr): s[r] = (1 / deg r) sum_{q in row r} keep . (g_inc
+ *                           xhat_q + be_inc), the decision of entry q, channel c being element perm[q] * C + c -- perm: the
+ *                           position of the CSR's entry q in the incidence lists it was built from, so the decisions are those
+ *                           of hg_incidence_ln_reduce_drop_fwd_col / _drop_bwd under the same seed.  out6 = s.
+ *   p, seed                 the stage's LayerNorm: F3 stores and multiplies x3 = keep . LN3(relu(u + b3a)), B3 masks dx3 by the
+ *                           same keep ahead of the LayerNorm backward; element row * C + c.  out0 = u stays unmasked.
+ * EQH_ERR_ARG, before anything else is looked at: a probability outside 0 <= p < 1 (NaN included).  EQH_ERR_ARG, nothing
+ * launched: args or drop NULL, another stage, tail != 0, p_inc > 0 without rowptr / perm / seed_inc, p > 0 without seed,
+ * p_inc != 0 on HG_CONV_B3.  Everything else as hg_conv_panel (rows == 0: EQH_OK).  A site with p = 0 keeps everything. */
+typedef struct {
+    float p_inc; const int64_t* seed_inc; const int32_t* perm;   /* F3 prologue site (needs args->rowptr) */
+    float p;     const int64_t* seed;                             /* LayerNorm site of F3 / B3 */
+} HgConvDrop;
+int hg_conv_panel_drop(int32_t stage, const HgConvPanel* args, const HgConvDrop* drop, void* stream);
 /* Up to three products of ONE row block in one launch: out[g] = a W_g + rw[g][row] * bias[g] + d[g], g < n <= 3 (bias, rw, d
  * may be NULL; rw: per-row weight of the bias).  MHNNConv (conv.py:87-101) with every first Linear split by input block: X
  * feeds the node halves of W1 and W3 and W4's own half, E the hyperedge half of W1 and W2's own half -- the library GEMMs of

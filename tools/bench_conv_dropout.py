@@ -2,21 +2,27 @@
 """What ``--dropout`` costs on the conv tails, with and without the dropout forms of the fused row kernels (not part of
 bench.py).  Prints ONE JSON line and writes it to ``--out`` (default profiles/conv_dropout_bench.json).  One process:
 
-* the replayed training step (GraphedTrainStep; QM9-like, batch 256, hidden 256) of ``egnn_equihnns`` and ``mhnnm`` in three
-  variants -- ``p0`` (dropout 0: the headline's path), ``p0.1_fused`` (dropout 0.1, ``ops.FUSED_DROPOUT = True``: the hidden
-  layers' dropout inside the row kernels, csrc/incidence.hip) and ``p0.1_aten`` (dropout 0.1 with the switch off: ReLU,
-  LayerNorm and F.dropout as ATen launches on materialised rows, the path before the switch existed).  One model and one
+* the replayed training step (GraphedTrainStep; QM9-like, batch 256, hidden 256) of ``egnn_equihnns``, ``mhnnm`` and
+  ``egnn_equihnnm`` in up to four variants -- ``p0`` (dropout 0: the headline's path), ``p0.1_fused`` (dropout 0.1,
+  ``ops.FUSED_DROPOUT = True``: the hidden layers' dropout inside the kernels -- the row kernels of csrc/incidence.hip and, for
+  the MHNNConv methods, the DROP forms of the panel kernels, ``ops.PANEL_DROPOUT = True``), ``p0.1_rows`` (the MHNNConv
+  methods only: dropout 0.1 with ``ops.PANEL_DROPOUT = False`` -- an MHNNConv with an active dropout leaves the panels for the
+  row kernels, the path before that switch existed) and ``p0.1_aten`` (dropout 0.1 with ``ops.FUSED_DROPOUT`` off: ReLU,
+  LayerNorm and F.dropout as ATen launches on materialised rows, the path before either switch existed).  One model and one
   trainer per variant, fed copies of the same resident batches; after a warm-up the variants run in interleaved blocks of
-  ``--steps`` steps on a host clock around a device synchronise.  The switch is set ahead of every block, so a capture that
-  happens late still sees its variant's value;
+  ``--steps`` steps on a host clock around a device synchronise.  The switches are set ahead of every block, so a capture
+  that happens late still sees its variant's values;
 * the lone ``ops.incidence_ln_reduce``, forward plus backward, on the incidences of one such batch (nnz ~ 10 k, C = 256,
   rows keyed by the nodes) with p = 0 and p = 0.1: hipGraphs of ``REPS`` forward + backward pairs, interleaved blocks of
   ``--inner`` replays between device events.
 
 Per variant: the median block, ``spread`` = (max - min) / median of its blocks.  ``verdict`` says per method whether the fused
-step is faster than the ATen step by more than both spreads -- the condition for the switch to be on by default.
+step is faster than the ATen step by more than both spreads -- the condition for ``FUSED_DROPOUT`` to be on by default --
+and ``panel_verdict`` whether the panel step beats the row-kernel step by more than the larger of the two spreads -- the
+condition for ``PANEL_DROPOUT``, decided by ``mhnnm``.
 
     python tools/bench_conv_dropout.py [--blocks 7] [--steps 10] [--warmup 5] [--inner 3] [--skip-steps] [--skip-kernel]
+                                       [--methods mhnnm,egnn_equihnnm] [--variants p0,p0.1_fused,p0.1_rows]
 """
 from __future__ import annotations
 
@@ -34,7 +40,10 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 REPS = 10
-VARIANTS = (("p0", 0.0, True), ("p0.1_fused", 0.1, True), ("p0.1_aten", 0.1, False))
+# (name, dropout, ops.FUSED_DROPOUT, ops.PANEL_DROPOUT)
+VARIANTS = (("p0", 0.0, True, True), ("p0.1_fused", 0.1, True, True), ("p0.1_rows", 0.1, True, False), ("p0.1_aten", 0.1, False, True))
+STEPS = {"egnn_equihnns": 1000, "mhnnm": 2000, "egnn_equihnnm": 3000}       # method -> seed of its batches
+MHNN_CONV = ("mhnnm", "egnn_equihnnm")                                      # methods whose conv is MHNNConv: the panel switch matters
 
 
 def _stat(ts):
@@ -53,7 +62,12 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
     ext = [bucket_sizes(b.num_nodes, b.num_hyperedges, b.nnz) for b in host]
     tgt = tuple(max(e[i] for e in ext) for i in range(3))
     batches, trainers, counters = {}, {}, {}
-    for name, p, switch in VARIANTS:
+    variants = [v for v in VARIANTS if v[0] in a.variants and (v[0] != "p0.1_rows" or method in MHNN_CONV)]
+
+    def switches(fused, panel):
+        ops.FUSED_DROPOUT, ops.PANEL_DROPOUT = fused, panel
+
+    for name, p, _, _ in variants:
         batches[name] = [pad_batch(b, *tgt).packed().to(dev) for b in host]     # (a trainer caches its index on its batches)
         for b in batches[name]:
             b.num_real_graphs = batch
@@ -69,18 +83,18 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
         counters[name] = n + 1
 
     try:
-        for name, _, switch in VARIANTS:                  # bootstrap, calibration, capture and warm-up of each variant
-            ops.FUSED_DROPOUT = switch
+        for name, _, fused, panel in variants:            # bootstrap, calibration, capture and warm-up of each variant
+            switches(fused, panel)
             for _ in range(2):
                 step(name)
             while getattr(trainers[name], "calibrating", False):
                 step(name)
             for _ in range(1 + a.warmup):
                 step(name)
-        times = {name: [] for name, _, _ in VARIANTS}
+        times = {v[0]: [] for v in variants}
         for _ in range(a.blocks):
-            for name, _, switch in VARIANTS:
-                ops.FUSED_DROPOUT = switch
+            for name, _, fused, panel in variants:
+                switches(fused, panel)
                 step(name)                                # (the first step after a switch of trainers is not timed)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -89,15 +103,19 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
                 torch.cuda.synchronize()
                 times[name].append((time.perf_counter() - t0) / a.steps * 1e3)
     finally:
-        ops.FUSED_DROPOUT = True
+        switches(True, True)
     out = {"molecules": batch, "flavour": "qm9", "hidden": hidden, "graphs": {n: len(t.slots) for n, t in trainers.items()}}
     base, _ = _stat(times["p0"])
     for name, ts in times.items():
         med, sp = _stat(ts)
         out[name] = {"ms": round(med, 4), "spread": round(sp, 4), "vs_p0": round(med / base, 4)}
-    f, t = out["p0.1_fused"], out["p0.1_aten"]
-    out["fused_vs_aten"] = round(f["ms"] / t["ms"], 4)
-    out["fused_faster_beyond_both_spreads"] = bool(f["ms"] * (1 + f["spread"]) < t["ms"] * (1 - t["spread"]))
+    f, t, r = out.get("p0.1_fused"), out.get("p0.1_aten"), out.get("p0.1_rows")
+    if f and t:
+        out["fused_vs_aten"] = round(f["ms"] / t["ms"], 4)
+        out["fused_faster_beyond_both_spreads"] = bool(f["ms"] * (1 + f["spread"]) < t["ms"] * (1 - t["spread"]))
+    if f and r:     # the panel path of MHNNConv against the row kernels it left the panels for
+        out["panel_vs_rows"] = round(f["ms"] / r["ms"], 4)
+        out["panel_faster_beyond_the_larger_spread"] = bool((r["ms"] - f["ms"]) / r["ms"] > max(f["spread"], r["spread"]))
     for tr in trainers.values():
         tr.close()
     del trainers, batches
@@ -170,8 +188,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-steps", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
+    ap.add_argument("--methods", default=",".join(STEPS), help="comma-separated, of " + ", ".join(STEPS))
+    ap.add_argument("--variants", default=",".join(v[0] for v in VARIANTS), help="comma-separated; p0 is always run")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_dropout_bench.json"))
     a = ap.parse_args()
+    a.methods = [m for m in a.methods.split(",") if m]
+    a.variants = set(a.variants.split(",")) | {"p0"}
+    if any(m not in STEPS for m in a.methods):
+        raise SystemExit(f"bench_conv_dropout: --methods takes {', '.join(STEPS)}")
     if not torch.cuda.is_available():
         raise SystemExit("bench_conv_dropout: no GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
@@ -179,16 +203,26 @@ def main():
               "timing": f"steps: {a.blocks} interleaved blocks of {a.steps} replayed steps on a host clock around a device synchronise; "
                         f"kernel: hipGraphs of {REPS} forward + backward pairs, {a.blocks} interleaved blocks of {a.inner} replays between "
                         "device events; median block, spread = (max - min) / median",
-              "variants": "p0: dropout 0; p0.1_fused: dropout 0.1 with ops.FUSED_DROPOUT on; p0.1_aten: dropout 0.1 with it off",
+              "variants": "p0: dropout 0; p0.1_fused: dropout 0.1 with ops.FUSED_DROPOUT and ops.PANEL_DROPOUT on; p0.1_rows (MHNNConv "
+                          "methods): dropout 0.1 with ops.PANEL_DROPOUT off; p0.1_aten: dropout 0.1 with ops.FUSED_DROPOUT off",
               "steps": {}}
     if not a.skip_kernel:
         result["incidence_ln_reduce"] = kernel_times(a, dev)
     if not a.skip_steps:
-        result["steps"]["egnn_equihnns_b256_h256"] = step_times("egnn_equihnns", 256, 1000, a, dev)
-        result["steps"]["mhnnm_b256_h256"] = step_times("mhnnm", 256, 2000, a, dev)
-        result["verdict"] = {k: ("fused faster than ATen beyond both spreads" if e["fused_faster_beyond_both_spreads"]
-                                 else "not faster beyond the spreads") for k, e in result["steps"].items()}
-        result["switch_on_by_default_is_justified"] = all(e["fused_faster_beyond_both_spreads"] for e in result["steps"].values())
+        for method in a.methods:
+            result["steps"][f"{method}_b256_h256"] = step_times(method, 256, STEPS[method], a, dev)
+        fused = {k: e for k, e in result["steps"].items() if "fused_faster_beyond_both_spreads" in e}
+        if fused:
+            result["verdict"] = {k: ("fused faster than ATen beyond both spreads" if e["fused_faster_beyond_both_spreads"]
+                                     else "not faster beyond the spreads") for k, e in fused.items()}
+            result["switch_on_by_default_is_justified"] = all(e["fused_faster_beyond_both_spreads"] for e in fused.values())
+        panel = {k: e for k, e in result["steps"].items() if "panel_faster_beyond_the_larger_spread" in e}
+        if panel:
+            result["panel_verdict"] = {k: ("panels faster than the row kernels beyond the larger spread"
+                                           if e["panel_faster_beyond_the_larger_spread"] else "not faster beyond the spreads")
+                                       for k, e in panel.items()}
+            if "mhnnm_b256_h256" in panel:
+                result["panel_switch_on_by_default_is_justified"] = panel["mhnnm_b256_h256"]["panel_faster_beyond_the_larger_spread"]
     line = json.dumps(result)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
