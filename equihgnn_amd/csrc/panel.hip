@@ -1046,17 +1046,27 @@ struct ConvPanelDropArgs : ConvPanelArgs {
     LnArgs<true> inc;               // F3's incidence prologue: element perm[q] * C + c (eps unused: eps_inc)
     LnArgs<true> ln;                // the LayerNorm of F3 / B3: element row * C + c (eps unused: eps)
 };
-template <bool DROP> struct CpArgsOf { using type = ConvPanelArgs; };
-template <> struct CpArgsOf<true> { using type = ConvPanelDropArgs; };
-template <bool DROP> using CpArgs = typename CpArgsOf<DROP>::type;
+// The S-tail stack under dropout (hg_conv_stack_drop; STACK forms of F1 / F3 / B1) takes two more sites and a scalar behind
+// THAT block: `ln` above is the W3 site (LayerNorm 3), `inc` the W2 site.
+struct ConvStackDropArgs : ConvPanelDropArgs {
+    LnArgs<true> x;                 // the wrapper's input dropout of the NEXT application, applied where F3 stores Xn: element row * C + c
+    LnArgs<true> ln1;               // the W1 site, LayerNorm 1 of F1 / F3's tail / B1: element row * C + c (eps unused: eps)
+    float inv_keep_x;               // B1's tail: g = dX [Xn > 0] / (1 - p_x) -- the stored Xn is the masked one, so no hash
+};
+template <bool DROP, bool STACK> struct CpArgsOf { using type = ConvPanelArgs; };
+template <> struct CpArgsOf<true, false> { using type = ConvPanelDropArgs; };
+template <> struct CpArgsOf<true, true> { using type = ConvStackDropArgs; };
+template <bool DROP, bool STACK = false> using CpArgs = typename CpArgsOf<DROP, STACK>::type;
 
 // ---- F1: X -> h1 (raw), h1n = LN1(relu(h1 + b1a)), pa -------------------------------------------------------------------------
 // the A image holds X's panel; w_a = W1a image (x W^T), w_b = W2v image
-template <int C, int NW, int NP>
+// DROP (the S-tail stack under dropout): h1n = keep . LN1(...) is what is stored -- F2 gathers the masked rows; h1 and pa stay
+// unmasked (ln1: element row * C + c, the element of hg_gather_ln_reduce_drop_*)
+template <int C, int NW, int NP, bool DROP = false>
 __device__ __forceinline__ void stage_f1(const ConvPanelArgs& p, uint4* __restrict__ s_img, float* __restrict__ s_stg,
                                          float* __restrict__ s_stg2, const uint4* w_a, const uint4* w_b, const float* b1a,
                                          const float* g1, const float* be1, float* h1, float* h1n, float* pa, const RtPos<NW>& P, int wave,
-                                         int lane, bool mul) {
+                                         int lane, bool mul, const LnArgs<true>* ln1 = nullptr) {
     using S = PnShape<C, NW>;
     WStream<S::KS, S::NTW, 2, NW, NP> ws(p.wplanes);
     ws.init(0, w_a, mul ? wave : 0, lane);
@@ -1082,11 +1092,15 @@ __device__ __forceinline__ void stage_f1(const ConvPanelArgs& p, uint4* __restri
         rt_store<C, NW>(b, pa, C, P.row, P.c4);
     }
     rt_ln_fwd<C, NW>(a, bv, gv, bev, p.eps, y);
+    if constexpr (DROP) {
+        const Keep<true> kp(*ln1);
+        rt_mask<C, NW>(kp, P.row, P.c4, y);
+    }
     if (P.live) rt_store<C, NW>(y, h1n, C, P.row, P.c4);
 }
 
-template <int C, int NW, int NP>
-PN_KERNEL(NW) k_conv_f1(const ConvPanelArgs p) {
+template <int C, int NW, int NP, bool DROP = false>
+PN_KERNEL(NW) k_conv_f1(const CpArgs<DROP, DROP> p) {
     using S = PnShape<C, NW>;
     __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
@@ -1098,7 +1112,8 @@ PN_KERNEL(NW) k_conv_f1(const ConvPanelArgs p) {
     rt_load<C, NW>(x, p.in0, p.ld0, P.rowc, P.c4);
     rt_a_put<C, NW, S::KS, NP>(x, s_img, P.lrow, P.c);
     __syncthreads();
-    stage_f1<C, NW, NP>(p, s_img, s_stg, s_stg2, p.w0, p.w1, p.b0, p.g0, p.be0, p.out0, p.out1, p.out2, P, wave, lane, mul);
+    if constexpr (DROP) stage_f1<C, NW, NP, true>(p, s_img, s_stg, s_stg2, p.w0, p.w1, p.b0, p.g0, p.be0, p.out0, p.out1, p.out2, P, wave, lane, mul, &p.ln1);
+    else stage_f1<C, NW, NP>(p, s_img, s_stg, s_stg2, p.w0, p.w1, p.b0, p.g0, p.be0, p.out0, p.out1, p.out2, P, wave, lane, mul);
 }
 
 // ---- F2: hbar[e] = mean over the hyperedge's nodes of h1n, qb = hbar w12^T + b12 ---------------------------------------------
@@ -1156,8 +1171,13 @@ PN_KERNEL(NW) k_conv_f2(const ConvPanelArgs p) {
 // DROP (MHNNConv with an active dropout, conv.py:87-101 + mlp.py:97; no tail): the prologue's per-incidence hidden layer is
 // masked per incidence (p.inc), x3 per row element (p.ln) -- the masked x3 is what is stored (the last Linear's weight-gradient
 // operand) and multiplied; u stays unmasked
-template <int C, int NW, int NP, bool DROP = false>
-PN_KERNEL(NW) k_conv_f3(const CpArgs<DROP> p) {
+// STACK (the S-tail stack under dropout; 1: no tail, 2: the chained F1 tail, a compile-time choice here): the DROP form, and Xn
+// is masked by the NEXT application's input dropout (p.x; p_x = 0 for the last application: threshold 0 keeps everything)
+// before it is stored and laid into the tail's A image -- the masked Xn is that application's input and the weight-gradient
+// operand of W1a / W2v; the tail's h1n is masked by p.ln1
+template <int C, int NW, int NP, bool DROP = false, int STACK = 0>
+PN_KERNEL(NW) k_conv_f3(const CpArgs<DROP, STACK != 0> p) {
+    static_assert(STACK == 0 || DROP, "the STACK forms are dropout forms");
     using S = PnShape<C, NW>;
     __shared__ uint4 s_img[pn_planes(NP) * S::KS * 64];
     __shared__ float s_stg[PN_ROWS * PN_STG_LD];
@@ -1240,12 +1260,22 @@ PN_KERNEL(NW) k_conv_f3(const CpArgs<DROP> p) {
             f4_add(t.v[j], bv.v[j]);
             if (p.relu) { t.v[j].x = fmaxf(t.v[j].x, 0.f); t.v[j].y = fmaxf(t.v[j].y, 0.f); t.v[j].z = fmaxf(t.v[j].z, 0.f); t.v[j].w = fmaxf(t.v[j].w, 0.f); }
         }
+        if constexpr (STACK != 0) {
+            const Keep<true> kx(p.x);
+            rt_mask<C, NW>(kx, P.row, P.c4, t);
+        }
         if (P.live) rt_store<C, NW>(t, p.out2, C, P.row, P.c4);
         if constexpr (!DROP) {
             if (p.tail) rt_a_put<C, NW, S::KS, NP>(t, s_img, P.lrow, P.c);
         }
+        if constexpr (STACK == 2) rt_a_put<C, NW, S::KS, NP>(t, s_img, P.lrow, P.c);
     }
     PN_STAMP(8);
+    if constexpr (STACK == 2) {
+        __syncthreads();
+        stage_f1<C, NW, NP, true>(p, s_img, s_stg, s_stg2, p.w2, p.w3, p.b1, p.g1, p.be1, p.out3, p.out4, p.out5, P, wave, lane, mul, &p.ln1);
+        PN_STAMP(9);
+    }
     if constexpr (!DROP) {
         if (!p.tail) return;
         __syncthreads();
@@ -1259,7 +1289,10 @@ PN_KERNEL(NW) k_conv_f3(const CpArgs<DROP> p) {
 // w_a = W3b image (dy W), w_b = w23 image (dy W); slab = [d b3a | d gamma3 | d beta3] of this workgroup; acc_out += dpre
 // DROP: dx3 is masked by the keep decisions of the forward's x3 (p.ln: element row * C + c, recomputed) ahead of the LayerNorm
 // backward; d gamma3 / d beta3 are sums over the masked rows
-template <int C, int NW, int NP, bool DROP = false>
+// IN_B1 changes nothing in the body: it gives the DROP form of k_conv_b1 an instantiation of its own.  The stage has internal
+// linkage, and with a second caller of stage_b3<.., true> the compiler laid out the LDS addressing of k_conv_b3<.., true>
+// differently (11 of its 12 instruction streams changed); with it they are the previous commit's, line for line.
+template <int C, int NW, int NP, bool DROP = false, bool IN_B1 = false>
 __device__ __forceinline__ void stage_b3(const CpArgs<DROP>& p, uint4* __restrict__ s_img, float* __restrict__ s_stg, RowTile<C, NW>& t,
                                          const float* xmask, const uint4* w_a, const uint4* w_b, const float* u_pre, const float* b3a,
                                          const float* g3, float* g_out, float* dpre_out, float* ds_out, float* slab, float* acc_out,
@@ -1364,8 +1397,12 @@ PN_KERNEL(NW) k_conv_b3(const CpArgs<DROP> p) {
 // slab = [d b1a | d gamma1 | d beta1];
 // tail: in3 = X of this application = Xn of the one before (mask), w1 = W3b image, w2 = w23 image, out5 = its u (read),
 //       b1/g1 = b3a, gamma3; out2 = g, out3 = dpre, out4 = ds, slab2, acc_out
-template <int C, int NW, int NP>
-PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
+// DROP (the S-tail stack under dropout): the gathered d h1n (after the folded w12 product) is masked by the keep decisions of
+// the forward's h1n (p.ln1, recomputed) ahead of the LayerNorm backward; the tail's dX is the gradient of the MASKED Xn of the
+// application before, so g = dX [Xn > 0] / (1 - p_x) (p.inv_keep_x; the stored Xn is zero where it was dropped), and its
+// stage_b3 is the DROP form (p.ln: the W3 site)
+template <int C, int NW, int NP, bool DROP = false>
+PN_KERNEL(NW) k_conv_b1(const CpArgs<DROP, DROP> p) {
     using S = PnShape<C, NW>;
     constexpr int KS2 = 2 * S::KS;
     __shared__ uint4 s_img[pn_planes(NP) * KS2 * 64];
@@ -1412,6 +1449,10 @@ PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
         RowTile<C, NW> bv, gv, dh;
         rt_load_vec<C, NW>(bv, p.b0, P.c4);
         rt_load_vec<C, NW>(gv, p.g0, P.c4);
+        if constexpr (DROP) {
+            const Keep<true> kp(p.ln1);
+            rt_mask<C, NW>(kp, P.row, P.c4, dsum);
+        }
         rt_ln_bwd<C, NW>(h, bv, gv, dsum, p.eps, P.live, dh, a_db, a_dg, a_dbeta);
         if (P.live) rt_store<C, NW>(dh, p.out0, C, P.row, P.c4);
         // (every wavefront is past the barrier behind the w12 product: its image may be overwritten, in the K = 2 C layout)
@@ -1434,7 +1475,11 @@ PN_KERNEL(NW) k_conv_b1(const ConvPanelArgs p) {
     write_slab<C, NW>(s_stg, p.slab + (int64_t)blockIdx.x * 3 * C, a_db, a_dg, a_dbeta, wave, lane);
     PN_STAMP(5);
     if (!p.tail) return;
-    stage_b3<C, NW, NP>(p, s_img, s_stg, dx, p.in3, p.w1, p.w2, p.out5, p.b1, p.g1, p.out2, p.out3, p.out4, p.slab2, p.acc_out, p.acc_first, P,
+    if constexpr (DROP) {
+#pragma unroll
+        for (int j = 0; j < S::NJ; ++j) { dx.v[j].x *= p.inv_keep_x; dx.v[j].y *= p.inv_keep_x; dx.v[j].z *= p.inv_keep_x; dx.v[j].w *= p.inv_keep_x; }
+    }
+    stage_b3<C, NW, NP, DROP, DROP>(p, s_img, s_stg, dx, p.in3, p.w1, p.w2, p.out5, p.b1, p.g1, p.out2, p.out3, p.out4, p.slab2, p.acc_out, p.acc_first, P,
                     wave, lane, mul);
     PN_STAMP(6);
 }
@@ -1660,8 +1705,19 @@ inline bool pn_mode(int32_t products, int32_t planes, int& np, int& ip) {
         else X(8, 1);                  \
     } while (0)
 
-// hg_conv_panel (drop == NULL) and hg_conv_panel_drop (F3 / B3, validated by the entry): one validation, one dispatch
-int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* drop, void* stream_) {
+// Whether hg_conv_stack_drop runs F3 CHAINED with the next application's F1 (k_conv_f3<.., true, 2>) at this shape, or as F3
+// without tail plus a lone F1 launch.  The rule: chained unless that form spills more than its p = 0 twin (DESIGN 4.8 has the
+// table this was read from): at C = 256 with 8 wavefronts and 6 products the chained form needs 120 bytes of scratch per lane
+// where k_conv_f3<256, 8, 6, false> has 68, so that shape runs unchained and its chained form is not built.
+constexpr bool stack_f3_chained(int C, int nw, int np) { return !(C == 256 && nw == 8 && np == 6); }
+template <int C, int NW, int NP>
+void launch_stack_f3_chained(dim3 grid, dim3 block, hipStream_t stream, const ConvStackDropArgs& as) {
+    if constexpr (stack_f3_chained(C, NW, NP)) hipLaunchKernelGGL((k_conv_f3<C, NW, NP, true, 2>), grid, block, 0, stream, as);
+}
+
+// hg_conv_panel (drop == NULL), hg_conv_panel_drop (F3 / B3) and hg_conv_stack_drop (sd != NULL: F1 / F3 / B1 / B3), each
+// validated by its entry: one validation, one dispatch
+int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* drop, void* stream_, const HgConvStackDrop* sd = nullptr) {
     if (!q) return EQH_ERR_ARG;
     const int C = q->C;
     int np, ip;
@@ -1693,6 +1749,19 @@ int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* dro
         ad.inc = ln_args<true>(q->eps_inc, drop->p_inc, drop->seed_inc, drop->perm);
         ad.ln = ln_args<true>(q->eps, drop->p, drop->seed);
     }
+    ConvStackDropArgs as{};
+    if (sd) {
+        static_cast<ConvPanelArgs&>(as) = a;
+        as.inc = ln_args<true>(q->eps_inc, sd->p_inc, sd->seed_inc, sd->perm);
+        as.ln = ln_args<true>(q->eps, sd->p3, sd->seed3);
+        as.x = ln_args<true>(q->eps, sd->p_x, sd->seed_x);
+        as.ln1 = ln_args<true>(q->eps, sd->p1, sd->seed1);
+        as.inv_keep_x = drop_inv_keep(sd->p_x);
+        // the lone B3 is the DROP form hg_conv_panel_drop launches
+        static_cast<ConvPanelArgs&>(ad) = a;
+        ad.inc = as.inc;
+        ad.ln = as.ln;
+    }
     const int blocks = (int)((q->rows + PN_ROWS - 1) / PN_ROWS);
     const int nw = pn_waves(np);
     const dim3 grid(blocks), block(64 * nw);
@@ -1721,7 +1790,8 @@ int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* dro
     switch (stage) {
         case HG_CONV_F1:
             if (!q->in0 || !f1_ok(q->w0, q->w1, q->b0, q->g0, q->be0, q->out0, q->out1, q->out2)) return EQH_ERR_ARG;
-            PN_LAUNCH(k_conv_f1);
+            if (sd) PN_LAUNCH_A(k_conv_f1, as, true);
+            else PN_LAUNCH(k_conv_f1);
             return EQH_OK;
         case HG_CONV_F2:
             if (!need({q->in0, q->rowptr, q->col, q->w0, q->bias_out, q->out0, q->out1})) return EQH_ERR_ARG;
@@ -1731,13 +1801,36 @@ int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* dro
             if (!need({q->in0, q->in1, q->w0, q->b0, q->g0, q->be0, q->w1, q->bias_out, q->out0, q->out1, q->out2})) return EQH_ERR_ARG;
             if (q->rowptr && !need({q->in2, q->col, q->g_inc, q->be_inc, q->out6})) return EQH_ERR_ARG;
             if (q->tail && !f1_ok(q->w2, q->w3, q->b1, q->g1, q->be1, q->out3, q->out4, q->out5)) return EQH_ERR_ARG;
-            if (drop) PN_LAUNCH_A(k_conv_f3, ad, true);
+            if (sd) {
+                // (unchained: F3 without tail, then a lone F1 that reads the stored Xn and takes its operands from the tail's slots)
+                if (!q->tail) {
+                    PN_LAUNCH_A(k_conv_f3, as, true, 1);
+                } else if (stack_f3_chained(C, nw, np)) {
+#define PN_F3_CHAINED(NW_, NP_)                                                                  \
+    do {                                                                                         \
+        if (C == 256) launch_stack_f3_chained<256, NW_, NP_>(grid, block, stream, as);            \
+        else if (C == 128) launch_stack_f3_chained<128, NW_, NP_>(grid, block, stream, as);       \
+        else launch_stack_f3_chained<64, NW_, NP_>(grid, block, stream, as);                      \
+    } while (0)
+                    PN_BY_MODE(PN_F3_CHAINED);
+                    EQH_CHECK_LAUNCH();
+#undef PN_F3_CHAINED
+                } else {
+                    as.tail = 0;
+                    PN_LAUNCH_A(k_conv_f3, as, true, 1);
+                    ConvStackDropArgs f1 = as;
+                    f1.in0 = q->out2; f1.ld0 = C;
+                    f1.w0 = as.w2; f1.w1 = as.w3; f1.b0 = q->b1; f1.g0 = q->g1; f1.be0 = q->be1;
+                    f1.out0 = q->out3; f1.out1 = q->out4; f1.out2 = q->out5;
+                    PN_LAUNCH_A(k_conv_f1, f1, true);
+                }
+            } else if (drop) PN_LAUNCH_A(k_conv_f3, ad, true);
             else PN_LAUNCH(k_conv_f3);
             return EQH_OK;
         case HG_CONV_B3: {
             if (!need({q->in0, q->w0, q->w1, q->in2, q->b0, q->g0, q->out1, q->out2, q->slab, q->dbias, q->dgamma, q->dbeta})) return EQH_ERR_ARG;
             if (q->in1 && !q->out0) return EQH_ERR_ARG;
-            if (drop) PN_LAUNCH_A(k_conv_b3, ad, true);
+            if (drop || sd) PN_LAUNCH_A(k_conv_b3, ad, true);
             else PN_LAUNCH(k_conv_b3);
             return eqh_reduce_slabs3_async(q->slab, blocks, 3 * (int64_t)C, q->dbias, q->dgamma, q->dbeta, C, C, q->accumulate, stream);
         }
@@ -1749,7 +1842,8 @@ int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* dro
                                   q->dgamma2, q->dbeta2}))
                 return EQH_ERR_ARG;
             if (q->tail && q->in3 && !q->out2) return EQH_ERR_ARG;
-            PN_LAUNCH(k_conv_b1);
+            if (sd) PN_LAUNCH_A(k_conv_b1, as, true);
+            else PN_LAUNCH(k_conv_b1);
             int rc = eqh_reduce_slabs3_async(q->slab, blocks, 3 * (int64_t)C, q->dbias, q->dgamma, q->dbeta, C, C, q->accumulate, stream);
             if (rc || !q->tail) return rc;
             return eqh_reduce_slabs3_async(q->slab2, blocks, 3 * (int64_t)C, q->dbias2, q->dgamma2, q->dbeta2, C, C, q->accumulate, stream);
@@ -1792,6 +1886,36 @@ extern "C" int hg_conv_panel_drop(int32_t stage, const HgConvPanel* q, const HgC
     if (drop->p_inc > 0.f && (stage != HG_CONV_F3 || !q->rowptr || !drop->perm || !drop->seed_inc)) return EQH_ERR_ARG;
     if (drop->p > 0.f && !drop->seed) return EQH_ERR_ARG;
     return conv_panel_launch(stage, q, drop, stream_);
+}
+
+// The S-tail stack's stages under dropout: F1, F3 (tail 0 / 1), B1 (tail 0 / 1), B3.  With every probability the stage reads
+// at 0 this is hg_conv_panel.
+extern "C" int hg_conv_stack_drop(int32_t stage, const HgConvPanel* q, const HgConvStackDrop* d, void* stream_) {
+    if (!q || !d) return EQH_ERR_ARG;
+    for (const float p : {d->p_inc, d->p3, d->p_x, d->p1})
+        if (!(p >= 0.f) || !(p < 1.f)) return EQH_ERR_ARG;
+    if (stage != HG_CONV_F1 && stage != HG_CONV_F3 && stage != HG_CONV_B1 && stage != HG_CONV_B3) return EQH_ERR_ARG;
+    // the sites a stage reads (HG_CONV_B3 stands at the last application, whose Xn is stored unmasked: p_x must be 0 there)
+    const bool f3 = stage == HG_CONV_F3, b1 = stage == HG_CONV_B1, tail = q->tail != 0;
+    const float p_inc = d->p_inc, p3 = (f3 || stage == HG_CONV_B3 || (b1 && tail)) ? d->p3 : 0.f;
+    const float p_x = (f3 || (b1 && tail)) ? d->p_x : 0.f, p1 = (stage == HG_CONV_F1 || b1 || (f3 && tail)) ? d->p1 : 0.f;
+    if (p_inc > 0.f && (!f3 || !q->rowptr || !d->perm || !d->seed_inc)) return EQH_ERR_ARG;
+    if (stage == HG_CONV_B3 && d->p_x != 0.f) return EQH_ERR_ARG;
+    if ((p3 > 0.f && !d->seed3) || (p1 > 0.f && !d->seed1) || (f3 && p_x > 0.f && !d->seed_x)) return EQH_ERR_ARG;
+    // (B1's tail applies p_x as a scalar on the mask of the STORED Xn: without the stored rows there is no mask to put it on)
+    if (b1 && tail && p_x > 0.f && !q->in3) return EQH_ERR_ARG;
+    if (p_inc == 0.f && p3 == 0.f && p_x == 0.f && p1 == 0.f) return conv_panel_launch(stage, q, nullptr, stream_);
+    const HgConvStackDrop use{p_inc, d->seed_inc, d->perm, p3, d->seed3, p_x, d->seed_x, p1, d->seed1};
+    return conv_panel_launch(stage, q, nullptr, stream_, &use);
+}
+
+// panel launches hg_conv_stack_drop issues for an HG_CONV_F3 with a tail at this width and matmul precision: 1 (F3 chained with
+// the next F1) or 2 (F3, then a lone F1); 0: not a shape of the panel kernels
+extern "C" int hg_conv_stack_drop_f3_launches(int32_t C, int32_t products) {
+    int np, ip;
+    if (!pn_width_ok(C) || !pn_mode(products, 0, np, ip)) return 0;
+    const int nw = pn_waves(np);
+    return stack_f3_chained(C, nw, np) ? 1 : 2;
 }
 
 // ---- a SUM of products over different row blocks of the same rows: out = sum_g A_g W_g + D, g < NG <= 3 -------------------------

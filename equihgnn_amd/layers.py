@@ -374,19 +374,28 @@ class MHNNSConv(nn.Module):
                                    p=W3.drop_p)
         return ops.linear(x, W3.lins[1].weight, W3.lins[1].bias, relu=relu_out)
 
-    def stack_supported(self, X, residual) -> bool:
-        """Whether forward_stack applies: the merged path (``residual`` from prepare()) at a width the panel kernels take."""
-        return (isinstance(residual, dict) and not self.plain and not (self.training and self.dropout > 0)
-                and ops.conv_stack_supported(X, self.W1.lins[0].weight.shape[0]))
+    def stack_supported(self, X, residual, p_x: float = 0.0) -> bool:
+        """Whether forward_stack applies: the merged path (``residual`` from prepare()) at a width the panel kernels take.
+        An active training dropout -- the MLPs' and ``p_x``, the wrapper's between two applications -- stays on the stack
+        when ops.FUSED_DROPOUT and ops.STACK_DROPOUT are on and every probability is below 1
+        (ops.stack_dropout_supported); otherwise the wrappers' loop over _forward_merged runs."""
+        if not isinstance(residual, dict) or self.plain:
+            return False
+        probs = (p_x,) + tuple(w.drop_p for w in (self.W1, self.W2, self.W3))
+        if (self.training and self.dropout > 0) or any(p > 0 for p in probs):
+            if not ops.stack_dropout_supported(probs + ((self.dropout,) if self.training else ())):
+                return False
+        return ops.conv_stack_supported(X, self.W1.lins[0].weight.shape[0])
 
-    def forward_stack(self, X, index: HyperIndex, residual, n_layers: int, relu_out: bool):
+    def forward_stack(self, X, index: HyperIndex, residual, n_layers: int, relu_out: bool, p_x: float = 0.0):
         """``n_layers`` applications of the layer (the wrappers' loop, equihnn_egnn.py:160-165: conv -> activation ->
-        dropout with p = 0) as one autograd node on the row-panel kernels (ops.merged_conv_stack)."""
+        dropout) as one autograd node on the row-panel kernels (ops.merged_conv_stack).  ``p_x``: the wrapper's dropout
+        between two applications; the one in front of the first application is the caller's (it acts on ``X``)."""
         m = residual
         if X is m["x0"]:
             X = m["x0_pass"]
         return ops.merged_conv_stack(X, m["cw"], self.W1, self.W2, self.W3, m["w12"], m["b12"], m["w23"], index, n_layers,
-                                     m["scale"], relu_out)
+                                     m["scale"], relu_out, p_x=p_x)
 
     def forward(self, X, index: HyperIndex, X0, residual=None, relu_out=False):
         """``relu_out``: return relu(output) (the wrappers' activation, fused into the last GEMM); only with the

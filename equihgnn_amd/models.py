@@ -129,11 +129,16 @@ class _Wrapper(nn.Module):
 
 def _conv_layers(model, x, index, x0, res, fuse_act, taps):
     """The wrappers' loop over the shared conv layer (equihnn_egnn.py:160-165, mhnn.py:208-212): conv -> activation ->
-    dropout, ``All_num_layers`` times.  With the merged residual, an inactive dropout and the ReLU fused, all applications
-    run as ONE autograd node on the row-panel kernels (MHNNSConv.forward_stack)."""
-    drop_off = not (model.dropout.training and model.dropout.p > 0)
-    if model.nlayer >= 1 and fuse_act and taps is None and drop_off and model.conv.stack_supported(x, res):
-        return model.conv.forward_stack(x, index, res, model.nlayer, relu_out=True)
+    dropout, ``All_num_layers`` times.  With the merged residual and the ReLU fused, all applications run as ONE autograd
+    node on the row-panel kernels (MHNNSConv.forward_stack) -- under an active dropout too (ops.STACK_DROPOUT): the first
+    application's input dropout is the pass below, the others are sites of the node, in the seed order of the loop."""
+    p_x = float(model.dropout.p) if (model.dropout.training and model.dropout.p > 0) else 0.0
+    if model.nlayer >= 1 and fuse_act and taps is None and model.conv.stack_supported(x, res, p_x):
+        if p_x > 0:
+            if x is res["x0"]:
+                x = res["x0_pass"]  # x0 reaches the first application through the residual's autograd node (one route for its gradient)
+            x = model._drop(x)
+        return model.conv.forward_stack(x, index, res, model.nlayer, relu_out=True, p_x=p_x)
     for i in range(model.nlayer):
         if i == 0 and isinstance(res, dict) and x is res["x0"] and model._drop_p > 0:
             x = res["x0_pass"]      # x0 reaches the first application through the residual's autograd node (one route for its gradient)

@@ -57,7 +57,7 @@ from .linears import (  # noqa: F401
     linear_add, _MatmulFan, matmul_fan, matmul,
 )
 from .conv_stack import (  # noqa: F401
-    conv_stack_supported, merged_conv_stack, _MergedConvStack,
+    conv_stack_supported, merged_conv_stack, _MergedConvStack, stack_dropout_supported, STACK_DROPOUT,
 )
 from . import conv_stack  # noqa: F401
 from .mhnn_panel import (mhnn_conv_panel, mhnn_panel_supported, panel_multi, panel_sum, merged_scope, PANEL_DROPOUT)  # noqa: F401
@@ -109,6 +109,7 @@ _SWITCH_OWNER = {
     "SIGNAL": "_base",
     "NODE_LN_FOLD": "egnn",
     "PANEL_DROPOUT": "mhnn_panel",
+    "STACK_DROPOUT": "conv_stack",
     "USE_GEOM": "frames",
     "USE_WGRAD_KERNEL": "grads",
     "USE_X6": "products",
@@ -123,7 +124,7 @@ _SWITCH_OWNER = {
 
 # (module objects by name: the package attributes ``linear`` etc. are the re-exported FUNCTIONS)
 _SUBMODULES = tuple(_importlib.import_module(f"{__name__}.{_n}") for _n in (
-    "_base", "aggregate", "products", "grads", "linears", "rows", "egnn", "readout", "se3", "frames", "mhnn_panel"))
+    "_base", "aggregate", "products", "grads", "linears", "rows", "egnn", "readout", "se3", "frames", "mhnn_panel", "conv_stack"))
 
 
 class _OpsModule(_types.ModuleType):

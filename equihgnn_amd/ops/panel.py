@@ -197,14 +197,21 @@ _CP_PTRS = ("in0", "in1", "in2", "in3", "rowptr", "col", "wq", "w0", "w1", "w2",
             "dbias2", "dgamma2", "dbeta2", "g_inc", "be_inc", "out6", "signal")
 
 
+_SD_PROBS = ("p_inc", "p3", "p_x", "p1")
+_SD_PTRS = ("seed_inc", "perm", "seed3", "seed_x", "seed1")
+
+
 def conv_panel(stage: int, rows: int, C: int, device, eps: float = 1e-5, scale: float = 1.0, relu: bool = False,
                acc_first: bool = False, tail: bool = False, accumulate: bool = False, ld0: int = 0, eps_inc: float = 1e-5,
-               products=None, drop=None, **tensors):
+               products=None, drop=None, stack_drop=None, **tensors):
     """One hg_conv_panel stage (include/equihgnn_hip.h lists the operands of each); ``tensors``: name -> device tensor or None.
     ``products``: 6, 3 or 1 partial products per fp32 product (default: the current mode's).
     ``drop`` = (p_inc, seed_inc, perm, p, seed): training dropout of HG_CONV_F3 / HG_CONV_B3 (hg_conv_panel_drop) -- p_inc, an
     int64 seed tensor on the device and the CSR's perm for F3's incidence prologue, p and its seed for the stage's LayerNorm.
-    With both probabilities 0 this is the call without the argument."""
+    With both probabilities 0 this is the call without the argument.
+    ``stack_drop`` = {p_inc, seed_inc, perm, p3, seed3, p_x, seed_x, p1, seed1} (missing keys: 0 / None): the sites of an S-tail
+    stack stage under dropout (hg_conv_stack_drop: HG_CONV_F1, _F3, _B1, _B3; include/equihgnn_hip.h says which stage reads
+    which).  The entry is called only when a probability is not 0; otherwise this is the call without the argument."""
     a = hip.HgConvPanel()
     a.products = _products(products)
     a.planes = _image_planes(f"conv_panel(stage {stage})", *((tensors.get(k), K, N) for k, (K, N) in _stage_images(stage, C).items()))
@@ -222,6 +229,17 @@ def conv_panel(stage: int, rows: int, C: int, device, eps: float = 1e-5, scale: 
             if t is not None:
                 setattr(d, k, t.data_ptr())
         hip.check(hip.lib().hg_conv_panel_drop(stage, a, d, _stream(device)), f"hg_conv_panel_drop(stage {stage})")
+        return
+    if stack_drop is not None and any(float(stack_drop.get(k) or 0.0) != 0.0 for k in _SD_PROBS):
+        if drop is not None:
+            raise TypeError("conv_panel: drop and stack_drop are two entry points, pass one")
+        d = hip.HgConvStackDrop()
+        for k in _SD_PROBS:
+            setattr(d, k, float(stack_drop.get(k) or 0.0))
+        for k in _SD_PTRS:
+            if stack_drop.get(k) is not None:
+                setattr(d, k, stack_drop[k].data_ptr())
+        hip.check(hip.lib().hg_conv_stack_drop(stage, a, d, _stream(device)), f"hg_conv_stack_drop(stage {stage})")
         return
     hip.check(hip.lib().hg_conv_panel(stage, a, _stream(device)), f"hg_conv_panel(stage {stage})")
 

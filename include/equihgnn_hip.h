@@ -322,6 +322,33 @@ typedef struct {
     float p;     const int64_t* seed;                             /* LayerNorm site of F3 / B3 */
 } HgConvDrop;
 int hg_conv_panel_drop(int32_t stage, const HgConvPanel* args, const HgConvDrop* drop, void* stream);
+/* The stages of the S-tail stack (the L applications of the merged MHNNSConv, ops.merged_conv_stack) with the training dropout
+ * of equihnn_egnn.py:160-165 + mlp.py:97: HG_CONV_F1, HG_CONV_F3 (tail 0 / 1), HG_CONV_B1 (tail 0 / 1), HG_CONV_B3, operands as
+ * hg_conv_panel.  keep = 0 or 1 / (1 - p) from the hash of (seed in device memory, element index); no mask is stored, every
+ * backward stage recomputes its decisions.  Sites, in the seed order of one application (draws 4a .. 4a + 3):
+ *   p_x, seed_x             the wrapper's input dropout of the NEXT application (draw 4(a + 1)), element row * C + c: F3 stores
+ *                           Xn = keep . act(x3 W3b^T + b3b) to out2 and feeds it to its tail; pass p_x = 0 for the last
+ *                           application.  B1's tail forms g = dX [Xn > 0] / (1 - p_x) from that stored Xn (in3; no seed needed).
+ *   p1, seed1               W1's hidden layer, element row * C + c (the element of hg_gather_ln_reduce_drop_*): F1 / F3's tail
+ *                           store h1n = keep . LN1(relu(h1 + b1a)), h1 and pa stay unmasked; B1 masks the gathered d h1n (after
+ *                           the folded w12 product) ahead of the LayerNorm backward.
+ *   p_inc, seed_inc, perm   W2's per-incidence hidden layer, F3's prologue, as HgConvDrop (backward: hg_incidence_ln_reduce_drop_bwd).
+ *   p3, seed3               W3's hidden layer, element row * C + c: the LayerNorm site of F3 / B3 / B1's tail, as HgConvDrop's p.
+ * A stage reads the sites listed for it and ignores the others.  An HG_CONV_F3 with a tail runs chained with the next F1 or as
+ * two launches (F3, then F1 on the stored Xn), whichever the shape was built for: hg_conv_stack_drop_f3_launches says which.
+ * EQH_ERR_ARG, before anything else is looked at: a probability outside 0 <= p < 1 (NaN included).  EQH_ERR_ARG, nothing
+ * launched: args or drop NULL, a stage outside the four, an active site of the stage without its seed, p_inc > 0 outside
+ * HG_CONV_F3 or without rowptr / perm, p_x != 0 on HG_CONV_B3 (the last application's Xn is unmasked), p_x > 0 on
+ * an HG_CONV_B1 with a tail but without the stored Xn (in3 NULL: there is no mask to scale).  Everything else as
+ * hg_conv_panel (rows == 0: EQH_OK); with every probability the stage reads at 0 it IS hg_conv_panel. */
+typedef struct {
+    float p_inc; const int64_t* seed_inc; const int32_t* perm;   /* W2 site: F3 prologue (needs args->rowptr) */
+    float p3;    const int64_t* seed3;                            /* W3 site: LayerNorm 3 of F3 / B3 / B1's tail */
+    float p_x;   const int64_t* seed_x;                           /* the next application's input dropout, applied to Xn */
+    float p1;    const int64_t* seed1;                            /* W1 site: LayerNorm 1 of F1 / F3's tail / B1 */
+} HgConvStackDrop;
+int hg_conv_stack_drop(int32_t stage, const HgConvPanel* args, const HgConvStackDrop* drop, void* stream);
+int hg_conv_stack_drop_f3_launches(int32_t C, int32_t products);
 /* Up to three products of ONE row block in one launch: out[g] = a W_g + rw[g][row] * bias[g] + d[g], g < n <= 3 (bias, rw, d
  * may be NULL; rw: per-row weight of the bias).  MHNNConv (conv.py:87-101) with every first Linear split by input block: X
  * feeds the node halves of W1 and W3 and W4's own half, E the hyperedge half of W1 and W2's own half -- the library GEMMs of

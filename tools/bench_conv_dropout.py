@@ -2,12 +2,15 @@
 """What ``--dropout`` costs on the conv tails, with and without the dropout forms of the fused row kernels (not part of
 bench.py).  Prints ONE JSON line and writes it to ``--out`` (default profiles/conv_dropout_bench.json).  One process:
 
-* the replayed training step (GraphedTrainStep; QM9-like, batch 256, hidden 256) of ``egnn_equihnns``, ``mhnnm`` and
-  ``egnn_equihnnm`` in up to four variants -- ``p0`` (dropout 0: the headline's path), ``p0.1_fused`` (dropout 0.1,
-  ``ops.FUSED_DROPOUT = True``: the hidden layers' dropout inside the kernels -- the row kernels of csrc/incidence.hip and, for
-  the MHNNConv methods, the DROP forms of the panel kernels, ``ops.PANEL_DROPOUT = True``), ``p0.1_rows`` (the MHNNConv
+* the replayed training step (GraphedTrainStep; QM9-like, batch 256, hidden 256) of ``egnn_equihnns``, ``mhnns``,
+  ``faformer_equihnns``, ``mhnnm`` and ``egnn_equihnnm`` in up to five variants -- ``p0`` (dropout 0: the headline's path),
+  ``p0.1_fused`` (dropout 0.1, ``ops.FUSED_DROPOUT = True``: the hidden layers' dropout inside the kernels -- the row kernels
+  of csrc/incidence.hip, for the MHNNConv methods the DROP forms of the panel kernels, ``ops.PANEL_DROPOUT = True``, and for
+  the S-tail methods the dropout forms of the conv stack's stages, ``ops.STACK_DROPOUT = True``), ``p0.1_rows`` (the MHNNConv
   methods only: dropout 0.1 with ``ops.PANEL_DROPOUT = False`` -- an MHNNConv with an active dropout leaves the panels for the
-  row kernels, the path before that switch existed) and ``p0.1_aten`` (dropout 0.1 with ``ops.FUSED_DROPOUT`` off: ReLU,
+  row kernels, the path before that switch existed), ``p0.1_stack_off`` (the S-tail methods only: dropout 0.1 with
+  ``ops.STACK_DROPOUT = False`` -- the conv stack leaves the panels for the loop over the row kernels, the path before that
+  switch existed and its yardstick) and ``p0.1_aten`` (dropout 0.1 with ``ops.FUSED_DROPOUT`` off: ReLU,
   LayerNorm and F.dropout as ATen launches on materialised rows, the path before either switch existed).  One model and one
   trainer per variant, fed copies of the same resident batches; after a warm-up the variants run in interleaved blocks of
   ``--steps`` steps on a host clock around a device synchronise.  The switches are set ahead of every block, so a capture
@@ -19,7 +22,8 @@ bench.py).  Prints ONE JSON line and writes it to ``--out`` (default profiles/co
 Per variant: the median block, ``spread`` = (max - min) / median of its blocks.  ``verdict`` says per method whether the fused
 step is faster than the ATen step by more than both spreads -- the condition for ``FUSED_DROPOUT`` to be on by default --
 and ``panel_verdict`` whether the panel step beats the row-kernel step by more than the larger of the two spreads -- the
-condition for ``PANEL_DROPOUT``, decided by ``mhnnm``.
+condition for ``PANEL_DROPOUT``, decided by ``mhnnm``; ``stack_verdict`` the same for ``STACK_DROPOUT``, decided by
+``egnn_equihnns``.
 
     python tools/bench_conv_dropout.py [--blocks 7] [--steps 10] [--warmup 5] [--inner 3] [--skip-steps] [--skip-kernel]
                                        [--methods mhnnm,egnn_equihnnm] [--variants p0,p0.1_fused,p0.1_rows]
@@ -40,10 +44,12 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 REPS = 10
-# (name, dropout, ops.FUSED_DROPOUT, ops.PANEL_DROPOUT)
-VARIANTS = (("p0", 0.0, True, True), ("p0.1_fused", 0.1, True, True), ("p0.1_rows", 0.1, True, False), ("p0.1_aten", 0.1, False, True))
-STEPS = {"egnn_equihnns": 1000, "mhnnm": 2000, "egnn_equihnnm": 3000}       # method -> seed of its batches
+# (name, dropout, ops.FUSED_DROPOUT, ops.PANEL_DROPOUT, ops.STACK_DROPOUT)
+VARIANTS = (("p0", 0.0, True, True, True), ("p0.1_fused", 0.1, True, True, True), ("p0.1_rows", 0.1, True, False, True),
+            ("p0.1_stack_off", 0.1, True, True, False), ("p0.1_aten", 0.1, False, True, True))
+STEPS = {"egnn_equihnns": 1000, "mhnnm": 2000, "egnn_equihnnm": 3000, "mhnns": 4000, "faformer_equihnns": 5000}   # method -> seed of its batches
 MHNN_CONV = ("mhnnm", "egnn_equihnnm")                                      # methods whose conv is MHNNConv: the panel switch matters
+S_TAIL = ("egnn_equihnns", "mhnns", "faformer_equihnns")                    # methods on the S tail: the stack switch matters
 
 
 def _stat(ts):
@@ -62,12 +68,14 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
     ext = [bucket_sizes(b.num_nodes, b.num_hyperedges, b.nnz) for b in host]
     tgt = tuple(max(e[i] for e in ext) for i in range(3))
     batches, trainers, counters = {}, {}, {}
-    variants = [v for v in VARIANTS if v[0] in a.variants and (v[0] != "p0.1_rows" or method in MHNN_CONV)]
+    variants = [v for v in VARIANTS if v[0] in a.variants and (v[0] != "p0.1_rows" or method in MHNN_CONV)
+                and (v[0] != "p0.1_stack_off" or method in S_TAIL)]
+    stack_default = ops.STACK_DROPOUT
 
-    def switches(fused, panel):
-        ops.FUSED_DROPOUT, ops.PANEL_DROPOUT = fused, panel
+    def switches(fused, panel, stack):
+        ops.FUSED_DROPOUT, ops.PANEL_DROPOUT, ops.STACK_DROPOUT = fused, panel, stack
 
-    for name, p, _, _ in variants:
+    for name, p, _, _, _ in variants:
         batches[name] = [pad_batch(b, *tgt).packed().to(dev) for b in host]     # (a trainer caches its index on its batches)
         for b in batches[name]:
             b.num_real_graphs = batch
@@ -83,8 +91,8 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
         counters[name] = n + 1
 
     try:
-        for name, _, fused, panel in variants:            # bootstrap, calibration, capture and warm-up of each variant
-            switches(fused, panel)
+        for name, _, fused, panel, stack in variants:     # bootstrap, calibration, capture and warm-up of each variant
+            switches(fused, panel, stack)
             for _ in range(2):
                 step(name)
             while getattr(trainers[name], "calibrating", False):
@@ -93,8 +101,8 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
                 step(name)
         times = {v[0]: [] for v in variants}
         for _ in range(a.blocks):
-            for name, _, fused, panel in variants:
-                switches(fused, panel)
+            for name, _, fused, panel, stack in variants:
+                switches(fused, panel, stack)
                 step(name)                                # (the first step after a switch of trainers is not timed)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -103,19 +111,22 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
                 torch.cuda.synchronize()
                 times[name].append((time.perf_counter() - t0) / a.steps * 1e3)
     finally:
-        switches(True, True)
+        switches(True, True, stack_default)
     out = {"molecules": batch, "flavour": "qm9", "hidden": hidden, "graphs": {n: len(t.slots) for n, t in trainers.items()}}
     base, _ = _stat(times["p0"])
     for name, ts in times.items():
         med, sp = _stat(ts)
         out[name] = {"ms": round(med, 4), "spread": round(sp, 4), "vs_p0": round(med / base, 4)}
-    f, t, r = out.get("p0.1_fused"), out.get("p0.1_aten"), out.get("p0.1_rows")
+    f, t, r, k = out.get("p0.1_fused"), out.get("p0.1_aten"), out.get("p0.1_rows"), out.get("p0.1_stack_off")
     if f and t:
         out["fused_vs_aten"] = round(f["ms"] / t["ms"], 4)
         out["fused_faster_beyond_both_spreads"] = bool(f["ms"] * (1 + f["spread"]) < t["ms"] * (1 - t["spread"]))
     if f and r:     # the panel path of MHNNConv against the row kernels it left the panels for
         out["panel_vs_rows"] = round(f["ms"] / r["ms"], 4)
         out["panel_faster_beyond_the_larger_spread"] = bool((r["ms"] - f["ms"]) / r["ms"] > max(f["spread"], r["spread"]))
+    if f and k:     # the conv stack under dropout against the loop over the row kernels it left the panels for
+        out["stack_vs_stack_off"] = round(f["ms"] / k["ms"], 4)
+        out["stack_faster_beyond_the_larger_spread"] = bool((k["ms"] - f["ms"]) / k["ms"] > max(f["spread"], k["spread"]))
     for tr in trainers.values():
         tr.close()
     del trainers, batches
@@ -204,7 +215,8 @@ def main():
                         f"kernel: hipGraphs of {REPS} forward + backward pairs, {a.blocks} interleaved blocks of {a.inner} replays between "
                         "device events; median block, spread = (max - min) / median",
               "variants": "p0: dropout 0; p0.1_fused: dropout 0.1 with ops.FUSED_DROPOUT and ops.PANEL_DROPOUT on; p0.1_rows (MHNNConv "
-                          "methods): dropout 0.1 with ops.PANEL_DROPOUT off; p0.1_aten: dropout 0.1 with ops.FUSED_DROPOUT off",
+                          "methods): dropout 0.1 with ops.PANEL_DROPOUT off; p0.1_stack_off (S-tail methods): dropout 0.1 with "
+                          "ops.STACK_DROPOUT off; p0.1_aten: dropout 0.1 with ops.FUSED_DROPOUT off",
               "steps": {}}
     if not a.skip_kernel:
         result["incidence_ln_reduce"] = kernel_times(a, dev)
@@ -223,6 +235,13 @@ def main():
                                        for k, e in panel.items()}
             if "mhnnm_b256_h256" in panel:
                 result["panel_switch_on_by_default_is_justified"] = panel["mhnnm_b256_h256"]["panel_faster_beyond_the_larger_spread"]
+        stack = {k: e for k, e in result["steps"].items() if "stack_faster_beyond_the_larger_spread" in e}
+        if stack:
+            result["stack_verdict"] = {k: ("stack faster than the row kernels beyond the larger spread"
+                                           if e["stack_faster_beyond_the_larger_spread"] else "not faster beyond the spreads")
+                                       for k, e in stack.items()}
+            if "egnn_equihnns_b256_h256" in stack:
+                result["stack_switch_on_by_default_is_justified"] = stack["egnn_equihnns_b256_h256"]["stack_faster_beyond_the_larger_spread"]
     line = json.dumps(result)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
