@@ -24,7 +24,18 @@
 // MFMA operand convention (lane l: r = l & 15, q = l >> 4): A[m = r][k = q], B[k = q][n = r],
 // D[m = 4 q + g][n = r] in accumulator component g.  Four MFMAs share one float4 of K: the j-th of them
 // takes component j on both sides, i.e. k = 16 s + 4 q + j (a permutation of K, which a sum does not see).
+//
+// Training dropout (template flag DROP, entry hg_readout_mse_drop_f32): the same body with up to three sites, keep = 0 or
+// 1 / (1 - p) from the hash of (seed in device memory, element index) of drop_hash.h, nothing stored:
+//   pre-pool (p_x)   x_b[c] = sum_n keep(n C + c) X[n, c] in the pooling phase, dX[n, c] = keep(n C + c) dxpool[b, c]: the
+//                    element of faf_dropout_add on the [N, C] rows;
+//   hidden 1, 2 (p_h) h_i[b, c] = keep_i(b H + c) LN_i(relu(.)), b the global molecule row: the element of
+//                    hg_bias_relu_ln_drop_*.  LDS holds the masked h_i (dW2, dw3 and the next product read it as it is); the
+//                    backward masks dh ahead of the LayerNorm backward and leaves the masked dh in LDS, so dgamma and dbeta
+//                    are column sums of it.
+// The p = 0 instantiations keep their argument block (RhArgs<false> is the `float eps` it replaces) and their statements.
 #include "common.h"
+#include "drop_hash.h"
 #include "mfma.h"
 
 namespace {
@@ -49,6 +60,50 @@ struct RhWeights {
 struct RhSlabs {   // per-workgroup partial gradients: [n_wg][H*C], [n_wg][H*H], [n_wg][3H] x 2, [n_wg][H+4]
     float *w1, *w2, *v1, *v2, *v3;
 };
+
+// The LayerNorms' eps and, with DROP, the dropout arguments: ONE kernel argument in the place of `float eps` (rowln.h's
+// LnArgs does the same for the row kernels).
+template <bool DROP>
+struct RhArgs {
+    float eps;
+};
+template <>
+struct RhArgs<true> {
+    float eps;
+    uint32_t thr_x, thr_h;      // drop_threshold(p_x), drop_threshold(p_h); thr_x = 0 skips the pre-pool site
+    float inv_x, inv_h;         // drop_inv_keep(.)
+    const int64_t *seed_x, *seed_h1, *seed_h2;
+};
+// what a thread derives from them once: one hash key per site
+struct RhSite {
+    DropKey key;
+    uint32_t thr;
+    float inv;
+};
+template <bool DROP>
+struct RhSites {
+    __device__ explicit RhSites(const RhArgs<DROP>&) {}
+};
+template <>
+struct RhSites<true> {
+    RhSite x, h1, h2;
+    __device__ explicit RhSites(const RhArgs<true>& a)
+        : x{drop_key(a.thr_x ? (uint64_t)*a.seed_x : 0), a.thr_x, a.inv_x},
+          h1{drop_key(a.thr_h ? (uint64_t)*a.seed_h1 : 0), a.thr_h, a.inv_h},
+          h2{drop_key(a.thr_h ? (uint64_t)*a.seed_h2 : 0), a.thr_h, a.inv_h} {}
+};
+// keep-scale of element row * H + c of a hidden site.  A lane's columns are l + 32 j, so it asks for the aligned pair
+// that holds c (keep_scale2's contract: an even index; row * H is even) and takes its half.
+__device__ __forceinline__ float rh_keep(const RhSite& s, int64_t row, int H, int c) {
+    float k0, k1;
+    keep_scale2(s.key, (uint64_t)row * (uint64_t)H + (uint64_t)(c & ~1), s.thr, s.inv, k0, k1);
+    return (c & 1) ? k1 : k0;
+}
+// v *= keep of the float4 at node row n, columns 4 cl .. 4 cl + 3 of the [N, C] rows (pre-pool site; C % 4 == 0)
+template <int C>
+__device__ __forceinline__ void rh_mask4(const RhSite& s, int n, int cl, float4& v) {
+    if (s.thr) keep_scale4(s.key, (uint64_t)n * (uint64_t)C + (uint64_t)(4 * cl), s.thr, s.inv, v);
+}
 
 // sum over the 32 lanes that share a row
 __device__ __forceinline__ float half_sum(float v) {
@@ -128,11 +183,13 @@ __device__ __forceinline__ void outer_rows(const float* sD, int ldd, const float
     }
 }
 
-// in place: sZ <- a = relu(z + bias); sXH <- (a - mean) * rstd; sH <- sXH * gamma + beta; 32 lanes per row
-template <int H>
+// in place: sZ <- a = relu(z + bias); sXH <- (a - mean) * rstd; sH <- sXH * gamma + beta; 32 lanes per row.
+// DROP: sH <- keep . (sXH * gamma + beta), keep of hidden site `layer` at molecule row b0 + row
+template <int H, bool DROP>
 __device__ __forceinline__ void relu_ln_rows(float* sZ, const float* __restrict__ bias,
                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                             float* sXH, float* sH, float* sRstd, int ld, float eps) {
+                                             float* sXH, float* sH, float* sRstd, int ld, float eps,
+                                             const RhSites<DROP>& ks, int layer, int b0) {
     constexpr int CPT = H / 32;
     const int row = threadIdx.x >> 5, l = threadIdx.x & 31;
     float a[CPT];
@@ -154,17 +211,24 @@ __device__ __forceinline__ void relu_ln_rows(float* sZ, const float* __restrict_
         const float xh = (a[j] - mu) * rstd;
         sZ[row * ld + c] = a[j];
         sXH[row * ld + c] = xh;
-        sH[row * ld + c] = fmaf(xh, gamma[c], beta[c]);
+        if constexpr (DROP)
+            sH[row * ld + c] = fmaf(xh, gamma[c], beta[c]) * rh_keep(layer == 1 ? ks.h1 : ks.h2, b0 + row, H, c);
+        else
+            sH[row * ld + c] = fmaf(xh, gamma[c], beta[c]);
     }
     if (l == 0) sRstd[row] = rstd;
 }
 
 // dz = [a > 0] * rstd * (dxh - mean(dxh) - xh * mean(dxh * xh)), dxh = dh * gamma; dh from sDH, or (sDH null)
-// dh[m][c] = dy[m] * w3[c] for the last hidden layer
-template <int H>
+// dh[m][c] = dy[m] * w3[c] for the last hidden layer.  DROP: dh is multiplied by the recomputed keep of hidden site `layer`
+// first, and the masked dh is left in sDHm (the layer's parameter sums read it there; sDHm may be sDH: own elements only).
+// (`layer` is a run-time argument, constant after inlining: as a template parameter it gave this helper two instantiations
+// where the p = 0 kernel inlines one function twice, and that reordered the p = 0 instruction streams)
+template <int H, bool DROP>
 __device__ __forceinline__ void relu_ln_bwd_rows(const float* sDH, const float* __restrict__ w3, const float* sDy,
                                                  const float* sA, const float* sXH, const float* __restrict__ gamma,
-                                                 const float* sRstd, float* sDZ, int ld) {
+                                                 const float* sRstd, float* sDZ, int ld, const RhSites<DROP>& ks, int layer,
+                                                 int b0, float* sDHm) {
     constexpr int CPT = H / 32;
     const int row = threadIdx.x >> 5, l = threadIdx.x & 31;
     float dxh[CPT], xh[CPT];
@@ -172,7 +236,11 @@ __device__ __forceinline__ void relu_ln_bwd_rows(const float* sDH, const float* 
 #pragma unroll
     for (int j = 0; j < CPT; ++j) {
         const int c = l + 32 * j;
-        const float dh = sDH ? sDH[row * ld + c] : sDy[row] * w3[c];
+        float dh = sDH ? sDH[row * ld + c] : sDy[row] * w3[c];
+        if constexpr (DROP) {
+            dh *= rh_keep(layer == 1 ? ks.h1 : ks.h2, b0 + row, H, c);
+            sDHm[row * ld + c] = dh;
+        }
         xh[j] = sXH[row * ld + c];
         dxh[j] = dh * gamma[c];
         s1 += dxh[j];
@@ -220,10 +288,10 @@ struct RhLds {
                          TOTAL = VEC + 7 * H + 4;   // VEC: b1 g1 be1 b2 g2 be2 w3 b3
 };
 
-template <int C, int H>
+template <int C, int H, bool DROP = false>
 __global__ void __launch_bounds__(RH_THREADS)
 k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n_graphs, int n_real, RhWeights w,
-              float eps, const float* __restrict__ target, float* __restrict__ y, float* __restrict__ loss,
+              RhArgs<DROP> ra, const float* __restrict__ target, float* __restrict__ y, float* __restrict__ loss,
               float* __restrict__ dX, RhSlabs slab, float* __restrict__ loss_part, int* __restrict__ state) {
     using L = RhLds<C, H>;
     constexpr int LX = L::LX, LH = L::LH;
@@ -248,6 +316,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b0 = blockIdx.x * RH_ROWS;
     const bool train = target != nullptr;
+    const float eps = ra.eps;
     RH_STAMP(0);
 
     // ---- requests issued first: the small parameter vectors (to LDS) and this wavefront's tile of W1
@@ -269,6 +338,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     const bool has_h_tile = wave < H / 16;
     float4 bw1[C / 16];
     if (has_h_tile) wt_tile_load<C>(w.w1, wave, lane, bw1);
+    const RhSites<DROP> ks(ra);     // (the seeds: three scalar loads behind the requests above)
 
     // ---- global_add_pool: wavefront w owns molecules 2w, 2w+1 of the tile; a row of X is C/4 float4 lanes, so
     // 64 / (C/4) atoms are read side by side, eight deep for each of the two molecules at once
@@ -293,8 +363,14 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
             }
 #pragma unroll
             for (int u = 0; u < DEEP; ++u) {
-                if (n0 + u * AP < end0) f4_add(acc0, v0[u]);
-                if (n1 + u * AP < end1) f4_add(acc1, v1[u]);
+                if (n0 + u * AP < end0) {
+                    if constexpr (DROP) rh_mask4<C>(ks.x, n0 + u * AP, cl, v0[u]);
+                    f4_add(acc0, v0[u]);
+                }
+                if (n1 + u * AP < end1) {
+                    if constexpr (DROP) rh_mask4<C>(ks.x, n1 + u * AP, cl, v1[u]);
+                    f4_add(acc1, v1[u]);
+                }
             }
         }
 #pragma unroll
@@ -327,7 +403,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     }
     __syncthreads();
     RH_STAMP(3);
-    relu_ln_rows<H>(sA1, vb1, vg1, vbe1, sXH1, sH1, sR1, LH, eps);
+    relu_ln_rows<H, DROP>(sA1, vb1, vg1, vbe1, sXH1, sH1, sR1, LH, eps, ks, 1, b0);
     __syncthreads();
     RH_STAMP(4);
     float cw2[H / 4];
@@ -337,7 +413,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     }
     __syncthreads();
     RH_STAMP(5);
-    relu_ln_rows<H>(sA2, vb2, vg2, vbe2, sXH2, sH2, sR2, LH, eps);
+    relu_ln_rows<H, DROP>(sA2, vb2, vg2, vbe2, sXH2, sH2, sR2, LH, eps, ks, 2, b0);
     __syncthreads();
     RH_STAMP(6);
     {
@@ -366,7 +442,8 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
 
     // ---- backward
     const int64_t wg = blockIdx.x;
-    relu_ln_bwd_rows<H>(nullptr, vw3, sDy, sA2, sXH2, vg2, sR2, sDZ2, LH);
+    // (DROP: the masked dh2 goes to sDZ1, which is free until the LayerNorm-1 backward two barriers on)
+    relu_ln_bwd_rows<H, DROP>(nullptr, vw3, sDy, sA2, sXH2, vg2, sR2, sDZ2, LH, ks, 2, b0, sDZ1);
     {   // dw3 | db3 | pad, and the squared-error partial (row order)
         float* v3 = slab.v3 + wg * (H + 4);
         const int t = threadIdx.x;
@@ -391,12 +468,13 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     if (has_h_tile) w_cols_mma<H>(sDZ2, LH, cw2, sDH1, LH, wave, lane);
     if (has_c0) w_cols_load<H, C>(w.w1, wave, lane, cw1a);
     if (has_c1) w_cols_load<H, C>(w.w1, wave + RH_WAVES, lane, cw1b);
-    ln_param_sums<H>(nullptr, vw3, sDy, sXH2, sDZ2, LH, slab.v2 + wg * 3 * H);
+    if constexpr (DROP) ln_param_sums<H>(sDZ1, nullptr, nullptr, sXH2, sDZ2, LH, slab.v2 + wg * 3 * H);
+    else ln_param_sums<H>(nullptr, vw3, sDy, sXH2, sDZ2, LH, slab.v2 + wg * 3 * H);
     outer_rows<H, H>(sDZ2, LH, sH1, LH, slab.w2 + wg * H * H, wave, lane);
     RH_STAMP(9);
     __syncthreads();
     RH_STAMP(10);
-    relu_ln_bwd_rows<H>(sDH1, nullptr, nullptr, sA1, sXH1, vg1, sR1, sDZ1, LH);
+    relu_ln_bwd_rows<H, DROP>(sDH1, nullptr, nullptr, sA1, sXH1, vg1, sR1, sDZ1, LH, ks, 1, b0, sDH1);
     __syncthreads();
     RH_STAMP(11);
     if (has_c0) w_cols_mma<H>(sDZ1, LH, cw1a, sDX, LX, wave, lane);
@@ -404,13 +482,18 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     __syncthreads();
     RH_STAMP(12);
 
-    // ---- dX[n, :] = dx[molecule(n), :] (zero rows for the padding molecules b >= n_real: their dy is 0)
+    // ---- dX[n, :] = dx[molecule(n), :] (zero rows for the padding molecules b >= n_real: their dy is 0); DROP: times the
+    // pre-pool keep of row n
     for (int mi = 2 * wave; mi < 2 * wave + 2; ++mi) {
         const int b = b0 + mi;
         if (b >= n_graphs) continue;
         const float4 g = *reinterpret_cast<const float4*>(sDX + mi * LX + 4 * cl);
         const int beg = rowptr[b], end = rowptr[b + 1];
-        for (int n = beg + sub; n < end; n += AP) *reinterpret_cast<float4*>(dX + (int64_t)n * C + 4 * cl) = g;
+        for (int n = beg + sub; n < end; n += AP) {
+            float4 gn = g;
+            if constexpr (DROP) rh_mask4<C>(ks.x, n, cl, gn);
+            *reinterpret_cast<float4*>(dX + (int64_t)n * C + 4 * cl) = gn;
+        }
     }
 
     RH_STAMP(13);
@@ -455,21 +538,21 @@ RhPlan rh_plan(int n_graphs, int C, int H) {
     return p;
 }
 
-template <int C, int H>
-int rh_launch(const float* x, const int32_t* rowptr, int n_graphs, int n_real, const RhWeights& w, float eps,
+template <int C, int H, bool DROP>
+int rh_launch(const float* x, const int32_t* rowptr, int n_graphs, int n_real, const RhWeights& w, const RhArgs<DROP>& ra,
               const float* target, float* y, float* loss, float* dx, const RhSlabs& slab, float* loss_part, int* state,
               int n_wg, hipStream_t stream) {
     constexpr size_t lds = (size_t)RhLds<C, H>::TOTAL * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS budget");
     static bool attr_set = false;
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_readout_mse<C, H>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_readout_mse<C, H, DROP>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return EQH_ERR_LAUNCH;
         attr_set = true;
     }
-    hipLaunchKernelGGL((k_readout_mse<C, H>), dim3(n_wg), dim3(RH_THREADS), lds, stream, x, rowptr, n_graphs, n_real, w,
-                       eps, target, y, loss, dx, slab, loss_part, state);
+    hipLaunchKernelGGL((k_readout_mse<C, H, DROP>), dim3(n_wg), dim3(RH_THREADS), lds, stream, x, rowptr, n_graphs, n_real, w,
+                       ra, target, y, loss, dx, slab, loss_part, state);
     EQH_CHECK_LAUNCH();
     return EQH_OK;
 }
@@ -491,10 +574,14 @@ extern "C" size_t hg_readout_mse_workspace_bytes(int32_t n_graphs, int32_t C, in
     return rh_plan(n_graphs, C, H).total * sizeof(float);
 }
 
-extern "C" int hg_readout_mse_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C,
-                                  int32_t H, const float* const* weights, float eps, const float* target, float* y,
-                                  float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
-                                  size_t workspace_bytes, int32_t* state, void* stream_) {
+namespace {
+
+// hg_readout_mse_f32 (DROP = false) and hg_readout_mse_drop_f32 (DROP = true): one host function
+template <bool DROP>
+int readout_mse(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C, int32_t H,
+                const float* const* weights, const RhArgs<DROP>& ra, const float* target, float* y, float* loss, float* dx,
+                float* const* dweights, int32_t accumulate, void* workspace, size_t workspace_bytes, int32_t* state,
+                void* stream_) {
     if (n_graphs < 0 || n_real < 0 || n_real > n_graphs || !hg_readout_mse_supported(C, H)) return EQH_ERR_ARG;
     if (n_graphs == 0) return EQH_OK;
     if (!x || !rowptr || !weights || !y) return EQH_ERR_ARG;
@@ -523,8 +610,8 @@ extern "C" int hg_readout_mse_f32(const float* x, const int32_t* rowptr, int32_t
     int rc = EQH_ERR_ARG;
 #define RH_CASE(CC, HH)                                                                                           \
     if (C == CC && H == HH)                                                                                       \
-        rc = rh_launch<CC, HH>(x, rowptr, n_graphs, n_real, w, eps, target, y, loss, dx, slab, loss_part, state, \
-                               p.n_wg, stream);
+        rc = rh_launch<CC, HH, DROP>(x, rowptr, n_graphs, n_real, w, ra, target, y, loss, dx, slab, loss_part, state, \
+                                     p.n_wg, stream);
     RH_CASE(64, 64) RH_CASE(64, 128) RH_CASE(128, 64) RH_CASE(128, 128) RH_CASE(256, 64) RH_CASE(256, 128)
 #undef RH_CASE
     if (rc || !train) return rc;
@@ -542,4 +629,28 @@ extern "C" int hg_readout_mse_f32(const float* x, const int32_t* rowptr, int32_t
     if (rc) return rc;
     return eqh_reduce_slabs3_async(slab.v3, p.n_wg, (int64_t)H + 4, dweights[8], dweights[9], ws + p.off_discard, H, 1,
                                    accumulate, stream);
+}
+
+}  // namespace
+
+extern "C" int hg_readout_mse_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C,
+                                  int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                                  float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
+                                  size_t workspace_bytes, int32_t* state, void* stream_) {
+    return readout_mse<false>(x, rowptr, n_graphs, n_real, C, H, weights, RhArgs<false>{eps}, target, y, loss, dx, dweights,
+                              accumulate, workspace, workspace_bytes, state, stream_);
+}
+
+extern "C" int hg_readout_mse_drop_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C,
+                                       int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                                       float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
+                                       size_t workspace_bytes, int32_t* state, float p_x, float p_h, const int64_t* seed_x,
+                                       const int64_t* seed_h1, const int64_t* seed_h2, void* stream_) {
+    // 0 <= p < 1 (a NaN fails the comparison), checked first; a call without an active site belongs to hg_readout_mse_f32
+    if (!(p_x >= 0.f && p_x < 1.f) || !(p_h >= 0.f && p_h < 1.f) || (p_x == 0.f && p_h == 0.f)) return EQH_ERR_ARG;
+    if ((p_x > 0.f && !seed_x) || (p_h > 0.f && (!seed_h1 || !seed_h2))) return EQH_ERR_ARG;
+    const RhArgs<true> ra{eps, drop_threshold(p_x), drop_threshold(p_h), drop_inv_keep(p_x), drop_inv_keep(p_h),
+                          seed_x, seed_h1, seed_h2};
+    return readout_mse<true>(x, rowptr, n_graphs, n_real, C, H, weights, ra, target, y, loss, dx, dweights, accumulate,
+                             workspace, workspace_bytes, state, stream_);
 }

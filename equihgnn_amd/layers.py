@@ -521,19 +521,25 @@ def head_loss(out, head):
     return ops.mse_loss(out[:nb], head[0][:nb])
 
 
-def readout(mlp_out, x, index: HyperIndex, taps=None, head=None):
+def readout(mlp_out, x, index: HyperIndex, taps=None, head=None, p_x=0.0, drop=None):
     """The tail of every wrapper: global_add_pool -> output MLP -> .view(-1) (equihnn_egnn.py:167-169,
     mhnn.py:216-218, equihnn_equiformer.py:91-93).  With ``head`` the training loss is returned instead, and
     when the head has the scripts' shape (three Linears, LayerNorm) pool, MLP, loss and the whole backward
-    pass of the head are one launch (ops.readout_mse)."""
+    pass of the head are one launch (ops.readout_mse).
+    ``p_x``, ``drop``: the wrapper's dropout in front of the pool (the S tail), its probability in effect and the callable
+    that applies it.  The one launch takes ``p_x`` as a site of its own (with the head's hidden-layer dropouts:
+    ops.readout_mse_drop_supported); every other path applies ``drop(x)`` first."""
     if head is not None and taps is None:
         ops.signal_point("readout")
         x2 = x.reshape(-1, x.shape[-1])
-        if ops.readout_mse_supported(x2, mlp_out) and head[0].is_cuda:
+        plain = p_x == 0.0 and ops.readout_mse_supported(x2, mlp_out)
+        if head[0].is_cuda and (plain or ops.readout_mse_drop_supported(x2, mlp_out, p_x)):
             loss, _ = ops.readout_mse(x2, index.pool.rowptr, mlp_out, head[0], head[1],
-                                      unit_grad=bool(head[2]) if len(head) > 2 else False)
+                                      unit_grad=bool(head[2]) if len(head) > 2 else False, p_x=p_x)
             ops.signal_point("after_readout")
             return loss
+    if drop is not None:
+        x = drop(x)
     xp = pool_sum(x, index)
     if taps is not None:
         taps["pool"] = xp

@@ -92,7 +92,9 @@ class _Wrapper(nn.Module):
     # (csrc/drop_hash.h) and their seeds, one per site, from one pool of 64 draws per forward pass, in this FIXED order:
     #   per application of a conv layer: the wrapper's input dropout(s) (x, then e), then the layer's MLPs W1, W2, W3 (W4),
     #   one seed per hidden layer of each; after the applications the dropout in front of the pool (the paired / M tails
-    #   draw theirs, x then e, after each application instead: mhnn.py:208-214), then the head's hidden layers.
+    #   draw theirs, x then e, after each application instead: mhnn.py:208-214), then the head's hidden layers.  On the
+    #   fused read-out (ops.READOUT_DROPOUT) the last three are sites of the one launch, drawn by ops.readout_mse in that
+    #   order: pre-pool (S tail), hidden 1, hidden 2.
     @property
     def _drop_p(self) -> float:
         return float(self.dropout.p) if (self.training and self.dropout.p > 0) else 0.0
@@ -176,7 +178,7 @@ class _STail(_Wrapper):
             res = self.conv.prepare(x0, index)   # layer-independent residual term, built once
             fuse_act = taps is None and isinstance(res, dict) and isinstance(self.act, nn.ReLU)   # ReLU in the GEMM epilogue
             x = _conv_layers(self, x, index, x0, res, fuse_act, taps)
-            return readout(self.mlp_out, self._drop(x), index, taps, head)
+            return readout(self.mlp_out, x, index, taps, head, p_x=self._drop_p, drop=self._drop)
 
 
 class _PairedBase(_Wrapper):

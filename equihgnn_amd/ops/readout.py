@@ -5,12 +5,20 @@ Part of equihgnn_amd.ops (host-side operators over libequihgnn_hip.so; no CPU fa
 from __future__ import annotations
 
 import ctypes
+import os
 
 import torch
 import torch.nn.functional as F
 
 from .. import hip
+from . import rows as _rows
 from ._base import (ACC_PARAMS, LINEAR_PARAMS, _acc_target, _f32c, _hand_out, _ptr, _require_gpu, _stream, _workspace, timed)
+from .frames import _dropout_seed
+
+# An active training dropout stays on the fused read-out head (the DROP form of csrc/readout.hip: the dropout in front of the
+# pool and the head's two hidden-layer dropouts inside the one launch).  False -- or ops.FUSED_DROPOUT False, or a probability
+# >= 1: the head runs as separate launches (dropout_add, pool, three Linears, two bias_relu_ln, mse_loss), as it did before.
+READOUT_DROPOUT = not os.environ.get("EQH_NO_READOUT_DROPOUT")
 
 
 class _MseLoss(torch.autograd.Function):
@@ -107,10 +115,12 @@ class _ReadoutMse(torch.autograd.Function):
     """pool -> MLP(C -> H -> H -> 1, LN) -> MSE with loss, dx and all parameter gradients from ONE launch
     (hg_readout_mse_f32).  The gradients are computed in forward(); backward() hands them out -- scaled by the
     incoming gradient unless ``unit_grad`` says it is the implicit 1 of ``loss.backward()``, in which case the
-    parameter gradients may already have been added to their persistent accumulators."""
+    parameter gradients may already have been added to their persistent accumulators.
+    ``drop`` = (p_x, p_h, seed_x, seed_h1, seed_h2) or None: the launch under training dropout (hg_readout_mse_drop_f32);
+    the seeds are int64 device tensors the kernel reads, so nothing is kept for the backward."""
 
     @staticmethod
-    def forward(ctx, x, rowptr, n_graphs, n_real, target, eps, unit_grad, params, *weights):
+    def forward(ctx, x, rowptr, n_graphs, n_real, target, eps, unit_grad, params, drop, *weights):
         _require_gpu(x, "readout_mse")
         dev = x.device
         x, target = _f32c(x), _f32c(target)
@@ -126,10 +136,15 @@ class _ReadoutMse(torch.autograd.Function):
         tg = [_acc_target(w) for w in params] if unit_grad else [None]
         in_place = all(t is not None for t in tg)
         grads = tg if in_place else [torch.empty_like(w) for w in ws_t]
-        hip.check(L.hg_readout_mse_f32(_ptr(x), _ptr(rowptr), n_graphs, n_real, C, H, vp(*[w.data_ptr() for w in ws_t]),
-                                       float(eps), _ptr(target), _ptr(y), _ptr(loss), _ptr(dx),
-                                       vp(*[g.data_ptr() for g in grads]), 1 if in_place else 0, _ptr(ws), ws_bytes,
-                                       _ptr(_readout_state(dev)), _stream(dev)), "hg_readout_mse_f32")
+        args = (_ptr(x), _ptr(rowptr), n_graphs, n_real, C, H, vp(*[w.data_ptr() for w in ws_t]), float(eps), _ptr(target),
+                _ptr(y), _ptr(loss), _ptr(dx), vp(*[g.data_ptr() for g in grads]), 1 if in_place else 0, _ptr(ws), ws_bytes,
+                _ptr(_readout_state(dev)))
+        if drop is None:
+            hip.check(L.hg_readout_mse_f32(*args, _stream(dev)), "hg_readout_mse_f32")
+        else:
+            p_x, p_h, seed_x, seed_h1, seed_h2 = drop
+            hip.check(L.hg_readout_mse_drop_f32(*args, p_x, p_h, _ptr(seed_x), _ptr(seed_h1), _ptr(seed_h2), _stream(dev)),
+                      "hg_readout_mse_drop_f32")
         ctx.unit_grad, ctx.in_place = unit_grad, in_place
         ctx.targets = tg if (unit_grad and not in_place) else [None] * 10
         ctx.held = (dx,) if in_place else (dx, *grads)
@@ -141,24 +156,25 @@ class _ReadoutMse(torch.autograd.Function):
     def backward(ctx, dloss, _dy):
         held = ctx.held
         if dloss is None:
-            return (None,) * 18
+            return (None,) * 19
         if not ctx.unit_grad:
             held = tuple(h * dloss for h in held)
         dx = held[0]
         dws = (None,) * 10 if ctx.in_place else tuple(_hand_out([g.view_as(g) for g in held[1:]], ctx.targets))
-        return (dx, None, None, None, None, None, None, None, *dws)
+        return (dx, None, None, None, None, None, None, None, None, *dws)
 
 
-def readout_mse_supported(x, mlp) -> bool:
-    """Whether ops.readout_mse takes this pooled-MLP head: 2-D fp32 device rows, MLP of three Linears with
-    LayerNorm hidden layers and one output, no active dropout, widths the kernel is built for."""
+def _head_drop_p(mlp) -> float:
+    """The head's hidden-layer dropout probability in effect (mlp.py:97): 0 in eval mode."""
+    return float(mlp.dropout) if (mlp.training and mlp.dropout > 0) else 0.0
+
+
+def _head_shape_ok(x, mlp) -> bool:
     lins = getattr(mlp, "lins", None)
     if lins is None or len(lins) != 3 or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32:
         return False
     norms = mlp.normalizations
     if mlp.InputNorm or not all(isinstance(n, torch.nn.LayerNorm) for n in norms[1:]):
-        return False
-    if mlp.training and mlp.dropout > 0:
         return False
     H, C = lins[0].weight.shape
     if lins[1].weight.shape != (H, H) or lins[2].weight.shape != (1, H) or x.shape[1] != C:
@@ -168,9 +184,29 @@ def readout_mse_supported(x, mlp) -> bool:
     return bool(hip.lib().hg_readout_mse_supported(C, H))
 
 
-def readout_mse(x, pool_rowptr, mlp, target, n_real=None, unit_grad=False):
+def readout_mse_supported(x, mlp) -> bool:
+    """Whether ops.readout_mse takes this pooled-MLP head without dropout: 2-D fp32 device rows, MLP of three Linears with
+    LayerNorm hidden layers and one output, no active dropout, widths the kernel is built for."""
+    return _head_drop_p(mlp) == 0.0 and _head_shape_ok(x, mlp)
+
+
+def readout_mse_drop_supported(x, mlp, p_x: float = 0.0) -> bool:
+    """Whether ops.readout_mse takes this head UNDER an active dropout -- ``p_x`` in front of the pool, the head's own behind
+    its hidden layers: the shapes of readout_mse_supported, ops.FUSED_DROPOUT and ops.READOUT_DROPOUT on, at least one
+    probability above 0 and both below 1."""
+    p_x, p_h = float(p_x), _head_drop_p(mlp)
+    if not (_rows.FUSED_DROPOUT and READOUT_DROPOUT) or not (0.0 <= p_x < 1.0 and p_h < 1.0) or (p_x == 0.0 and p_h == 0.0):
+        return False
+    return _head_shape_ok(x, mlp)
+
+
+def readout_mse(x, pool_rowptr, mlp, target, n_real=None, unit_grad=False, p_x=0.0, seeds=None):
     """(loss, predictions) of the readout head: x [N, C] node rows, pool_rowptr int32 [B+1] (sorted ``batch``),
-    ``mlp`` the output MLP, ``target`` [>= n_real]; loss = mean over the first n_real molecules."""
+    ``mlp`` the output MLP, ``target`` [>= n_real]; loss = mean over the first n_real molecules.
+    Under training dropout (``p_x`` > 0: dropout of the node rows in front of the pool; the head's own probability when it is
+    training) the launch is the dropout form, see readout_mse_drop_supported.  Its seeds are drawn through ``_dropout_seed`` in
+    the order pre-pool (only when ``p_x`` > 0), hidden layer 1, hidden layer 2 -- the order of the separate launches -- unless
+    ``seeds`` = (seed_x, seed_h1, seed_h2) gives them (int64 [1] device tensors; None for a site that is off)."""
     n_graphs = pool_rowptr.shape[0] - 1
     n_real = n_graphs if n_real is None else int(n_real)
     lins, norms = mlp.lins, mlp.normalizations
@@ -180,4 +216,13 @@ def readout_mse(x, pool_rowptr, mlp, target, n_real=None, unit_grad=False):
         for w in weights:
             if w.requires_grad and w.is_leaf:
                 (LINEAR_PARAMS if w.dim() == 2 else ACC_PARAMS)[id(w)] = w
-    return _ReadoutMse.apply(x, pool_rowptr, n_graphs, n_real, target, norms[1].eps, unit_grad, weights, *weights)
+    p_x, p_h = float(p_x), _head_drop_p(mlp)
+    if not (0.0 <= p_x < 1.0 and p_h < 1.0):
+        raise ValueError(f"readout_mse: dropout probabilities have to be in [0, 1), but got p_x = {p_x}, p_h = {p_h}")
+    drop = None
+    if p_x > 0.0 or p_h > 0.0:
+        if seeds is None:
+            seed_x = _dropout_seed(x.device, p_x)
+            seeds = (seed_x, _dropout_seed(x.device, p_h), _dropout_seed(x.device, p_h))
+        drop = (p_x, p_h, *seeds)
+    return _ReadoutMse.apply(x, pool_rowptr, n_graphs, n_real, target, norms[1].eps, unit_grad, weights, drop, *weights)

@@ -1016,6 +1016,20 @@ int hg_readout_mse_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, 
                        int32_t H, const float* const* weights, float eps, const float* target, float* y,
                        float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
                        size_t workspace_bytes, int32_t* state, void* stream);
+/* The same launch under training dropout (mlp.py:97 in the head, and the wrapper's dropout in front of the pool), up to
+ * three sites, each kept element scaled by 1 / (1 - p) and decided by the hash of (*seed, element index) of the faf_* and
+ * hg_*_drop_* entries; the seeds are int64 in device memory, read by the kernel, and nothing is stored:
+ *   p_x, seed_x   the node rows in front of the pool: x_b = sum_n keep(n C + c) x[n, c], dx[n, c] = keep(n C + c) dxpool[b, c]
+ *                 -- the element of faf_dropout_add on x [n_nodes, C]; p_x = 0 skips the site (seed_x may be NULL);
+ *   p_h, seed_h1, seed_h2   the two hidden layers: h_i[b, c] = keep_i(b H + c) LN_i(relu(.)), b the molecule row -- the
+ *                 element of hg_bias_relu_ln_drop_fwd on [n_graphs, H]; p_h = 0 skips both (the seeds may be NULL).
+ * Shares hg_readout_mse_supported and hg_readout_mse_workspace_bytes.  EQH_ERR_ARG (checked first): a probability outside
+ * [0, 1), a NULL seed of an active site, or p_x = p_h = 0 (that call belongs to hg_readout_mse_f32). */
+int hg_readout_mse_drop_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C,
+                            int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                            float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
+                            size_t workspace_bytes, int32_t* state, float p_x, float p_h, const int64_t* seed_x,
+                            const int64_t* seed_h1, const int64_t* seed_h2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Elementwise passes of FAFormer's SwiGLU MLP (fa_former_layer.py:241-289) and its 8-frame average (:61-120):

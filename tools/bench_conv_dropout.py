@@ -10,7 +10,10 @@ bench.py).  Prints ONE JSON line and writes it to ``--out`` (default profiles/co
   methods only: dropout 0.1 with ``ops.PANEL_DROPOUT = False`` -- an MHNNConv with an active dropout leaves the panels for the
   row kernels, the path before that switch existed), ``p0.1_stack_off`` (the S-tail methods only: dropout 0.1 with
   ``ops.STACK_DROPOUT = False`` -- the conv stack leaves the panels for the loop over the row kernels, the path before that
-  switch existed and its yardstick) and ``p0.1_aten`` (dropout 0.1 with ``ops.FUSED_DROPOUT`` off: ReLU,
+  switch existed and its yardstick), ``p0.1_readout_off`` (``egnn_equihnns``, ``mhnns`` and ``mhnnm``: dropout 0.1 with
+  ``ops.READOUT_DROPOUT = False`` -- the read-out head leaves its one launch for dropout_add, pool, three Linears, two
+  bias_relu_ln and the loss, the path before that switch existed and its yardstick) and ``p0.1_aten`` (dropout 0.1 with
+  ``ops.FUSED_DROPOUT`` off: ReLU,
   LayerNorm and F.dropout as ATen launches on materialised rows, the path before either switch existed).  One model and one
   trainer per variant, fed copies of the same resident batches; after a warm-up the variants run in interleaved blocks of
   ``--steps`` steps on a host clock around a device synchronise.  The switches are set ahead of every block, so a capture
@@ -23,7 +26,7 @@ Per variant: the median block, ``spread`` = (max - min) / median of its blocks. 
 step is faster than the ATen step by more than both spreads -- the condition for ``FUSED_DROPOUT`` to be on by default --
 and ``panel_verdict`` whether the panel step beats the row-kernel step by more than the larger of the two spreads -- the
 condition for ``PANEL_DROPOUT``, decided by ``mhnnm``; ``stack_verdict`` the same for ``STACK_DROPOUT``, decided by
-``egnn_equihnns``.
+``egnn_equihnns``; ``readout_verdict`` the same for ``READOUT_DROPOUT``, decided by ``egnn_equihnns``.
 
     python tools/bench_conv_dropout.py [--blocks 7] [--steps 10] [--warmup 5] [--inner 3] [--skip-steps] [--skip-kernel]
                                        [--methods mhnnm,egnn_equihnnm] [--variants p0,p0.1_fused,p0.1_rows]
@@ -44,12 +47,14 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 REPS = 10
-# (name, dropout, ops.FUSED_DROPOUT, ops.PANEL_DROPOUT, ops.STACK_DROPOUT)
-VARIANTS = (("p0", 0.0, True, True, True), ("p0.1_fused", 0.1, True, True, True), ("p0.1_rows", 0.1, True, False, True),
-            ("p0.1_stack_off", 0.1, True, True, False), ("p0.1_aten", 0.1, False, True, True))
+# (name, dropout, ops.FUSED_DROPOUT, ops.PANEL_DROPOUT, ops.STACK_DROPOUT, ops.READOUT_DROPOUT)
+VARIANTS = (("p0", 0.0, True, True, True, True), ("p0.1_fused", 0.1, True, True, True, True),
+            ("p0.1_rows", 0.1, True, False, True, True), ("p0.1_stack_off", 0.1, True, True, False, True),
+            ("p0.1_readout_off", 0.1, True, True, True, False), ("p0.1_aten", 0.1, False, True, True, True))
 STEPS = {"egnn_equihnns": 1000, "mhnnm": 2000, "egnn_equihnnm": 3000, "mhnns": 4000, "faformer_equihnns": 5000}   # method -> seed of its batches
 MHNN_CONV = ("mhnnm", "egnn_equihnnm")                                      # methods whose conv is MHNNConv: the panel switch matters
 S_TAIL = ("egnn_equihnns", "mhnns", "faformer_equihnns")                    # methods on the S tail: the stack switch matters
+READOUT = ("egnn_equihnns", "mhnns", "mhnnm")                               # methods the read-out switch is measured on
 
 
 def _stat(ts):
@@ -69,13 +74,13 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
     tgt = tuple(max(e[i] for e in ext) for i in range(3))
     batches, trainers, counters = {}, {}, {}
     variants = [v for v in VARIANTS if v[0] in a.variants and (v[0] != "p0.1_rows" or method in MHNN_CONV)
-                and (v[0] != "p0.1_stack_off" or method in S_TAIL)]
-    stack_default = ops.STACK_DROPOUT
+                and (v[0] != "p0.1_stack_off" or method in S_TAIL) and (v[0] != "p0.1_readout_off" or method in READOUT)]
+    stack_default, readout_default = ops.STACK_DROPOUT, ops.READOUT_DROPOUT
 
-    def switches(fused, panel, stack):
-        ops.FUSED_DROPOUT, ops.PANEL_DROPOUT, ops.STACK_DROPOUT = fused, panel, stack
+    def switches(fused, panel, stack, readout):
+        ops.FUSED_DROPOUT, ops.PANEL_DROPOUT, ops.STACK_DROPOUT, ops.READOUT_DROPOUT = fused, panel, stack, readout
 
-    for name, p, _, _, _ in variants:
+    for name, p, *_ in variants:
         batches[name] = [pad_batch(b, *tgt).packed().to(dev) for b in host]     # (a trainer caches its index on its batches)
         for b in batches[name]:
             b.num_real_graphs = batch
@@ -91,8 +96,8 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
         counters[name] = n + 1
 
     try:
-        for name, _, fused, panel, stack in variants:     # bootstrap, calibration, capture and warm-up of each variant
-            switches(fused, panel, stack)
+        for name, _, *sw in variants:     # bootstrap, calibration, capture and warm-up of each variant
+            switches(*sw)
             for _ in range(2):
                 step(name)
             while getattr(trainers[name], "calibrating", False):
@@ -101,8 +106,8 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
                 step(name)
         times = {v[0]: [] for v in variants}
         for _ in range(a.blocks):
-            for name, _, fused, panel, stack in variants:
-                switches(fused, panel, stack)
+            for name, _, *sw in variants:
+                switches(*sw)
                 step(name)                                # (the first step after a switch of trainers is not timed)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -111,7 +116,7 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
                 torch.cuda.synchronize()
                 times[name].append((time.perf_counter() - t0) / a.steps * 1e3)
     finally:
-        switches(True, True, stack_default)
+        switches(True, True, stack_default, readout_default)
     out = {"molecules": batch, "flavour": "qm9", "hidden": hidden, "graphs": {n: len(t.slots) for n, t in trainers.items()}}
     base, _ = _stat(times["p0"])
     for name, ts in times.items():
@@ -127,6 +132,10 @@ def step_times(method, batch, seed0, a, dev, hidden=256):
     if f and k:     # the conv stack under dropout against the loop over the row kernels it left the panels for
         out["stack_vs_stack_off"] = round(f["ms"] / k["ms"], 4)
         out["stack_faster_beyond_the_larger_spread"] = bool((k["ms"] - f["ms"]) / k["ms"] > max(f["spread"], k["spread"]))
+    o = out.get("p0.1_readout_off")
+    if f and o:     # the fused read-out head under dropout against the separate launches it left its one launch for
+        out["readout_vs_readout_off"] = round(f["ms"] / o["ms"], 4)
+        out["readout_faster_beyond_the_larger_spread"] = bool((o["ms"] - f["ms"]) / o["ms"] > max(f["spread"], o["spread"]))
     for tr in trainers.values():
         tr.close()
     del trainers, batches
@@ -216,7 +225,8 @@ def main():
                         "device events; median block, spread = (max - min) / median",
               "variants": "p0: dropout 0; p0.1_fused: dropout 0.1 with ops.FUSED_DROPOUT and ops.PANEL_DROPOUT on; p0.1_rows (MHNNConv "
                           "methods): dropout 0.1 with ops.PANEL_DROPOUT off; p0.1_stack_off (S-tail methods): dropout 0.1 with "
-                          "ops.STACK_DROPOUT off; p0.1_aten: dropout 0.1 with ops.FUSED_DROPOUT off",
+                          "ops.STACK_DROPOUT off; p0.1_readout_off (egnn_equihnns, mhnns, mhnnm): dropout 0.1 with "
+                          "ops.READOUT_DROPOUT off; p0.1_aten: dropout 0.1 with ops.FUSED_DROPOUT off",
               "steps": {}}
     if not a.skip_kernel:
         result["incidence_ln_reduce"] = kernel_times(a, dev)
@@ -242,6 +252,13 @@ def main():
                                        for k, e in stack.items()}
             if "egnn_equihnns_b256_h256" in stack:
                 result["stack_switch_on_by_default_is_justified"] = stack["egnn_equihnns_b256_h256"]["stack_faster_beyond_the_larger_spread"]
+        ro = {k: e for k, e in result["steps"].items() if "readout_faster_beyond_the_larger_spread" in e}
+        if ro:
+            result["readout_verdict"] = {k: ("fused read-out faster than the separate launches beyond the larger spread"
+                                             if e["readout_faster_beyond_the_larger_spread"] else "not faster beyond the spreads")
+                                         for k, e in ro.items()}
+            if "egnn_equihnns_b256_h256" in ro:
+                result["readout_switch_on_by_default_is_justified"] = ro["egnn_equihnns_b256_h256"]["readout_faster_beyond_the_larger_spread"]
     line = json.dumps(result)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
