@@ -94,7 +94,9 @@ class _Wrapper(nn.Module):
     #   one seed per hidden layer of each; after the applications the dropout in front of the pool (the paired / M tails
     #   draw theirs, x then e, after each application instead: mhnn.py:208-214), then the head's hidden layers.  On the
     #   fused read-out (ops.READOUT_DROPOUT) the last three are sites of the one launch, drawn by ops.readout_mse in that
-    #   order: pre-pool (S tail), hidden 1, hidden 2.
+    #   order: pre-pool (S tail), hidden 1, hidden 2.  On the paired tail's one-launch head (ops.PAIRED_READOUT) the LAST
+    #   application's x and e dropouts and the head's two are the four sites of that launch, drawn by ops.readout_pair_mse
+    #   in the same order: x, e, hidden 1, hidden 2.
     @property
     def _drop_p(self) -> float:
         return float(self.dropout.p) if (self.training and self.dropout.p > 0) else 0.0
@@ -212,11 +214,26 @@ class _PairedBase(_Wrapper):
                     x, e = self.conv(x, e, index)
                     if i != self.nlayer - 1:
                         x, e = self.act(x), self.act(e)
+                    elif self._one_launch_head(x, e, taps, head):
+                        # the last application's two dropouts, the pools, the head, the loss and their backward: one launch
+                        loss, _ = ops.readout_pair_mse(x, e, index, data.n_e, data.e_order, self.mlp_out, head[0], head[1],
+                                                       unit_grad=bool(head[2]) if len(head) > 2 else False, p_x=self._drop_p)
+                        return loss
                     x, e = self._drop(x), self._drop(e)
             both = self._pool(x, e, index, data)
             if taps is not None:
                 taps["pool"] = both
             return head_loss(self.mlp_out(both, mask=index.pad_masks()[3]).view(-1), head)
+
+    def _one_launch_head(self, x, e, taps, head) -> bool:
+        """Whether the tail ends in ops.readout_pair_mse: training mode, a loss is asked for, nothing is tapped, ops.PAIRED_READOUT
+        is on and the head has a shape the launch is built for (under an active dropout: its dropout form)."""
+        if head is None or taps is not None or not (self.training and ops.PAIRED_READOUT and x.is_cuda and head[0].is_cuda):
+            return False
+        p_x = self._drop_p
+        if p_x == 0.0 and ops.readout_pair_mse_supported(x, e, self.mlp_out):
+            return True
+        return ops.readout_pair_mse_drop_supported(x, e, self.mlp_out, p_x)
 
     fused_pool = False   # the read-out as ONE launch each way (ops.pool_pair) instead of mask, product, two reduces and a cat
 

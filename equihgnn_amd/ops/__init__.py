@@ -73,7 +73,8 @@ from .egnn import (  # noqa: F401
 )
 from .readout import (  # noqa: F401
     _MseLoss, mse_loss, _READOUT_STATE, _readout_state, _ReadoutMse, readout_mse_supported, readout_mse, _PoolPair, pool_pair,
-    pool_pair_bytes, readout_mse_drop_supported, READOUT_DROPOUT,
+    pool_pair_bytes, readout_mse_drop_supported, READOUT_DROPOUT, _ReadoutPairMse, readout_pair_mse,
+    readout_pair_mse_supported, readout_pair_mse_drop_supported, PAIRED_READOUT,
 )
 from .se3 import (  # noqa: F401
     _RowGemm, _RowGemm2, _RadialWeightLayout, radial_weight_layout, _AttnPool, attn_pool_supported, attn_pool,
@@ -108,6 +109,7 @@ _SWITCH_OWNER = {
     "TIMELINE": "_base",
     "SIGNAL": "_base",
     "NODE_LN_FOLD": "egnn",
+    "PAIRED_READOUT": "readout",
     "PANEL_DROPOUT": "mhnn_panel",
     "READOUT_DROPOUT": "readout",
     "STACK_DROPOUT": "conv_stack",

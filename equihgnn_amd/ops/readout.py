@@ -1,4 +1,5 @@
-"""Readout head (pool + output MLP + MSE in one launch), the paired node / high-order-hyperedge pool and the fused MSE loss.
+"""Readout heads (pool + output MLP + MSE in one launch: the S / M tails' and the paired tail's), the paired node /
+high-order-hyperedge pool and the fused MSE loss.
 
 Part of equihgnn_amd.ops (host-side operators over libequihgnn_hip.so; no CPU fallback).
 """
@@ -19,6 +20,12 @@ from .frames import _dropout_seed
 # pool and the head's two hidden-layer dropouts inside the one launch).  False -- or ops.FUSED_DROPOUT False, or a probability
 # >= 1: the head runs as separate launches (dropout_add, pool, three Linears, two bias_relu_ln, mse_loss), as it did before.
 READOUT_DROPOUT = not os.environ.get("EQH_NO_READOUT_DROPOUT")
+
+# The paired tail's head (models._PairedBase: [node pool | pool of the hyperedges of order > 2] -> MLP(2C -> H -> H -> 1) -> MSE)
+# as ONE launch, csrc/readout_pair.hip, its dropout sites included.  False: the separate launches (the last application's two
+# dropout_add passes, the pool, three Linears, two bias_relu_ln, mse_loss), as before.  On by default (DESIGN.md section 4.8:
+# 0.18 ms of the mhnn / egnn_equihnn step); EQH_NO_PAIRED_READOUT switches it off, EQH_PAIRED_READOUT=0 does the same.
+PAIRED_READOUT = not os.environ.get("EQH_NO_PAIRED_READOUT") and os.environ.get("EQH_PAIRED_READOUT", "1") != "0"
 
 
 class _MseLoss(torch.autograd.Function):
@@ -226,3 +233,133 @@ def readout_mse(x, pool_rowptr, mlp, target, n_real=None, unit_grad=False, p_x=0
             seeds = (seed_x, _dropout_seed(x.device, p_h), _dropout_seed(x.device, p_h))
         drop = (p_x, p_h, *seeds)
     return _ReadoutMse.apply(x, pool_rowptr, n_graphs, n_real, target, norms[1].eps, unit_grad, weights, drop, *weights)
+
+
+class _ReadoutPairMse(torch.autograd.Function):
+    """[node pool | order > 2 hyperedge pool] -> MLP(2C -> H -> H -> 1, LN) -> MSE with loss, dx, de and all parameter gradients
+    from ONE launch (hg_readout_pair_mse_f32): _ReadoutMse for the paired tail.  The gradients are computed in forward();
+    backward() hands them out, scaled by the incoming gradient unless ``unit_grad``.
+    ``drop`` = (p_x, p_h, seed_x, seed_e, seed_h1, seed_h2) or None (hg_readout_pair_mse_drop_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, e, rowptr, he_pool, e_order, n_graphs, n_real, target, eps, unit_grad, params, drop, *weights):
+        _require_gpu(x, "readout_pair_mse")
+        dev = x.device
+        x, e, target = _f32c(x), _f32c(e), _f32c(target)
+        ws_t = [_f32c(w.detach()) for w in weights]
+        H, C = ws_t[0].shape[0], x.shape[1]
+        L = hip.lib()
+        vp = ctypes.c_void_p * 10
+        y = torch.empty(n_graphs, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dx, de = torch.empty_like(x), torch.empty_like(e)
+        ws_bytes = L.hg_readout_pair_mse_workspace_bytes(n_graphs, C, H)
+        ws = _workspace(ws_bytes, dev)
+        tg = [_acc_target(w) for w in params] if unit_grad else [None]
+        in_place = all(t is not None for t in tg)
+        grads = tg if in_place else [torch.empty_like(w) for w in ws_t]
+        args = (_ptr(x), _ptr(rowptr), _ptr(e), _ptr(he_pool.rowptr), _ptr(he_pool.perm), _ptr(e_order), e.shape[0], n_graphs,
+                n_real, C, H, vp(*[w.data_ptr() for w in ws_t]), float(eps), _ptr(target), _ptr(y), _ptr(loss), _ptr(dx),
+                _ptr(de), vp(*[g.data_ptr() for g in grads]), 1 if in_place else 0, _ptr(ws), ws_bytes,
+                _ptr(_readout_state(dev)))
+        if drop is None:
+            hip.check(L.hg_readout_pair_mse_f32(*args, _stream(dev)), "hg_readout_pair_mse_f32")
+        else:
+            p_x, p_h, seed_x, seed_e, seed_h1, seed_h2 = drop
+            hip.check(L.hg_readout_pair_mse_drop_f32(*args, p_x, p_h, _ptr(seed_x), _ptr(seed_e), _ptr(seed_h1), _ptr(seed_h2),
+                                                     _stream(dev)), "hg_readout_pair_mse_drop_f32")
+        ctx.unit_grad, ctx.in_place = unit_grad, in_place
+        ctx.targets = tg if (unit_grad and not in_place) else [None] * 10
+        ctx.held = (dx, de) if in_place else (dx, de, *grads)
+        ctx.mark_non_differentiable(y)
+        ctx.set_materialize_grads(False)
+        return loss, y
+
+    @staticmethod
+    def backward(ctx, dloss, _dy):
+        held = ctx.held
+        if dloss is None:
+            return (None,) * 22
+        if not ctx.unit_grad:
+            held = tuple(h * dloss for h in held)
+        dx, de = held[0], held[1]
+        dws = (None,) * 10 if ctx.in_place else tuple(_hand_out([g.view_as(g) for g in held[2:]], ctx.targets))
+        return (dx, de, None, None, None, None, None, None, None, None, None, None, *dws)
+
+
+def _pair_mlp_ok(mlp, C: int) -> bool:
+    """The head's side of the question (no tensor, no device): three Linears 2C -> H -> H -> 1, LayerNorm behind both hidden
+    layers with one eps, no InputNorm, (C, H) the kernel is built for."""
+    lins = getattr(mlp, "lins", None)
+    if lins is None or len(lins) != 3:
+        return False
+    norms = mlp.normalizations
+    if mlp.InputNorm or not all(isinstance(n, torch.nn.LayerNorm) for n in norms[1:]):
+        return False
+    H = lins[0].weight.shape[0]
+    if lins[0].in_features != 2 * C or lins[1].weight.shape != (H, H) or lins[2].weight.shape != (1, H):
+        return False
+    if norms[1].eps != norms[2].eps:
+        return False
+    return bool(hip.lib().hg_readout_pair_mse_supported(C, H))
+
+
+def _pair_head_shape_ok(x, e, mlp) -> bool:
+    for t in (x, e):
+        if not t.is_cuda or t.dim() != 2 or t.dtype != torch.float32:
+            return False
+    return e.shape[1] == x.shape[1] and _pair_mlp_ok(mlp, x.shape[1])
+
+
+def readout_pair_mse_supported(x, e, mlp) -> bool:
+    """Whether ops.readout_pair_mse takes this head without dropout: x [N, C] and e [M, C] 2-D fp32 device rows, MLP of three
+    Linears (the first on 2C inputs) with LayerNorm hidden layers and one output, no active dropout, widths the kernel is built
+    for (C in 64 / 128 / 256, hidden width 128 / 256)."""
+    return _head_drop_p(mlp) == 0.0 and _pair_head_shape_ok(x, e, mlp)
+
+
+def readout_pair_mse_drop_supported(x, e, mlp, p_x: float = 0.0) -> bool:
+    """... UNDER an active dropout (``p_x`` on x and e in front of the pools, the head's own behind its hidden layers): the shapes
+    of readout_pair_mse_supported, ops.FUSED_DROPOUT and ops.READOUT_DROPOUT on, a probability above 0, both below 1."""
+    p_x, p_h = float(p_x), _head_drop_p(mlp)
+    if not (_rows.FUSED_DROPOUT and READOUT_DROPOUT) or not (0.0 <= p_x < 1.0 and p_h < 1.0) or (p_x == 0.0 and p_h == 0.0):
+        return False
+    return _pair_head_shape_ok(x, e, mlp)
+
+
+def readout_pair_mse(x, e, index, n_e, e_order, mlp, target, n_real=None, unit_grad=False, p_x=0.0, seeds=None):
+    """(loss, predictions) of the paired tail's head: x [N, C] node rows and e [M, C] hyperedge rows of the batch of ``index``
+    (its atom pool and, from ``n_e``, its hyperedge pool), ``e_order`` int64 [M] (only hyperedges of order > 2 are pooled),
+    ``mlp`` the output MLP on [B, 2C], ``target`` [>= n_real]; loss = mean over the first n_real molecules.
+    Under training dropout (``p_x`` > 0 on x and on e in front of the pools; the head's own probability when it is training)
+    the launch is the dropout form.  Its seeds are drawn through ``_dropout_seed`` in the order x, e (both only when ``p_x`` >
+    0), hidden layer 1, hidden layer 2 -- the order of the separate launches -- unless ``seeds`` = (seed_x, seed_e, seed_h1,
+    seed_h2) gives them (int64 [1] device tensors; None for a site that is off)."""
+    if x.dim() != 2 or e.dim() != 2 or x.shape[1] != e.shape[1]:
+        raise ValueError(f"readout_pair_mse: x [N, C] and e [M, C] of one width, got {tuple(x.shape)} and {tuple(e.shape)}")
+    he_pool, _ = index.hyperedge_pool(n_e)
+    n_graphs = index.pool.n_rows
+    if he_pool.n_rows != n_graphs or e_order.shape[0] != e.shape[0] or x.shape[0] != index.N:
+        raise ValueError("readout_pair_mse: x, e, n_e and e_order do not belong to this index's batch")
+    if e_order.dtype != torch.int64:
+        raise TypeError(f"readout_pair_mse: e_order must be int64, got {e_order.dtype}")
+    n_real = n_graphs if n_real is None else int(n_real)
+    lins, norms = mlp.lins, mlp.normalizations
+    weights = (lins[0].weight, lins[0].bias, norms[1].weight, norms[1].bias, lins[1].weight, lins[1].bias,
+               norms[2].weight, norms[2].bias, lins[2].weight, lins[2].bias)
+    if torch.is_grad_enabled():
+        for w in weights:
+            if w.requires_grad and w.is_leaf:
+                (LINEAR_PARAMS if w.dim() == 2 else ACC_PARAMS)[id(w)] = w
+    p_x, p_h = float(p_x), _head_drop_p(mlp)
+    if not (0.0 <= p_x < 1.0 and p_h < 1.0):
+        raise ValueError(f"readout_pair_mse: dropout probabilities have to be in [0, 1), but got p_x = {p_x}, p_h = {p_h}")
+    drop = None
+    if p_x > 0.0 or p_h > 0.0:
+        if seeds is None:
+            seed_x = _dropout_seed(x.device, p_x)
+            seed_e = _dropout_seed(x.device, p_x)
+            seeds = (seed_x, seed_e, _dropout_seed(x.device, p_h), _dropout_seed(x.device, p_h))
+        drop = (p_x, p_h, *seeds)
+    return _ReadoutPairMse.apply(x, e, index.pool.rowptr, he_pool, e_order.contiguous(), n_graphs, n_real, target, norms[1].eps,
+                                 unit_grad, weights, drop, *weights)

@@ -18,6 +18,8 @@ into two / one plane in registers and sum three / one bf16 terms into fp32.  Whe
 independent.  Products that go to none of these (the fp32 library below its threshold, the EGNN edge kernel without the `edges`
 flag, the single-product and skinny weight gradients hg_wgrad_f32 and hg_wgrad_skinny_f32) and all row-wise work (the
 recomputation of h, SiLU and its derivative, dwd, the row sums of dA / dB, every reduction) stay at fp32 grade in every mode.
+So do the two one-launch read-out heads (csrc/readout.hip, csrc/readout_pair.hip): every product in them, the paired head's
+[16, 2C] x [2C, H] first layer included, is the fp32 16 x 16 x 4 MFMA whatever the word and the flags say.
 ops.products and the panel operators read the mode at call time (an autograd node of the panel
 operators, and of the edge update, multiplies its backward pass as it multiplied its forward pass); a captured step replays the
 mode it was captured under (trainer keys its graphs by the word and the three flags; ops.wgrad_batch reads the mode when it runs, at defer_flush).

@@ -1032,6 +1032,38 @@ int hg_readout_mse_drop_f32(const float* x, const int32_t* rowptr, int32_t n_gra
                             const int64_t* seed_h1, const int64_t* seed_h2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same head for the paired tail (mhnn.py:58,72, equihnn_fa_former.py:99-101), one launch (csrc/readout_pair.hip):
+ *   z_b  = [ sum_{n in molecule b} x[n, :]  |  sum_{m in molecule b, e_order[m] > 2} e[m, :] ]        [2C]
+ *   then MLP(2C -> H -> H -> 1, LayerNorm after ReLU), the MSE over the first n_real molecules and the whole backward.
+ *   x [n_nodes, C] with rowptr int32 [n_graphs + 1] as in hg_readout_mse_f32; e [n_e, C] with the hyperedge pool of
+ *   hg_pool_pair_fwd: e_rowptr int32 [n_graphs + 1] and e_perm int32 (NULL: the identity; an entry that is negative or
+ *   >= n_e is skipped), e_order int64 [n_e].  n_e == 0 needs none of the e pointers.  A molecule without atoms, or without
+ *   a hyperedge of order > 2, pools to zeros in that half.
+ *   weights[10] as in hg_readout_mse_f32 with W1 [H, 2C].  With a target: dx [n_nodes, C] and de [n_e, C] are written for
+ *   every row that the two pools list (rows of the molecules b >= n_real and hyperedge rows of order <= 2: exact zeros),
+ *   dweights[10], loss [1].  state, accumulate, workspace: as in hg_readout_mse_f32.
+ * Supported: C in {64,128,256}, H in {128,256}.  fp32 MFMA in every matmul-precision mode.
+ * The _drop_ form: up to four sites, kept elements scaled by 1 / (1 - p), decided by the hash of (*seed, element index):
+ *   p_x, seed_x   element n C + c of x (faf_dropout_add on [n_nodes, C]);  p_x, seed_e   element m C + c of e [n_e, C];
+ *   p_h, seed_h1, seed_h2   element b H + c of the two hidden layers (hg_bias_relu_ln_drop_fwd on [n_graphs, H]).
+ * EQH_ERR_ARG (checked first): a probability outside [0, 1), a NULL seed of an active site, or p_x = p_h = 0.
+ * ------------------------------------------------------------------------------------------- */
+int hg_readout_pair_mse_supported(int32_t C, int32_t H);
+size_t hg_readout_pair_mse_workspace_bytes(int32_t n_graphs, int32_t C, int32_t H);
+int hg_readout_pair_mse_f32(const float* x, const int32_t* rowptr, const float* e, const int32_t* e_rowptr,
+                            const int32_t* e_perm, const int64_t* e_order, int32_t n_e, int32_t n_graphs, int32_t n_real,
+                            int32_t C, int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                            float* loss, float* dx, float* de, float* const* dweights, int32_t accumulate, void* workspace,
+                            size_t workspace_bytes, int32_t* state, void* stream);
+int hg_readout_pair_mse_drop_f32(const float* x, const int32_t* rowptr, const float* e, const int32_t* e_rowptr,
+                                 const int32_t* e_perm, const int64_t* e_order, int32_t n_e, int32_t n_graphs,
+                                 int32_t n_real, int32_t C, int32_t H, const float* const* weights, float eps,
+                                 const float* target, float* y, float* loss, float* dx, float* de,
+                                 float* const* dweights, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                                 int32_t* state, float p_x, float p_h, const int64_t* seed_x, const int64_t* seed_e,
+                                 const int64_t* seed_h1, const int64_t* seed_h2, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Elementwise passes of FAFormer's SwiGLU MLP (fa_former_layer.py:241-289) and its 8-frame average (:61-120):
  *   faf_swiglu_dropout: out [R, H] = dropout_p(SiLU(pre[:, :H]) * pre[:, H:]),  pre [R, 2H];
  *   faf_dropout_mean:   out [R, C] = mean over the F consecutive rows r*F .. r*F+F-1 of dropout_p(x),  x [R*F, C].
