@@ -89,9 +89,11 @@ class HBatch:
         return out
 
     @classmethod
-    def empty_packed(cls, n_nodes: int, n_hyperedges: int, n_inc: int, n_graphs: int, pin: bool = False) -> "HBatch":
+    def empty_packed(cls, n_nodes: int, n_hyperedges: int, n_inc: int, n_graphs: int, pin: bool = False,
+                     device=None) -> "HBatch":
         """An uninitialised packed host batch of the given extents (one flat buffer, optionally pinned): the staging
-        buffer a loader thread collates into and the trainer's static inputs are refreshed from with ONE copy."""
+        buffer a loader thread collates into and the trainer's static inputs are refreshed from with ONE copy.
+        ``device``: the same layout in that device's memory (what a ``DeviceMolStore`` collates into)."""
         spec = (("x", (n_nodes, 9), torch.int64), ("pos", (n_nodes, 3), torch.float32),
                 ("edge_index0", (n_inc,), torch.int64), ("edge_index1", (n_inc,), torch.int64),
                 ("edge_attr", (n_hyperedges, 1), torch.int64), ("n_e", (n_graphs,), torch.int64),
@@ -102,8 +104,8 @@ class HBatch:
             layout.append((name, total, tuple(shape), dtype))
             nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
             total += (nbytes + 255) // 256 * 256
-        flat = torch.empty(max(total, 256), dtype=torch.uint8)
-        if pin:
+        flat = torch.empty(max(total, 256), dtype=torch.uint8, device=device)
+        if pin and device is None:
             flat = flat.pin_memory()
         proto = cls(**{name: torch.empty(0) for name, _, _ in spec}, num_nodes=n_nodes, num_hyperedges=n_hyperedges,
                     num_graphs=n_graphs)
@@ -235,6 +237,11 @@ class MolStore:
     def empty_staging(self, tgt, n_graphs: int, pin: bool = False) -> "HBatch":
         """An empty packed staging batch of extents ``tgt`` for ``collate(out=...)``."""
         return HBatch.empty_packed(tgt[0], tgt[1], tgt[2], n_graphs, pin=pin)
+
+    def to_device(self, device) -> "DeviceMolStore":
+        """The store in ``device``'s memory: uploaded once, batches assembled there by two kernel launches
+        (``DeviceMolStore``).  A CPU device raises ``HipLibraryError``: there is no fallback."""
+        return DeviceMolStore(self, device)
 
     @staticmethod
     def _ranges(starts, counts):
@@ -553,15 +560,17 @@ class GBatch:
         return out
 
     @classmethod
-    def empty_packed(cls, n_nodes: int, n_edges: int, n_bond_features: int, n_graphs: int, pin: bool = False) -> "GBatch":
+    def empty_packed(cls, n_nodes: int, n_edges: int, n_bond_features: int, n_graphs: int, pin: bool = False,
+                     device=None) -> "GBatch":
         """An uninitialised packed host batch of the given extents (one flat buffer, optionally pinned): the staging buffer
-        a loader thread collates into (``GraphStore.collate(out=...)``)."""
+        a loader thread collates into (``GraphStore.collate(out=...)``).  ``device``: the same layout in that device's
+        memory (what a ``DeviceGraphStore`` collates into)."""
         spec = (("x", (n_nodes, 9), torch.int64), ("edge_index", (2, n_edges), torch.int64),
                 ("edge_attr", (n_edges, n_bond_features), torch.int64), ("batch", (n_nodes,), torch.int64),
                 ("y", (n_graphs,), torch.float32))
         layout, total = cls._plan(spec)
-        flat = torch.empty(total, dtype=torch.uint8)
-        if pin:
+        flat = torch.empty(total, dtype=torch.uint8, device=device)
+        if pin and device is None:
             flat = flat.pin_memory()
         proto = cls(**{name: torch.empty(0) for name, _, _ in spec}, num_nodes=n_nodes, num_edges=n_edges, num_graphs=n_graphs)
         return proto._from_flat(flat, layout)
@@ -679,6 +688,10 @@ class GraphStore:
     def empty_staging(self, tgt, n_graphs: int, pin: bool = False) -> "GBatch":
         return GBatch.empty_packed(tgt[0], tgt[1], self.F, n_graphs, pin=pin)
 
+    def to_device(self, device) -> "DeviceGraphStore":
+        """The store in ``device``'s memory (``DeviceGraphStore``).  A CPU device raises ``HipLibraryError``."""
+        return DeviceGraphStore(self, device)
+
     def collate(self, idx, pad_to: Optional[tuple] = None, out: Optional["GBatch"] = None) -> "GBatch":
         """The batch of molecules ``idx`` (what ``collate_graphs`` returns for them), optionally padded to the static
         extents ``pad_to`` = (atoms, edges) exactly as ``pad_graph_batch`` does, optionally written into the tensors of
@@ -754,6 +767,236 @@ class GraphStore:
             ptrs[name] = arr.ctypes.data if arr.size else None
         self._ptr_cache = (key, ptrs)
         return ptrs
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# device-resident stores: the dataset uploaded once, batches assembled by two kernel launches (csrc/collate_dev.hip)
+# ------------------------------------------------------------------------------------------------------------------
+class _DeviceStore:
+    """What ``DeviceMolStore`` and ``DeviceGraphStore`` share.  The store's arrays are device tensors of the host store's
+    dtypes (the offsets too: the kernels index the arrays by them); the per-molecule counts and offsets ALSO stay on the host
+    as numpy arrays, so ``extents`` / ``count_columns`` -- all ``fit.BucketedLoader.plan`` asks -- never touch the device.
+    ``collate`` enqueues ``hb_collate_dev`` / ``gb_collate_dev`` on the current stream: no allocation beyond the output (none
+    with ``out``), no synchronisation, no host read."""
+
+    _COLUMNS: tuple = ()     # ((count name, offset name), ...): one per extent of a batch
+    _ROWS: dict = {}         # array name -> the column whose offsets index its rows
+    _HOST = None             # the host store class (its bucket / ladder / SPARE rules are this one's)
+    _MIN_SPARE: tuple = ()   # rows a padded extent needs beyond the batch's own (hb_collate's "must exceed" rule)
+
+    def __init__(self, host, device):
+        from . import hip
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise hip.HipLibraryError(f"{type(host).__name__}.to_device({str(device)!r}): a device store lives in the memory "
+                                      "of an MI355X (HIP) device and is collated by its kernels; there is no CPU fallback")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        host._checked_pointers()                 # dtypes, widths and lengths against the offsets, once, before the upload
+        for _, off in self._COLUMNS:             # the kernels index the arrays by the offsets: they must not run backwards
+            arr = getattr(host, off)
+            if int(arr[0]) != 0 or (len(host) and int(np.diff(arr).min()) < 0):
+                raise ValueError(f"{type(host).__name__}.{off} must start at 0 and not decrease")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        self._seat_device(device, {c: np.ascontiguousarray(getattr(host, c)) for c, _ in self._COLUMNS},
+                          {n: up(getattr(host, n)) for n in (*self._ROWS, "y")})
+
+    def _seat_device(self, device, counts: dict, tensors: dict):
+        self.device = device
+        for (cname, oname) in self._COLUMNS:
+            c = counts[cname]
+            setattr(self, cname, c)
+            setattr(self, oname, np.concatenate(([0], np.cumsum(c))).astype(np.int64))
+        self._offsets = torch.from_numpy(np.stack([getattr(self, o) for _, o in self._COLUMNS])).to(device)
+        for name, t in tensors.items():
+            setattr(self, name, t)
+
+    def __len__(self) -> int:
+        return int(getattr(self, self._COLUMNS[0][0]).shape[0])
+
+    def extents(self, idx) -> tuple:
+        idx = np.asarray(idx, dtype=np.int64)
+        return tuple(int(getattr(self, c)[idx].sum()) for c, _ in self._COLUMNS)
+
+    def count_columns(self) -> tuple:
+        return tuple(getattr(self, c) for c, _ in self._COLUMNS)
+
+    def bucket(self, ext, quantum: int) -> tuple:
+        return self._HOST.bucket(ext, quantum)
+
+    def ladder_step(self, quantum: int) -> tuple:
+        return self._HOST.ladder_step(quantum)
+
+    @property
+    def SPARE(self) -> tuple:
+        return self._HOST.SPARE
+
+    def subset(self, idx):
+        """The device store of molecules ``idx`` (a train / valid / test split): the rows are chosen on the host from the
+        offsets and gathered on the device."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
+            raise IndexError("subset: molecule index outside the store")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.device)
+        rows = [up(MolStore._ranges(getattr(self, o)[idx], getattr(self, c)[idx])[0]) for c, o in self._COLUMNS]
+        st = type(self).__new__(type(self))
+        if hasattr(self, "F"):
+            st.F = self.F
+        tensors = {n: getattr(self, n).index_select(0, rows[col]) for n, col in self._ROWS.items()}
+        tensors["y"] = self.y.index_select(0, up(idx))
+        st._seat_device(self.device, {c: np.ascontiguousarray(getattr(self, c)[idx]) for c, _ in self._COLUMNS}, tensors)
+        torch.cuda.current_stream(self.device).synchronize()    # (a loader collates on a stream of its own: gathers done first)
+        return st
+
+    def _index(self, idx):
+        """(device int64 [B], host array or None) of a batch's molecule indices: a host array is range-checked and uploaded, a
+        device tensor is trusted (callers pass slices of a permutation the host built)."""
+        if torch.is_tensor(idx) and idx.is_cuda:
+            if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device:
+                raise ValueError(f"collate: a device index must be a contiguous int64 vector on {self.device}")
+            return idx, None
+        host = np.ascontiguousarray(idx.numpy() if torch.is_tensor(idx) else idx, dtype=np.int64).reshape(-1)
+        if host.shape[0] and (int(host.min()) < 0 or int(host.max()) >= len(self)):
+            raise IndexError("collate: molecule index outside the store")
+        return torch.from_numpy(host).to(self.device), host
+
+    def _extents_for(self, dev_idx, host_idx, pad_to, misfit: str):
+        """The output extents, from the HOST counts; ``pad_to`` that does not fit raises before any launch.  (A device
+        index with ``pad_to`` is trusted to fit -- the loader's plan chose the bucket from the same counts; the kernels
+        never write past the extents and report a misfit in ``out._counts[-1]``.  A device index without ``pad_to`` is
+        read back once: the only synchronising form, which no loader uses.)"""
+        if pad_to is not None and host_idx is None:
+            return tuple(int(v) for v in pad_to)
+        if host_idx is None:
+            host_idx = dev_idx.cpu().numpy()
+            if host_idx.shape[0] and (int(host_idx.min()) < 0 or int(host_idx.max()) >= len(self)):
+                raise IndexError("collate: molecule index outside the store")
+        tot = self.extents(host_idx)
+        if pad_to is None:
+            return tot
+        ext = tuple(int(v) for v in pad_to)
+        if len(ext) != len(tot) or any(p < t + s for p, t, s in zip(ext, tot, self._MIN_SPARE)):
+            raise ValueError(misfit)
+        return ext
+
+    def _scratch(self, out, n_graphs: int, query):
+        """The collate workspace and the counts word of an output batch, allocated once per batch object"""
+        need = int(query(n_graphs))
+        ws = getattr(out, "_collate_ws", None)
+        if ws is None or ws.numel() < need or ws.device != self.device:
+            out._collate_ws = ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            out._counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+        return ws, out._counts
+
+    def _bind_outputs(self, a, out, shapes: dict, floats: tuple):
+        for name, shp in shapes.items():
+            ten = getattr(out, name)
+            want = torch.float32 if name in floats else torch.int64
+            if (not torch.is_tensor(ten) or tuple(ten.shape) != shp or ten.dtype != want or not ten.is_contiguous()
+                    or ten.device != self.device):
+                raise ValueError(f"collate: out.{name} must be a contiguous {want} tensor of shape {shp} on {self.device}")
+            setattr(a, "out_" + name, ten.data_ptr() or None)
+
+
+class DeviceMolStore(_DeviceStore):
+    """``MolStore.to_device(device)``: the hypergraph dataset in device memory.  ``collate`` writes the bytes
+    ``MolStore.collate`` writes for the same ``idx`` and ``pad_to`` (tests/test_hip_device_collate.py: bit for bit), by the two
+    launches of ``hb_collate_dev``; ``fit.BucketedLoader`` takes it in place of the host store and then runs without a
+    producer thread, pinned staging or a per-batch host-to-device copy."""
+
+    _COLUMNS = (("n_nodes", "node_off"), ("n_he", "he_off"), ("n_inc", "inc_off"))
+    _ROWS = {"x": 0, "pos": 0, "v": 2, "e": 2, "edge_attr": 1, "e_order": 1}
+    _HOST = MolStore
+    _MIN_SPARE = (1, 1, 0)  # nodes and hyperedges strictly (the padding molecule's own), incidences may fill their extent
+
+    def empty_staging(self, tgt, n_graphs: int, pin: bool = False) -> "HBatch":
+        """An empty packed DEVICE batch of extents ``tgt`` for ``collate(out=...)`` (``pin`` has no meaning here)."""
+        out = HBatch.empty_packed(tgt[0], tgt[1], tgt[2], n_graphs, device=self.device)
+        from . import hip
+        self._scratch(out, n_graphs, hip.lib().hb_collate_dev_workspace_bytes)
+        return out
+
+    def collate(self, idx, pad_to: Optional[tuple] = None, out: Optional["HBatch"] = None) -> "HBatch":
+        from . import hip
+        dev_idx, host_idx = self._index(idx)
+        B = int(dev_idx.shape[0])
+        PN, PM, PZ = self._extents_for(dev_idx, host_idx, pad_to,
+                                       "collate: pad_to must exceed the batch (nodes and hyperedges strictly)")
+        PB = B + (0 if pad_to is None else 1)
+        if out is None:
+            t = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+            out = HBatch(x=t((PN, 9), torch.int64), pos=t((PN, 3), torch.float32), edge_index0=t((PZ,), torch.int64),
+                         edge_index1=t((PZ,), torch.int64), edge_attr=t((PM, 1), torch.int64), n_e=t((PB,), torch.int64),
+                         e_order=t((PM,), torch.int64), batch=t((PN,), torch.int64), y=t((PB,), torch.float32))
+        a = hip.HbCollateDev()
+        self._bind_outputs(a, out, dict(x=(PN, 9), pos=(PN, 3), edge_index0=(PZ,), edge_index1=(PZ,), edge_attr=(PM, 1),
+                                        n_e=(PB,), e_order=(PM,), batch=(PN,), y=(PB,)), ("pos", "y"))
+        ws, counts = self._scratch(out, PB, hip.lib().hb_collate_dev_workspace_bytes)
+        a.B, a.n_mols, a.idx = B, len(self), dev_idx.data_ptr() or None
+        off = self._offsets
+        a.node_off, a.he_off, a.inc_off = (off[k].data_ptr() for k in range(3))
+        for name in self._ROWS:
+            setattr(a, name, getattr(self, name).data_ptr() or None)
+        a.y = self.y.data_ptr() or None
+        a.PN, a.PM, a.PZ, a.padded = PN, PM, PZ, 0 if pad_to is None else 1
+        a.out_counts, a.workspace, a.workspace_bytes = counts.data_ptr(), ws.data_ptr(), ws.numel()
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            hip.check(hip.lib().hb_collate_dev(ctypes.byref(a), stream), "hb_collate_dev")
+        out._collate_idx = dev_idx          # (keeps an uploaded index alive until the batch is collated into again)
+        if pad_to is not None:
+            out.num_real_graphs = B
+        out.num_nodes, out.num_hyperedges, out.num_graphs = PN, PM, PB
+        return out
+
+
+class DeviceGraphStore(_DeviceStore):
+    """``GraphStore.to_device(device)``: the 2-D graph dataset in device memory, collated by ``gb_collate_dev`` into the bytes
+    ``GraphStore.collate`` writes."""
+
+    _COLUMNS = (("n_nodes", "node_off"), ("n_edges", "edge_off"))
+    _ROWS = {"x": 0, "src": 1, "dst": 1, "edge_attr": 1}
+    _HOST = GraphStore
+    _MIN_SPARE = (1, 0)     # atoms strictly, edges may fill their extent
+
+    def __init__(self, host, device):
+        self.F = int(host.F)
+        super().__init__(host, device)
+
+    def empty_staging(self, tgt, n_graphs: int, pin: bool = False) -> "GBatch":
+        out = GBatch.empty_packed(tgt[0], tgt[1], self.F, n_graphs, device=self.device)
+        from . import hip
+        self._scratch(out, n_graphs, hip.lib().gb_collate_dev_workspace_bytes)
+        return out
+
+    def collate(self, idx, pad_to: Optional[tuple] = None, out: Optional["GBatch"] = None) -> "GBatch":
+        from . import hip
+        dev_idx, host_idx = self._index(idx)
+        B, F = int(dev_idx.shape[0]), self.F
+        PN, PE = self._extents_for(dev_idx, host_idx, pad_to, "collate: pad_to must exceed the batch (atoms strictly)")
+        PB = B + (0 if pad_to is None else 1)
+        if out is None:
+            t = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+            out = GBatch(x=t((PN, 9), torch.int64), edge_index=t((2, PE), torch.int64), edge_attr=t((PE, F), torch.int64),
+                         batch=t((PN,), torch.int64), y=t((PB,), torch.float32))
+        a = hip.GbCollateDev()
+        self._bind_outputs(a, out, dict(x=(PN, 9), edge_index=(2, PE), edge_attr=(PE, F), batch=(PN,), y=(PB,)), ("y",))
+        ws, counts = self._scratch(out, PB, hip.lib().gb_collate_dev_workspace_bytes)
+        a.B, a.n_mols, a.idx = B, len(self), dev_idx.data_ptr() or None
+        a.node_off, a.edge_off = (self._offsets[k].data_ptr() for k in range(2))
+        for name in self._ROWS:
+            setattr(a, name, getattr(self, name).data_ptr() or None)
+        a.y = self.y.data_ptr() or None
+        a.F, a.PN, a.PE, a.padded = F, PN, PE, 0 if pad_to is None else 1
+        a.out_counts, a.workspace, a.workspace_bytes = counts.data_ptr(), ws.data_ptr(), ws.numel()
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            hip.check(hip.lib().gb_collate_dev(ctypes.byref(a), stream), "gb_collate_dev")
+        out._collate_idx = dev_idx
+        if pad_to is not None:
+            out.num_real_graphs = B
+        out.num_nodes, out.num_edges, out.num_graphs = PN, PE, PB
+        return out
 
 
 def graph_bucket_sizes(n_nodes: int, n_edges: int, quantum: int = 128):

@@ -175,11 +175,26 @@ class BucketedLoader:
     extents: atoms and edges).  The store answers everything that differs -- ``count_columns``, ``bucket``,
     ``ladder_step``, ``SPARE``, ``empty_staging`` -- and the rest is one code path.
 
+    A store in device memory (``store.to_device(device)``: ``batch.DeviceMolStore`` / ``DeviceGraphStore``) plans the same
+    batches and buckets and is collated where it lives, by kernels on the loader's side stream: no prefetch thread, no pinned
+    staging, no per-batch host-to-device copy (``_iter_device``).  ``device`` then defaults to the store's.
+
     The reference does this with torch_geometric's DataLoader (main.py:227-229): a per-molecule Python collate on
     the training process's own thread."""
 
     def __init__(self, store, batch_size: int, shuffle: bool, seed: int = 0, device=None, rank: int = 0,
                  world: int = 1, quantum: int = 64, prefetch: int = 3, pin: Optional[bool] = None, levels: int = 1):
+        # a device-resident store (batch.DeviceMolStore / DeviceGraphStore) is collated where it lives, by kernels on the
+        # loader's side stream: no producer thread, no pinned staging, no per-batch host-to-device copy (see _iter_device)
+        self._device_store = getattr(store, "device", None) is not None
+        if self._device_store:
+            want = torch.device(store.device)
+            given = want if device is None else torch.device(device)
+            if given.type == "cuda" and given.index is None:
+                given = torch.device("cuda", torch.cuda.current_device())
+            if given != want:
+                raise ValueError(f"BucketedLoader: the store lives on {want}, the loader was asked for {given}")
+            device = want
         self.store, self.bs, self.shuffle, self.seed = store, batch_size, shuffle, seed
         self.device, self.rank, self.world, self.quantum, self.prefetch = device, rank, world, quantum, prefetch
         self.pin = (device is not None and torch.device(device).type == "cuda") if pin is None else pin
@@ -362,7 +377,79 @@ class BucketedLoader:
                     else:
                         setattr(self, name, val)
 
+    def _iter_device(self):
+        """One epoch from a device-resident store.  The epoch's permutation goes to the device in ONE copy; each batch's
+        collate (two launches, batch.Device*Store.collate) is enqueued ``prefetch`` batches ahead on the side stream, into
+        the ring of prefetch + 4 device batches per (extents, molecules) shape that the host path keeps too.  Ring entry:
+        [batch, collated (event on the side stream), consumed (event on the consumer's stream)].  The same ``older`` /
+        ``prev`` discipline as ``__iter__`` says when the consumer is done with an entry: the side stream waits for that
+        event before it refills it.  A batch is yielded only once its collate event has fired (queried on the host, waited
+        for on the host only if it has not), so it is complete in device memory for EVERY stream -- the trainer's look-ahead
+        reads it on a stream of its own."""
+        import time
+        batches, tgts = self.plan()
+        dev = self.device
+        side = self._side = getattr(self, "_side", None) or torch.cuda.Stream(dev)
+        with torch.cuda.stream(side):
+            flat = np.concatenate(batches) if batches else np.zeros(0, np.int64)
+            perm = torch.from_numpy(np.ascontiguousarray(flat, dtype=np.int64)).to(dev)
+        first = np.concatenate(([0], np.cumsum([len(b) for b in batches]))).astype(np.int64)
+        ring, depth = self._ring, self.prefetch + 4
+
+        def enqueue(i):
+            b, tgt = batches[i], tgts[i]
+            slot = ring.setdefault((tgt, len(b)), {"bufs": [], "next": 0})
+            t0 = time.perf_counter()
+            with torch.cuda.stream(side):
+                if len(slot["bufs"]) < depth:
+                    ent = [self.store.empty_staging(tgt, len(b) + 1), torch.cuda.Event(), torch.cuda.Event()]
+                    slot["bufs"].append(ent)
+                else:
+                    ent = slot["bufs"][slot["next"] % depth]
+                    slot["next"] += 1
+                    if not ent[2].query():      # (its last hand-out was four batches before this refill: almost always fired)
+                        side.wait_event(ent[2])
+                self.store.collate(perm[int(first[i]):int(first[i + 1])], pad_to=tgt, out=ent[0])
+                ent[1].record(side)
+            self.collate_seconds += time.perf_counter() - t0
+            self.collated += len(b)
+            return ent
+
+        def fresh(b):       # as in __iter__: a refilled batch object must not carry the index of its previous contents
+            b._hyper_index = None
+            b._graph_index = None
+            b._generation = getattr(b, "_generation", 0) + 1
+            return b
+
+        ahead, issued = [], 0
+        prev = older = None
+        try:
+            for i in range(len(batches)):
+                # (a consumer with one batch of look-ahead has by now enqueued the step on the batch handed out TWO yields ago)
+                if older is not None:
+                    older[2].record(torch.cuda.current_stream(dev))
+                older = prev
+                while issued < min(len(batches), i + 1 + self.prefetch):
+                    ahead.append(enqueue(issued))
+                    issued += 1
+                ent = ahead[i]
+                if not ent[1].query():
+                    ent[1].synchronize()
+                prev = ent
+                yield fresh(ent[0])
+            if older is not None:
+                older[2].record(torch.cuda.current_stream(dev))
+            older = None
+        finally:
+            # also reached when the consumer abandons the epoch: what it last held may still be read by kernels it enqueued
+            for e_ in (older, prev):
+                if e_ is not None:
+                    e_[2].record(torch.cuda.current_stream(dev))
+
     def __iter__(self):
+        if self._device_store:
+            yield from self._iter_device()
+            return
         pend, self._pending = getattr(self, "_pending", None), None
         ep = pend if pend is not None else self._start_epoch()
         q, th, stop, cuda = ep["q"], ep["th"], ep["stop"], ep["cuda"]

@@ -437,6 +437,65 @@ typedef struct {
 } GbCollate;
 int gb_collate(const GbCollate* args);
 
+/* hb_collate / gb_collate for a store that lives in DEVICE memory (batch.DeviceMolStore / DeviceGraphStore): the same fields,
+ * every array pointer a device pointer -- idx [B] included, in practice a slice of the epoch's permutation, uploaded once -- and
+ * the same bytes in every output field.  B, n_mols, the extents, F and padded stay host scalars; padded == 0: the caller passes
+ * the batch's own N, M, Z (N, E) as PN, PM, PZ (PN, PE).  Two launches on `stream`, capturable (no allocation, no
+ * synchronisation, no host read, no atomics: the same bytes on every run):
+ *   1. scan: ONE workgroup walks the B molecules in chunks and writes, per molecule, the exclusive prefix of its node,
+ *      hyperedge and incidence (atom and edge) counts and the first source row of each into `workspace`, and
+ *      out_counts[4] = N, M, Z, status (graphs: N, E, status, 0).  status bit 0: an idx entry outside [0, n_mols), which counts
+ *      as an empty molecule (y = 0); bit 1: the extents do not fit (padded: PN <= N, PM <= M, PZ < Z; graphs PN <= N, PE < E;
+ *      unpadded: an extent differs from its total).
+ *   2. fill: one work item per output element (x, pos, batch), incidence, hyperedge row and molecule; each finds its molecule
+ *      by binary search in the prefix and copies / offsets its source element or writes its padding value.  EVERY element of
+ *      every output field is written (rows past the real ones as padding), none past PN / PM / PZ / PB whatever status says.
+ * The offsets must start at 0, not decrease and end at the arrays' lengths (the Python stores check this once, before the
+ * upload): the kernels index the store by them.
+ * Before any launch: EQH_ERR_ARG for a NULL block, B / n_mols / an extent / F < 0, NULL out_counts, NULL idx, offsets or y
+ * with B > 0, a NULL output whose extent is positive, a NULL workspace or workspace_bytes below *_workspace_bytes(B);
+ * EQH_ERR_RANGE for padded != 0 with PN < 1 or (hypergraphs) PM < 1, which cannot hold even an empty batch.  B == 0 is legal
+ * and writes only padding. */
+typedef struct {
+    int64_t B, n_mols;
+    const int64_t* idx;
+    const int64_t *node_off, *he_off, *inc_off;
+    const int64_t* x;
+    const float* pos;
+    const int64_t *v, *e, *edge_attr, *e_order;
+    const float* y;
+    int64_t PN, PM, PZ;
+    int32_t padded;
+    int64_t* out_x;
+    float* out_pos;
+    int64_t *out_edge_index0, *out_edge_index1, *out_edge_attr, *out_n_e, *out_e_order, *out_batch;
+    float* out_y;
+    int64_t* out_counts;
+    void* workspace;
+    int64_t workspace_bytes;
+} HbCollateDev;
+int hb_collate_dev(const HbCollateDev* args, void* stream);
+int64_t hb_collate_dev_workspace_bytes(int64_t B);
+
+typedef struct {
+    int64_t B, n_mols;
+    const int64_t* idx;
+    const int64_t *node_off, *edge_off;
+    const int64_t* x;
+    const int64_t *src, *dst, *edge_attr;
+    int64_t F;
+    const float* y;
+    int64_t PN, PE;
+    int32_t padded;
+    int64_t *out_x, *out_edge_index, *out_edge_attr, *out_batch;
+    float* out_y;
+    int64_t* out_counts;
+    void* workspace;
+    int64_t workspace_bytes;
+} GbCollateDev;
+int gb_collate_dev(const GbCollateDev* args, void* stream);
+int64_t gb_collate_dev_workspace_bytes(int64_t B);
+
 /* Measurement aid (bench.py, not used by the models): eqh_stamp stores the device's constant-rate wall clock into
  * *slot (uint64, device memory) from a one-thread kernel on `stream` -- capturable, so two stamps around a launch
  * time it INSIDE a replayed hipGraph; eqh_wall_clock_khz is that clock's rate. */
