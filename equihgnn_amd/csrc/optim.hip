@@ -13,6 +13,10 @@
 //   the update (k_adam<true>) sums them in a fixed order in front of its bias corrections -- the kernel boundary is the
 //   ordering between the two stages, no ticket, no fence, no atomics -- and folds min(1, max_norm / (norm + 1e-6)) into
 //   the gradient scale.  Workgroup 0 keeps a 4-float readout {norm, coef, running max of norm, steps with coef < 1}.
+// eqh_adam_step_ema / eqh_adam_step_clip_ema: the same launch keeping an exponential moving average of the parameters
+//   (k_adam<CLIP, true>): the average is a fifth stream of the pass, requested with p, g, m, v, updated in registers from the
+//   new p and stored with them -- e += (1 - d_t) (p - e), a copy at the first update; d_t from the step counter the kernel
+//   reads anyway.  eqh_swap_f32 exchanges two flat buffers in place (live parameters <-> their average around an evaluation).
 // eqh_copy_many: up to 64 small device-to-device copies in one launch (gradients that autograd allocated,
 //   packed into the flat gradient buffer).
 #include "common.h"
@@ -77,11 +81,22 @@ template <> struct ClipArgs<true> {
     int n_partials;
 };
 
-template <bool CLIP>
+// What stands where k_adam's `int64_t zero_also_n` stood, at the end of the argument block: for EMA = false that count alone
+// (the kernels without an average keep their argument blocks), for EMA = true the average's arguments behind it.
+template <bool EMA> struct EmaArgs { int64_t zero_also_n; };
+template <> struct EmaArgs<true> {
+    int64_t zero_also_n;
+    float* ema;               // n floats beside p: the moving average, updated in place
+    float decay;              // d in [0, 1)
+    int warmup;               // != 0: d_t = min(d, (1 + t) / (10 + t))
+};
+
+template <bool CLIP, bool EMA>
 __global__ void __launch_bounds__(256)
 k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
        const float* __restrict__ lr_ptr, float beta1, float beta2, float eps, float wd, ClipArgs<CLIP> ca,
-       AdamState* __restrict__ st, int zero_grad, float* __restrict__ zero_also, int64_t zero_also_n) {
+       AdamState* __restrict__ st, int zero_grad, float* __restrict__ zero_also, EmaArgs<EMA> ea) {
+    const int64_t zero_also_n = ea.zero_also_n;
     // AD_U quads per thread and pass, all sixteen 16-byte loads of a pass requested before anything else -- before the bias
     // corrections are worked out, too (the step counter's load, two powf and a barrier otherwise sit in front of every memory
     // request).  Round 6: one quad per thread on 1340 workgroups moved 44 MB in 23 us (1.9 TB/s, four loads in flight per
@@ -91,6 +106,9 @@ k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, floa
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * AD_U;
     int64_t i0 = (int64_t)blockIdx.x * blockDim.x * AD_U + threadIdx.x;
     float4 pp[AD_U], gg[AD_U], mm[AD_U], vv[AD_U];
+    float4 ee[EMA ? AD_U : 1];   // EMA: a fifth stream, the average (twenty loads of a pass in flight)
+    float* __restrict__ e = nullptr;
+    if constexpr (EMA) e = ea.ema;
     auto load = [&](int64_t base) {
 #pragma unroll
         for (int u = 0; u < AD_U; ++u) {
@@ -100,16 +118,29 @@ k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, floa
                 gg[u] = reinterpret_cast<const float4*>(g)[i];
                 mm[u] = reinterpret_cast<float4*>(m)[i];
                 vv[u] = reinterpret_cast<float4*>(v)[i];
+                if constexpr (EMA) ee[u] = reinterpret_cast<float4*>(e)[i];
             }
         }
     };
     load(i0);
     // the bias corrections once per workgroup (two powf per THREAD were most of the kernel's instructions)
-    __shared__ float s_corr[CLIP ? 3 : 2];
+    constexpr int EMA_AT = CLIP ? 3 : 2;
+    __shared__ float s_corr[EMA_AT + (EMA ? 2 : 0)];
     if (threadIdx.x == 0) {
         const float t = (float)(st->step + 1);
         s_corr[0] = *lr_ptr / (1.0f - powf(beta1, t));
         s_corr[1] = sqrtf(1.0f - powf(beta2, t));
+        if constexpr (EMA) {
+            // the average's weight 1 - d_t of update t = step + 1, formed in double and rounded once; t == 1 copies
+            const int64_t ti = st->step + 1;
+            double d = (double)ea.decay;
+            if (ea.warmup) {
+                const double dw = (double)(1 + ti) / (double)(10 + ti);
+                d = dw < d ? dw : d;
+            }
+            s_corr[EMA_AT] = (float)(1.0 - d);
+            s_corr[EMA_AT + 1] = ti == 1 ? 1.0f : 0.0f;
+        }
     }
     if constexpr (CLIP) {
         // the second stage of the norm, by the first wavefront of EVERY workgroup in one fixed order (so all of them scale
@@ -141,6 +172,12 @@ k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, floa
     const float bc2_sqrt = s_corr[1];
     float gscale = ca.gscale;
     if constexpr (CLIP) gscale = s_corr[2];
+    float ema_w = 0.f;
+    bool ema_first = false;
+    if constexpr (EMA) {
+        ema_w = s_corr[EMA_AT];
+        ema_first = s_corr[EMA_AT + 1] != 0.f;
+    }
     for (; i0 < n4; i0 += stride) {
 #pragma unroll
         for (int u = 0; u < AD_U; ++u) {
@@ -155,10 +192,15 @@ k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, floa
                 ve[c] = beta2 * ve[c] + (1.0f - beta2) * gr * gr;
                 const float denom = sqrtf(ve[c]) / bc2_sqrt + eps;
                 pe[c] -= step_size * (me[c] / denom);
+                if constexpr (EMA) {    // from the NEW p: subtract, scale, add (three roundings); the first update is a copy
+                    float* ae = &ee[u].x;
+                    ae[c] = ema_first ? pe[c] : ae[c] + ema_w * (pe[c] - ae[c]);
+                }
             }
             reinterpret_cast<float4*>(p)[i] = pp[u];
             reinterpret_cast<float4*>(m)[i] = mm[u];
             reinterpret_cast<float4*>(v)[i] = vv[u];
+            if constexpr (EMA) reinterpret_cast<float4*>(e)[i] = ee[u];
             if (zero_grad) reinterpret_cast<float4*>(g)[i] = f4_zero();   // the next step's kernels accumulate into zeros
         }
         if (i0 + stride < n4) load(i0 + stride);
@@ -174,7 +216,9 @@ k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, floa
             const float vi = beta2 * v[i] + (1.0f - beta2) * gr * gr;
             m[i] = mi;
             v[i] = vi;
-            p[i] -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+            const float pi = p[i] - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+            p[i] = pi;
+            if constexpr (EMA) e[i] = ema_first ? pi : e[i] + ema_w * (pi - e[i]);
             if (zero_grad) g[i] = 0.f;
         }
     }
@@ -185,6 +229,40 @@ k_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, floa
         if (ticket == gridDim.x - 1) {
             st->step += 1;
             st->ticket = 0;
+        }
+    }
+}
+
+// eqh_swap_f32: SW_U quads of each buffer per thread and trip, all loads of a trip requested before the first store; at most
+// SWAP_GRID workgroups, workgroup 0 takes the ragged tail.  The two buffers do not overlap (checked on the host).
+constexpr int SW_U = 4;
+constexpr int SWAP_GRID = 2048;
+
+__global__ void __launch_bounds__(256) k_swap(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    const int64_t n4 = n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x * SW_U;
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x * SW_U + threadIdx.x; i0 < n4; i0 += stride) {
+        float4 aa[SW_U], bb[SW_U];
+#pragma unroll
+        for (int u = 0; u < SW_U; ++u) {
+            const int64_t i = i0 + (int64_t)u * blockDim.x;
+            aa[u] = i < n4 ? reinterpret_cast<const float4*>(a)[i] : f4_zero();
+            bb[u] = i < n4 ? reinterpret_cast<const float4*>(b)[i] : f4_zero();
+        }
+#pragma unroll
+        for (int u = 0; u < SW_U; ++u) {
+            const int64_t i = i0 + (int64_t)u * blockDim.x;
+            if (i < n4) {
+                reinterpret_cast<float4*>(a)[i] = bb[u];
+                reinterpret_cast<float4*>(b)[i] = aa[u];
+            }
+        }
+    }
+    if (blockIdx.x == 0) {  // ragged tail (n not a multiple of 4)
+        for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += blockDim.x) {
+            const float x = a[i];
+            a[i] = b[i];
+            b[i] = x;
         }
     }
 }
@@ -241,17 +319,25 @@ extern "C" int eqh_mse_fwd_bwd(const float* pred, const float* target, int32_t n
     return EQH_OK;
 }
 
-// eqh_adam_step (CLIP = false) and eqh_adam_step_clip (CLIP = true): one set of argument checks, one launch
-template <bool CLIP>
+// eqh_adam_step (CLIP = false) and eqh_adam_step_clip (CLIP = true), each with its _ema twin (EMA = true): one set of
+// argument checks, one launch
+template <bool CLIP, bool EMA>
 static int adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr, float beta1,
                      float beta2, float eps, float weight_decay, ClipArgs<CLIP> ca, void* state, int32_t zero_grad,
-                     float* zero_also, int64_t zero_also_n, void* stream_) {
+                     float* zero_also, EmaArgs<EMA> ea, void* stream_) {
+    const int64_t zero_also_n = ea.zero_also_n;
     if (n < 0 || !lr || !state) return EQH_ERR_ARG;
     if constexpr (CLIP) {
         if (!ca.partials || !ca.readout || !(ca.max_norm > 0.f)) return EQH_ERR_ARG;
     }
+    if constexpr (EMA) {
+        if (!(ea.decay >= 0.f && ea.decay < 1.f)) return EQH_ERR_ARG;     // (a NaN decay fails both comparisons)
+    }
     if (n == 0) return EQH_OK;
     if (!param || !grad || !exp_avg || !exp_avg_sq) return EQH_ERR_ARG;
+    if constexpr (EMA) {
+        if (!ea.ema) return EQH_ERR_ARG;
+    }
     if (zero_also_n < 0 || (zero_also_n > 0 && !zero_also) || (zero_also_n & 3) || !eqh_aligned16(zero_also)) return EQH_ERR_ARG;
     if (!eqh_aligned16(param) || !eqh_aligned16(grad) || !eqh_aligned16(exp_avg) || !eqh_aligned16(exp_avg_sq) ||
         ((uintptr_t)state & 7))
@@ -259,9 +345,12 @@ static int adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_s
     if constexpr (CLIP) {
         if (((uintptr_t)ca.partials & 7) || !eqh_aligned16(ca.readout)) return EQH_ERR_ALIGN;
     }
-    hipLaunchKernelGGL(k_adam<CLIP>, dim3(eqh_grid_for(n / 16 + 1, 256, 2048)), dim3(256), 0, static_cast<hipStream_t>(stream_),
-                       param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, ca,
-                       static_cast<AdamState*>(state), (int)zero_grad, zero_also, zero_also_n);
+    if constexpr (EMA) {
+        if (!eqh_aligned16(ea.ema)) return EQH_ERR_ALIGN;
+    }
+    hipLaunchKernelGGL((k_adam<CLIP, EMA>), dim3(eqh_grid_for(n / 16 + 1, 256, 2048)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                       ca, static_cast<AdamState*>(state), (int)zero_grad, zero_also, ea);
     EQH_CHECK_LAUNCH();
     return EQH_OK;
 }
@@ -270,8 +359,17 @@ extern "C" int eqh_adam_step(float* param, float* grad, float* exp_avg, float* e
                              const float* lr, float beta1, float beta2, float eps, float weight_decay,
                              float grad_scale, void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n,
                              void* stream_) {
-    return adam_step<false>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
-                            ClipArgs<false>{grad_scale}, state, zero_grad, zero_also, zero_also_n, stream_);
+    return adam_step<false, false>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                                   ClipArgs<false>{grad_scale}, state, zero_grad, zero_also, EmaArgs<false>{zero_also_n}, stream_);
+}
+
+extern "C" int eqh_adam_step_ema(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                 const float* lr, float beta1, float beta2, float eps, float weight_decay,
+                                 float grad_scale, void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n,
+                                 float* ema, float decay, int32_t warmup, void* stream_) {
+    return adam_step<false, true>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                                  ClipArgs<false>{grad_scale}, state, zero_grad, zero_also,
+                                  EmaArgs<true>{zero_also_n, ema, decay, (int)warmup}, stream_);
 }
 
 extern "C" size_t eqh_grad_sumsq_workspace_bytes(int64_t n) {
@@ -292,9 +390,33 @@ extern "C" int eqh_adam_step_clip(float* param, float* grad, float* exp_avg, flo
                                   float grad_scale, void* state, int32_t zero_grad, float* zero_also,
                                   int64_t zero_also_n, const void* partials, float max_norm, float* readout,
                                   void* stream_) {
-    return adam_step<true>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
-                           ClipArgs<true>{grad_scale, max_norm, static_cast<const double*>(partials), readout, sumsq_grid(n)},
-                           state, zero_grad, zero_also, zero_also_n, stream_);
+    return adam_step<true, false>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                                  ClipArgs<true>{grad_scale, max_norm, static_cast<const double*>(partials), readout, sumsq_grid(n)},
+                                  state, zero_grad, zero_also, EmaArgs<false>{zero_also_n}, stream_);
+}
+
+extern "C" int eqh_adam_step_clip_ema(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                      const float* lr, float beta1, float beta2, float eps, float weight_decay,
+                                      float grad_scale, void* state, int32_t zero_grad, float* zero_also,
+                                      int64_t zero_also_n, const void* partials, float max_norm, float* readout,
+                                      float* ema, float decay, int32_t warmup, void* stream_) {
+    return adam_step<true, true>(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                                 ClipArgs<true>{grad_scale, max_norm, static_cast<const double*>(partials), readout, sumsq_grid(n)},
+                                 state, zero_grad, zero_also, EmaArgs<true>{zero_also_n, ema, decay, (int)warmup}, stream_);
+}
+
+// The in-place exchange of two buffers that do not overlap (the live parameters and their average, around an evaluation)
+extern "C" int eqh_swap_f32(float* a, float* b, int64_t n, void* stream_) {
+    if (n < 0) return EQH_ERR_ARG;
+    if (n == 0) return EQH_OK;
+    if (!a || !b) return EQH_ERR_ARG;
+    const uintptr_t lo = (uintptr_t)(a < b ? a : b), hi = (uintptr_t)(a < b ? b : a);
+    if ((hi - lo) / sizeof(float) < (uint64_t)n) return EQH_ERR_ARG;      // the same buffer, or two that overlap
+    if (!eqh_aligned16(a) || !eqh_aligned16(b)) return EQH_ERR_ALIGN;
+    hipLaunchKernelGGL(k_swap, dim3(eqh_grid_for(n / 16 + 1, 256, SWAP_GRID)), dim3(256), 0, static_cast<hipStream_t>(stream_),
+                       a, b, n);
+    EQH_CHECK_LAUNCH();
+    return EQH_OK;
 }
 
 extern "C" int eqh_copy_many(int32_t count, const float* const* src, float* const* dst, const int64_t* n,

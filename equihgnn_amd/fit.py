@@ -33,7 +33,7 @@ import weakref
 import atexit
 
 from .batch import HBatch, HMol, MolStore, bucket_sizes, collate, shard_indices, shard_permutation
-from .trainer import GraphedTrainStep, TrainStep, _world, with_next
+from .trainer import GraphedTrainStep, TrainStep, _checked_decay, _world, with_next
 
 
 # ------------------------------------------------------------------------------------------------
@@ -581,8 +581,15 @@ class Fitter:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  std: Optional[float] = None, patience_lr: int = 10, patience_stop: int = 50,
                  step_factory: Callable = TrainStep, metric_seed: int = 0, clip_gnorm: Optional[float] = None,
-                 device_metrics: bool = False):
-        """``clip_gnorm``: global-norm gradient clipping in the training step (the reference's ``--clip_gnorm``, which its
+                 device_metrics: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False):
+        """``ema_decay`` / ``ema_warmup``: the training step keeps an exponential moving average of the weights
+        (``TrainStep`` / ``GraphedTrainStep(ema_decay=..)``; handed to ``step_factory`` only when given, as ``clip_gnorm``),
+        and every evaluation -- the per-epoch validation and ``test`` -- runs inside ``step.averaged()``: the scheduler, early
+        stopping and ``best_val_mae`` follow the averaged weights, and ``best_state`` is the state dict taken inside that
+        context, i.e. averaged parameters with the LIVE buffers (BatchNorm statistics are not averaged).
+        ``test(best_state=..)`` loads it as ever and then evaluates WITHOUT a second averaging: the loaded weights already
+        are the average.
+        ``clip_gnorm``: global-norm gradient clipping in the training step (the reference's ``--clip_gnorm``, which its
         Trainer never receives: off by default).  Handed to ``step_factory`` only when given, so a factory without the
         keyword keeps working; each epoch's history row then carries ``grad_norm_max`` and ``clipped_steps``.
         ``device_metrics``: keep the epoch's loss sum, the bootstrap MAE / MSE sums and the test table in device memory and
@@ -592,9 +599,12 @@ class Fitter:
         this object has issued, with the option on or off."""
         self.model, self.lr, self.std = model, lr, std
         self.clip_gnorm = clip_gnorm
+        self.ema_decay = _checked_decay("Fitter", ema_decay)
         self.device_metrics = bool(device_metrics)
         self.host_reads = 0
         extra = {} if clip_gnorm is None else {"clip_gnorm": clip_gnorm}
+        if self.ema_decay is not None:
+            extra.update(ema_decay=self.ema_decay, ema_warmup=bool(ema_warmup))
         if self.device_metrics:
             if not all(p.is_cuda for p in model.parameters()) or next(model.parameters(), None) is None:
                 raise ValueError("Fitter(device_metrics=True) keeps its sums in device memory: the model must be on a GPU")
@@ -618,15 +628,25 @@ class Fitter:
         _drop_index(data)
         return self.model(data)
 
+    def _averaged(self):
+        """The context an evaluation runs in.  With ``ema_decay``: ``step.averaged()`` (once the step has its optimiser:
+        before the first update the average is the live weights); nothing when already inside it, or without a decay."""
+        if (self.ema_decay is not None and getattr(self.step, "opt", None) is not None
+                and not getattr(self.step, "_averaging", False)):
+            return self.step.averaged()
+        return contextlib.nullcontext()
+
     def _evaluate(self, loader) -> Dict[str, float]:
         self.model.eval()
         self.metrics.reset()
         scale = self.std if self.std else 1.0          # main.py:67-70: `if self.std:`
-        with torch.no_grad():
-            for data in loader:
-                out, y = _real(self._predict(data), data)
-                self._update_metrics(out, y, scale)
-        self.model.train()
+        try:
+            with self._averaged(), torch.no_grad():
+                for data in loader:
+                    out, y = _real(self._predict(data), data)
+                    self._update_metrics(out, y, scale)
+        finally:
+            self.model.train()
         return self._compute_metrics()
 
     def _update_metrics(self, out, y, scale):
@@ -678,7 +698,10 @@ class Fitter:
             if self.sched is None and self.step.opt is not None:  # built lazily with the optimiser
                 self.sched = torch.optim.lr_scheduler.ReduceLROnPlateau(
                     self.step.opt, mode="min", factor=0.1, patience=self.patience_lr, min_lr=self.lr * 1e-5)
-            val = self._evaluate(valid_loader)
+            with self._averaged():      # (ema_decay: the validation pass AND the checkpoint see the averaged weights)
+                val = self._evaluate(valid_loader)
+                better = val["mae_mean"] < res.best_val_mae
+                state = copy.deepcopy(self.model.state_dict()) if better else None
             lr_now = self.step.opt.param_groups[0]["lr"] if self.step.opt is not None else self.lr
             res.history.append({"epoch": epoch, "train_loss": tot / max(n, 1), "lr": float(lr_now),
                                 **{"val_" + k: v for k, v in val.items()}})
@@ -690,9 +713,9 @@ class Fitter:
                 res.history[-1].update(grad_norm_max=seen, clipped_steps=int(clipped))
             if self.sched is not None:
                 self.sched.step(val["mae_mean"])
-            if val["mae_mean"] < res.best_val_mae:     # ModelCheckpoint(save_top_k=1) + EarlyStopping
+            if better:                                 # ModelCheckpoint(save_top_k=1) + EarlyStopping
                 res.best_val_mae, res.best_epoch, bad = val["mae_mean"], epoch, 0
-                res.best_state = copy.deepcopy(self.model.state_dict())
+                res.best_state = state
             else:
                 bad += 1
                 if bad >= self.patience_stop:
@@ -702,7 +725,11 @@ class Fitter:
 
     def test(self, test_loader, best_state: Optional[dict] = None):
         """trainer.test(ckpt_path="best"): metrics plus the gathered (pred, truth) table that
-        main.py:122-132 logs as test_results.csv (unscaled, as there)."""
+        main.py:122-132 logs as test_results.csv (unscaled, as there).
+
+        With ``ema_decay`` and no ``best_state`` the pass runs inside ``step.averaged()``: it tests the averaged weights.  A
+        ``best_state`` of an ``ema_decay`` fit already holds averaged parameters (``Fitter.__init__``): it is loaded into the
+        live weights as ever and evaluated as it stands, without a second averaging."""
         if best_state is not None:
             self.model.load_state_dict(best_state)
         self.model.eval()
@@ -711,7 +738,7 @@ class Fitter:
         preds, truth = [], []
         table, filled = None, 0     # device_metrics: both columns in ONE device buffer [2, capacity], moved to the host once
         try:
-            with torch.no_grad():
+            with self._averaged() if best_state is None else contextlib.nullcontext(), torch.no_grad():
                 for data in test_loader:
                     out, y = _real(self._predict(data), data)
                     self._update_metrics(out, y, scale)

@@ -10,6 +10,7 @@ produces (the reference's dead branches, which is why main.py:281 needs
 """
 from __future__ import annotations
 
+import contextlib
 import inspect
 from typing import Callable, Optional
 
@@ -49,19 +50,90 @@ class FlatGradients:
             self.flat.mul_(1.0 / w)
 
 
-class TrainStep:
+def _checked_decay(who: str, decay) -> Optional[float]:
+    """``ema_decay`` as a float in [0, 1), or None (no average)."""
+    if decay is None:
+        return None
+    d = float(decay)
+    if not 0.0 <= d < 1.0:      # (a NaN fails both comparisons)
+        raise ValueError(f"{who}: ema_decay must lie in [0, 1) (got {decay})")
+    return d
+
+
+def ema_decay_at(decay: float, t: int, warmup: bool) -> float:
+    """d_t of update t = 1, 2, ..: ``decay``, or with ``warmup`` min(decay, (1 + t) / (10 + t)) (torch_ema / timm)."""
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
+class _Averaged:
+    """What TrainStep and GraphedTrainStep share of the weight average (``ema_decay``): ``averaged()`` and
+    ``ema_state_dict()``.  The step class says how the live and the averaged values change places (``_ema_exchange``, its own
+    inverse) and where each averaged parameter lies (``_ema_of``: id(parameter) -> tensor, live parameters only).  Only
+    parameters that receive a gradient are averaged (the others never change: they are their own average); buffers are not
+    (an evaluation on the average reads the live BatchNorm statistics)."""
+
+    ema_decay: Optional[float] = None
+    _averaging = False
+
+    def _ema_ready(self, what: str):
+        if self.ema_decay is None:
+            raise RuntimeError(f"{type(self).__name__}.{what}: built without ema_decay, there is no average")
+        if self.opt is None:
+            raise RuntimeError(f"{type(self).__name__}.{what}: no optimiser yet (the first step builds it and the average)")
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """``with step.averaged(): ...``: the model's parameters hold the averaged weights inside the block and the live ones
+        again behind it, bit for bit, also when the block raises.  An exchange in place: every address stays what it was, so
+        captured graphs (GraphedEvalStep) replay on the average without a re-capture.  No step() inside the block."""
+        self._ema_ready("averaged()")
+        if self._averaging:
+            raise RuntimeError(f"{type(self).__name__}.averaged(): already inside averaged()")
+        self._ema_exchange()
+        self._averaging = True
+        try:
+            yield self
+        finally:
+            self._averaging = False
+            self._ema_exchange()
+
+    @torch.no_grad()
+    def ema_state_dict(self) -> dict:
+        """``model.state_dict()`` with the averaged value of every averaged parameter, all entries clones; the live weights
+        are not touched.  (Inside ``averaged()`` the parameters themselves hold the average: the model's state is returned.)"""
+        self._ema_ready("ema_state_dict()")
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        if self._averaging:
+            return sd
+        ema = self._ema_of()
+        for name, p in self.model.named_parameters(remove_duplicate=False):
+            if id(p) in ema and name in sd:
+                sd[name] = ema[id(p)].detach().clone()
+        return sd
+
+
+class TrainStep(_Averaged):
     """``loss = step(data)``; ``data.y`` is the target.  Model-agnostic (the gloo tests drive it
     with the CPU oracle, the GPU path with the HIP models)."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, on_batch: Optional[Callable] = None,
-                 clip_gnorm: Optional[float] = None, loss_readout: bool = False):
+                 clip_gnorm: Optional[float] = None, loss_readout: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         """``clip_gnorm``: clip the rank-averaged gradient by its global L2 norm before the update
         (``torch.nn.utils.clip_grad_norm_``; the reference's ``--clip_gnorm``, main.py:175, which its Trainer never
         receives -- so the default, and the reference's behaviour, is off).  ``loss_readout``: keep {sum, count} of the
         steps' losses in ``loss_sum``, 2 doubles on the model's device (a GPU), added to by one launch behind every step's
-        backward; the reader zeroes it.  Off: nothing is allocated or launched."""
+        backward; the reader zeroes it.  Off: nothing is allocated or launched.
+        ``ema_decay`` / ``ema_warmup``: keep an exponential moving average of the live parameters in shadow tensors
+        (``ema_shadows``, laid out at the first step), updated behind ``opt.step()`` by ONE ``torch._foreach_lerp_`` -- update
+        t = 1 copies, from t = 2 on e += (1 - d_t) (p - e), d_t = ``ema_decay`` or, with ``ema_warmup``,
+        min(ema_decay, (1 + t) / (10 + t)).  ``averaged()`` exchanges the ``p.data`` of the live parameters with the shadows;
+        ``ema_state_dict()`` returns the averaged state.  ``None``: no shadows, the step of before."""
         self.model = model
+        self.ema_decay, self.ema_warmup = _checked_decay("TrainStep", ema_decay), bool(ema_warmup)
+        self.ema_shadows: Optional[list] = None         # one tensor per live parameter, in self.flat.params' order
+        self.ema_updates = 0                            # t of the last update of the average
         self.loss_readout = bool(loss_readout)
         self.loss_sum: Optional[torch.Tensor] = None    # {sum of the steps' losses, number of steps}, float64, on the device
         self.lr, self.wd = lr, weight_decay
@@ -87,9 +159,13 @@ class TrainStep:
             p.grad.copy_(g)
         fused = live[0].is_cuda
         self.opt = torch.optim.Adam(live, lr=self.lr, weight_decay=self.wd, fused=fused)
+        if self.ema_decay is not None:
+            self.ema_shadows = [p.detach().clone() for p in live]   # before the first update the average IS the live weights
         return loss
 
     def step(self, data) -> torch.Tensor:
+        if self._averaging:
+            raise RuntimeError("TrainStep.step(): inside averaged() the parameters hold the average, not the live weights")
         if self.on_batch is not None:
             self.on_batch(data)
         if self.flat is None:
@@ -104,7 +180,25 @@ class TrainStep:
         if self.clip_gnorm is not None:
             self._clip()
         self.opt.step()
+        if self.ema_decay is not None:
+            self._ema_update()
         return loss.detach()
+
+    @torch.no_grad()
+    def _ema_update(self):
+        self.ema_updates += 1
+        live = [p.data for p in self.flat.params]
+        if self.ema_updates == 1:
+            torch._foreach_copy_(self.ema_shadows, live)
+        else:
+            torch._foreach_lerp_(self.ema_shadows, live, 1.0 - ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup))
+
+    def _ema_exchange(self):
+        for i, p in enumerate(self.flat.params):
+            p.data, self.ema_shadows[i] = self.ema_shadows[i], p.data
+
+    def _ema_of(self):
+        return {id(p): e for p, e in zip(self.flat.params, self.ema_shadows)}
 
     @torch.no_grad()
     def _clip(self):
@@ -152,12 +246,21 @@ class FlatAdam(torch.optim.Optimizer):
     min(1, max / (norm + 1e-6)), updates).  The threshold is FIXED at construction: it is a kernel argument of a captured
     graph, which a replay does not read again.  ``grad_norm``: 4 floats on the device, {norm before clipping, coef, running
     maximum of the norm, number of steps with coef < 1}; the kernel keeps the last two running, the reader zeroes them.
-    ``None`` (default): one eqh_adam_step call, as before, and ``grad_norm`` is ``None``."""
+    ``None`` (default): one eqh_adam_step call, as before, and ``grad_norm`` is ``None``.
 
-    def __init__(self, param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+    ``ema_decay``: keep an exponential moving average of the parameter in ``state[param]["ema"]`` (a clone of the parameter
+    at construction, carried by ``state_dict()``), updated by the SAME launch: ``step()`` calls the ``_ema`` twin of the entry
+    it would have called (eqh_adam_step_ema / eqh_adam_step_clip_ema), which streams the average beside p, grad and the
+    moments.  Update t = 1 copies the parameter; from t = 2 on e += (1 - d_t) (p - e) with d_t = ``ema_decay``, or
+    min(``ema_decay``, (1 + t) / (10 + t)) with ``ema_warmup`` (the torch_ema / timm warm-up).  Decay and flag are FIXED at
+    construction, as the threshold is.  ``None`` (default): today's calls and no ``"ema"`` key."""
+
+    def __init__(self, param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=False):
         super().__init__([param], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"FlatAdam: max_grad_norm must be positive (got {max_grad_norm})")
+        self.ema_decay, self.ema_warmup = _checked_decay("FlatAdam", ema_decay), bool(ema_warmup)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.grad_norm = None
         self.grad_scale = 1.0
@@ -175,6 +278,8 @@ class FlatAdam(torch.optim.Optimizer):
             nbytes = hip.lib().eqh_grad_sumsq_workspace_bytes(param.numel())
             st["clip_partials"] = torch.empty(nbytes // 8, dtype=torch.float64, device=param.device)   # never cleared
             self.grad_norm = torch.zeros(4, dtype=torch.float32, device=param.device)
+        if self.ema_decay is not None:
+            st["ema"] = param.data.detach().clone()     # before the first update the average IS the live parameter
 
     def sync_lr(self):
         """Mirror param_groups[0]['lr'] (what schedulers write) into the device scalar; outside capture."""
@@ -197,13 +302,20 @@ class FlatAdam(torch.optim.Optimizer):
                 ops._ptr(st["lr"]), b1, b2, g["eps"], g["weight_decay"], self.grad_scale, ops._ptr(st["step_block"]),
                 1 if self.zero_grad_in_step else 0, ops._ptr(zs) if zs is not None else None,
                 zs.numel() if zs is not None else 0)
+        ema = () if self.ema_decay is None else (ops._ptr(st["ema"]), self.ema_decay, 1 if self.ema_warmup else 0)
         if self.max_grad_norm is None:
-            hip.check(hip.lib().eqh_adam_step(*args, stream), "eqh_adam_step")
+            if ema:
+                hip.check(hip.lib().eqh_adam_step_ema(*args, *ema, stream), "eqh_adam_step_ema")
+            else:
+                hip.check(hip.lib().eqh_adam_step(*args, stream), "eqh_adam_step")
             return
         partials = ops._ptr(st["clip_partials"])
         hip.check(hip.lib().eqh_grad_sumsq(ops._ptr(p.grad), p.numel(), partials, stream), "eqh_grad_sumsq")
-        hip.check(hip.lib().eqh_adam_step_clip(*args, partials, self.max_grad_norm, ops._ptr(self.grad_norm), stream),
-                  "eqh_adam_step_clip")
+        clip = (partials, self.max_grad_norm, ops._ptr(self.grad_norm))
+        if ema:
+            hip.check(hip.lib().eqh_adam_step_clip_ema(*args, *clip, *ema, stream), "eqh_adam_step_clip_ema")
+        else:
+            hip.check(hip.lib().eqh_adam_step_clip(*args, *clip, stream), "eqh_adam_step_clip")
 
 
 def with_next(batches):
@@ -224,7 +336,7 @@ class CollectiveCaptureRefused(RuntimeError):
     """The process-group backend could not record a collective into a hipGraph (raised by GraphedTrainStep._capture_pass)."""
 
 
-class GraphedTrainStep:
+class GraphedTrainStep(_Averaged):
     """TrainStep with the launch-bound part captured in hipGraphs.
 
     forward + MSE + backward (≈700 kernel launches for egnn_equihnns, including the per-batch index
@@ -248,8 +360,14 @@ class GraphedTrainStep:
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, collective: bool = True, keep_grads: bool = False,
                  force_collective: bool = False, graph_collective: bool = True, clip_gnorm: Optional[float] = None,
-                 loss_readout: bool = False):
-        """``loss_readout``: keep {sum, count} of the steps' losses in ``loss_sum`` (2 doubles on the device): behind every
+                 loss_readout: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False):
+        """``ema_decay`` / ``ema_warmup``: keep an exponential moving average of ``pflat`` (``FlatAdam(ema_decay=..)``: a fifth
+        stream of the update launch, no launch more in the step; every rank forms the same average from the same averaged
+        gradient, without a collective).  Fixed at construction (kernel arguments of the captured graphs).  ``averaged()``
+        then exchanges ``pflat`` and the average in place by ONE launch on the current stream (eqh_swap_f32) and exchanges
+        them back on leaving: the graphs of a ``GraphedEvalStep`` hold addresses, so they replay on the average as they are.
+        ``ema_state_dict()``: the model's state with the averaged parameters.  ``None``: nothing allocated, the calls of before.
+        ``loss_readout``: keep {sum, count} of the steps' losses in ``loss_sum`` (2 doubles on the device): behind every
         step -- the eager bootstrap step, a capture step, a calibration step, a replay -- ``step()`` issues one ordinary
         launch that adds the step's loss scalar to it (``ops.loss_accumulate``), stream-ordered behind the replay.  It is no
         node of the captured graphs: their launch lists, and what ``step()`` returns, are those of before.  Whoever reads
@@ -267,6 +385,7 @@ class GraphedTrainStep:
         capture the collective (always graph A -> eager all-reduce -> graph B)."""
         self.model, self.lr, self.wd = model, lr, weight_decay
         self.clip_gnorm = clip_gnorm
+        self.ema_decay, self.ema_warmup = _checked_decay("GraphedTrainStep", ema_decay), bool(ema_warmup)
         self.loss_readout = bool(loss_readout)
         self.loss_sum: Optional[torch.Tensor] = None    # {sum of the steps' losses, number of steps}, float64, on the device
         self.collective = collective
@@ -527,7 +646,8 @@ class GraphedTrainStep:
         self._buffer_restore(snap)             # discovery + probe passes were not steps
         loss = self._fwd_bwd(data)
         # Adam is elementwise: one update over the flat tensor equals the per-parameter updates
-        self.opt = FlatAdam(self.pflat, lr=self.lr, weight_decay=self.wd, max_grad_norm=self.clip_gnorm)
+        self.opt = FlatAdam(self.pflat, lr=self.lr, weight_decay=self.wd, max_grad_norm=self.clip_gnorm,
+                            ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
         self.opt.zero_grad_in_step = not self.keep_grads
         self.opt.zero_also = lambda: self.scratch.buf
         if self._multi():
@@ -760,6 +880,24 @@ class GraphedTrainStep:
                 "stream": stream, "free": free, "ready": None, "ready_ev": ready, "holds": None, "light": light}
 
     @property
+    def ema_flat(self) -> Optional[torch.Tensor]:
+        """With ``ema_decay``: the average of ``pflat``, same length and element order (the optimiser's ``state["ema"]``);
+        ``None`` without it or before the first step."""
+        return self.opt.state[self.pflat].get("ema") if self.opt is not None else None
+
+    def _ema_exchange(self):
+        from . import hip, ops
+        live, ema = self.pflat.data, self.ema_flat
+        hip.check(hip.lib().eqh_swap_f32(ops._ptr(live), ops._ptr(ema), live.numel(), ops._stream(live.device)), "eqh_swap_f32")
+
+    def _ema_of(self):
+        ema, base, out = self.ema_flat, self.pflat.data_ptr(), {}
+        for p in self.live:
+            off = (p.data_ptr() - base) // 4
+            out[id(p)] = ema[off:off + p.numel()].view_as(p)
+        return out
+
+    @property
     def grad_norm(self) -> Optional[torch.Tensor]:
         """With ``clip_gnorm``: the update kernel's readout, 4 floats on the device -- {norm of the averaged gradient before
         clipping, coef, running maximum of the norm, number of clipped steps}; zero the last two to restart them.  Reading
@@ -888,6 +1026,8 @@ class GraphedTrainStep:
         """One training step on ``data``.  ``next_data``: the batch of the NEXT call, if the caller has it (a loader with one
         batch of look-ahead, ``with_next``): its per-batch index is then built beside this step instead of at the head of
         the next one.  Numerically the two forms are the same step."""
+        if self._averaging:
+            raise RuntimeError("GraphedTrainStep.step(): inside averaged() pflat holds the average, not the live weights")
         if self.live is None:
             loss = self._bootstrap(data)
             if self.loss_readout:

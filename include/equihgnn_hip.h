@@ -65,6 +65,26 @@ int eqh_adam_step_clip(float* param, float* grad, float* exp_avg, float* exp_avg
                        const float* lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                        void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n,
                        const void* partials, float max_norm, float* readout, void* stream);
+/* The same two updates keeping an exponential moving average (EMA) of the parameters in the SAME launch: `ema`, n floats,
+ * 16-byte aligned, is read with p, grad and the moments and written with them.  With t = 1, 2, .. the number of the update
+ * (the state block's counter + 1) and p_t the parameters it leaves: e_1 = p_1 (a copy, whatever `ema` held), and for t >= 2
+ * e_t = e_{t-1} + (1 - d_t) (p_t - e_{t-1}) -- subtract, scale, add in fp32, the weight 1 - d_t formed in double once per
+ * workgroup -- with d_t = decay, or min(decay, (1 + t) / (10 + t)) when warmup != 0.  The update of p and the moments is bit
+ * for bit that of the entry without the average.  decay outside [0, 1) (NaN included) or `ema` null with n > 0: EQH_ERR_ARG;
+ * `ema` not 16-byte aligned: EQH_ERR_ALIGN; every check of the twin entry holds; n == 0: EQH_OK, nothing launched.
+ * eqh_swap_f32: exchanges the n floats at `a` with the n floats at `b` in place (the live parameters and their average,
+ * around an evaluation; calling it twice restores both).  Capturable.  a or b null with n > 0, n < 0, or two ranges that
+ * overlap (a == b included): EQH_ERR_ARG; a or b not 16-byte aligned: EQH_ERR_ALIGN; n == 0: EQH_OK, nothing launched. */
+int eqh_adam_step_ema(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                      const float* lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                      void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n,
+                      float* ema, float decay, int32_t warmup, void* stream);
+int eqh_adam_step_clip_ema(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                           const float* lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                           void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n,
+                           const void* partials, float max_norm, float* readout,
+                           float* ema, float decay, int32_t warmup, void* stream);
+int eqh_swap_f32(float* a, float* b, int64_t n, void* stream);
 /* Mean-squared-error loss of main.py:36,49-63 and its gradient in one launch: loss[0] = mean((pred - target)^2)
  * over n values, grad[i] = 2 (pred[i] - target[i]) / n.  n <= 65536 (one workgroup; a batch of molecules). */
 int eqh_mse_fwd_bwd(const float* pred, const float* target, int32_t n, float* loss, float* grad, void* stream);
