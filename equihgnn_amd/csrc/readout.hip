@@ -5,13 +5,16 @@
 //   y_b   = w3 . h2 + b3                                        equihnn_egnn.py:168-169 (.view(-1))
 //   loss  = mean_{b < n_real} (y_b - t_b)^2                     F.mse_loss, main.py:49-63
 //
-// At the BASELINE batch this head is 257 rows: as separate launches (pool, 3 GEMMs, 2 LayerNorms, loss, and
-// their ~14 backward kernels) it cost ~150 us of a 1.73 ms step for ~75 MFLOP of work; every one of those
-// launches sat at the in-graph floor.  Here one workgroup owns 16 molecules: it pools their atoms into LDS,
-// runs the three layers with fp32 MFMA (16 x 16 x 4, the 16 molecules are the M dimension), forms
-// dy = 2 (y - t) / n_real, walks back through the layers from the activations still in LDS, writes dX for its
-// atoms and one partial slab of every parameter gradient; the slabs are summed by the library's fixed-order
-// reducer (deferred into the step's batched reduction when that is active).  No atomics; bitwise reproducible.
+// The design, the MFMA operand convention, the dropout elements and the loss ticket are readout_head.h's, shared with the paired
+// tail's head (readout_pair.hip).  At the BASELINE batch this head is 257 rows: as separate launches (pool, 3 GEMMs, 2
+// LayerNorms, loss, and their ~14 backward kernels) it cost ~150 us of a 1.73 ms step for ~75 MFLOP of work; every one of those
+// launches sat at the in-graph floor.  This file's own phases:
+//
+//   pooling   wavefront w pools molecules 2w, 2w+1 side by side, eight rows deep, with clamped loads.
+//   products  every weight tile is requested a phase ahead of its use (wt_tile_load / w_cols_load, then *_mma): the kernel is a
+//             chain of short dependent phases on 17 workgroups, and every exposed memory latency is step time.
+//   LDS       X, dX and ten H buffers [16][H + 4]; dZ2 and dZ1 have buffers of their own.
+//   sums      [dbias | dgamma | dbeta] by one thread per (quantity, column).
 //
 // Round 6, measured with tools/readout_stamps.py (-DRH_STAMPS: s_memtime stamps of every phase): 26 us of the launch's 34 are
 // the chain of phases itself -- pooling 5.4 us (rowptr -> rows -> LDS: two dependent round trips to memory), the layer products
@@ -21,22 +24,10 @@
 // gradient slabs instead of 17 for the batched reduction (12.8 vs 9.4 us).  Dropped; in the graphed step the 17-workgroup launch
 // is where the NEXT batch's index build runs on the idle CUs (trainer.GraphedTrainStep, signal point "readout").
 //
-// MFMA operand convention (lane l: r = l & 15, q = l >> 4): A[m = r][k = q], B[k = q][n = r],
-// D[m = 4 q + g][n = r] in accumulator component g.  Four MFMAs share one float4 of K: the j-th of them
-// takes component j on both sides, i.e. k = 16 s + 4 q + j (a permutation of K, which a sum does not see).
-//
-// Training dropout (template flag DROP, entry hg_readout_mse_drop_f32): the same body with up to three sites, keep = 0 or
-// 1 / (1 - p) from the hash of (seed in device memory, element index) of drop_hash.h, nothing stored:
-//   pre-pool (p_x)   x_b[c] = sum_n keep(n C + c) X[n, c] in the pooling phase, dX[n, c] = keep(n C + c) dxpool[b, c]: the
-//                    element of faf_dropout_add on the [N, C] rows;
-//   hidden 1, 2 (p_h) h_i[b, c] = keep_i(b H + c) LN_i(relu(.)), b the global molecule row: the element of
-//                    hg_bias_relu_ln_drop_*.  LDS holds the masked h_i (dW2, dw3 and the next product read it as it is); the
-//                    backward masks dh ahead of the LayerNorm backward and leaves the masked dh in LDS, so dgamma and dbeta
-//                    are column sums of it.
-// The p = 0 instantiations keep their argument block (RhArgs<false> is the `float eps` it replaces) and their statements.
-#include "common.h"
-#include "drop_hash.h"
-#include "mfma.h"
+// Training dropout (template flag DROP, entry hg_readout_mse_drop_f32): the same body with up to three sites (pre-pool, hidden
+// 1, hidden 2).  The backward leaves the masked dh in LDS for the layer's dgamma and dbeta.  The p = 0 instantiations keep
+// their argument block (RhArgs<false> is the `float eps` it replaces) and their statements.
+#include "readout_head.h"
 
 namespace {
 
@@ -49,17 +40,6 @@ __device__ unsigned long long* rh_stamp_buf = nullptr;
 #else
 #define RH_STAMP(slot) do { } while (0)
 #endif
-
-constexpr int RH_THREADS = 512;
-constexpr int RH_WAVES = RH_THREADS / 64;
-constexpr int RH_ROWS = 16;  // molecules per workgroup = the M of one MFMA tile
-
-struct RhWeights {
-    const float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *w3, *b3;
-};
-struct RhSlabs {   // per-workgroup partial gradients: [n_wg][H*C], [n_wg][H*H], [n_wg][3H] x 2, [n_wg][H+4]
-    float *w1, *w2, *v1, *v2, *v3;
-};
 
 // The LayerNorms' eps and, with DROP, the dropout arguments: ONE kernel argument in the place of `float eps` (rowln.h's
 // LnArgs does the same for the row kernels).
@@ -75,49 +55,22 @@ struct RhArgs<true> {
     const int64_t *seed_x, *seed_h1, *seed_h2;
 };
 // what a thread derives from them once: one hash key per site
-struct RhSite {
-    DropKey key;
-    uint32_t thr;
-    float inv;
-};
 template <bool DROP>
 struct RhSites {
     __device__ explicit RhSites(const RhArgs<DROP>&) {}
 };
 template <>
 struct RhSites<true> {
-    RhSite x, h1, h2;
+    RoSite x, h1, h2;
     __device__ explicit RhSites(const RhArgs<true>& a)
         : x{drop_key(a.thr_x ? (uint64_t)*a.seed_x : 0), a.thr_x, a.inv_x},
           h1{drop_key(a.thr_h ? (uint64_t)*a.seed_h1 : 0), a.thr_h, a.inv_h},
           h2{drop_key(a.thr_h ? (uint64_t)*a.seed_h2 : 0), a.thr_h, a.inv_h} {}
+    __device__ __forceinline__ const RoSite& hidden(int layer) const { return layer == 1 ? h1 : h2; }
 };
-// keep-scale of element row * H + c of a hidden site.  A lane's columns are l + 32 j, so it asks for the aligned pair
-// that holds c (keep_scale2's contract: an even index; row * H is even) and takes its half.
-__device__ __forceinline__ float rh_keep(const RhSite& s, int64_t row, int H, int c) {
-    float k0, k1;
-    keep_scale2(s.key, (uint64_t)row * (uint64_t)H + (uint64_t)(c & ~1), s.thr, s.inv, k0, k1);
-    return (c & 1) ? k1 : k0;
-}
-// v *= keep of the float4 at node row n, columns 4 cl .. 4 cl + 3 of the [N, C] rows (pre-pool site; C % 4 == 0)
-template <int C>
-__device__ __forceinline__ void rh_mask4(const RhSite& s, int n, int cl, float4& v) {
-    if (s.thr) keep_scale4(s.key, (uint64_t)n * (uint64_t)C + (uint64_t)(4 * cl), s.thr, s.inv, v);
-}
-
-// sum over the 32 lanes that share a row
-__device__ __forceinline__ float half_sum(float v) {
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 8);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 1);
-    return v;
-}
 
 // out[m][n] = sum_k A[m][k] W[n][k]: A in LDS (16 rows, stride lda), W [N][K] row-major in global memory.
-// The two halves are separate so that a tile's weights can be requested a phase ahead of their use (the kernel
-// is a chain of short dependent phases on 17 workgroups: every exposed memory latency is step time).
+// The two halves are separate so that a tile's weights can be requested a phase ahead of their use.
 template <int K>
 __device__ __forceinline__ void wt_tile_load(const float* __restrict__ W, int t, int lane, float4 (&b)[K / 16]) {
     const float* wrow = W + (int64_t)(16 * t + (lane & 15)) * K + 4 * (lane >> 4);
@@ -167,58 +120,6 @@ __device__ __forceinline__ void w_cols_mma(const float* sA, int lda, const float
     for (int g = 0; g < 4; ++g) sOut[(4 * q + g) * ldo + 16 * t + r] = acc[g];
 }
 
-// out[o][i] = sum_{m < 16} D[m][o] In[m][i] (both in LDS) -> this workgroup's slab [O][I] in global memory
-template <int O, int I>
-__device__ __forceinline__ void outer_rows(const float* sD, int ldd, const float* sIn, int ldi,
-                                           float* __restrict__ out, int wave, int lane) {
-    const int r = lane & 15, q = lane >> 4;
-    for (int t = wave; t < (O / 16) * (I / 16); t += RH_WAVES) {
-        const int to = t / (I / 16), ti = t - to * (I / 16);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            acc = mfma16(sD[(4 * q + j) * ldd + 16 * to + r], sIn[(4 * q + j) * ldi + 16 * ti + r], acc);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) out[(int64_t)(16 * to + 4 * q + g) * I + 16 * ti + r] = acc[g];
-    }
-}
-
-// in place: sZ <- a = relu(z + bias); sXH <- (a - mean) * rstd; sH <- sXH * gamma + beta; 32 lanes per row.
-// DROP: sH <- keep . (sXH * gamma + beta), keep of hidden site `layer` at molecule row b0 + row
-template <int H, bool DROP>
-__device__ __forceinline__ void relu_ln_rows(float* sZ, const float* __restrict__ bias,
-                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                             float* sXH, float* sH, float* sRstd, int ld, float eps,
-                                             const RhSites<DROP>& ks, int layer, int b0) {
-    constexpr int CPT = H / 32;
-    const int row = threadIdx.x >> 5, l = threadIdx.x & 31;
-    float a[CPT];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-        const int c = l + 32 * j;
-        a[j] = fmaxf(sZ[row * ld + c] + bias[c], 0.f);
-        s += a[j];
-    }
-    const float mu = half_sum(s) * (1.0f / H);
-    float v = 0.f;
-#pragma unroll
-    for (int j = 0; j < CPT; ++j) v = fmaf(a[j] - mu, a[j] - mu, v);
-    const float rstd = 1.0f / sqrtf(half_sum(v) * (1.0f / H) + eps);
-#pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-        const int c = l + 32 * j;
-        const float xh = (a[j] - mu) * rstd;
-        sZ[row * ld + c] = a[j];
-        sXH[row * ld + c] = xh;
-        if constexpr (DROP)
-            sH[row * ld + c] = fmaf(xh, gamma[c], beta[c]) * rh_keep(layer == 1 ? ks.h1 : ks.h2, b0 + row, H, c);
-        else
-            sH[row * ld + c] = fmaf(xh, gamma[c], beta[c]);
-    }
-    if (l == 0) sRstd[row] = rstd;
-}
-
 // dz = [a > 0] * rstd * (dxh - mean(dxh) - xh * mean(dxh * xh)), dxh = dh * gamma; dh from sDH, or (sDH null)
 // dh[m][c] = dy[m] * w3[c] for the last hidden layer.  DROP: dh is multiplied by the recomputed keep of hidden site `layer`
 // first, and the masked dh is left in sDHm (the layer's parameter sums read it there; sDHm may be sDH: own elements only).
@@ -231,6 +132,8 @@ __device__ __forceinline__ void relu_ln_bwd_rows(const float* sDH, const float* 
                                                  int b0, float* sDHm) {
     constexpr int CPT = H / 32;
     const int row = threadIdx.x >> 5, l = threadIdx.x & 31;
+    RoSite site{};
+    if constexpr (DROP) site = ks.hidden(layer);
     float dxh[CPT], xh[CPT];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -238,7 +141,7 @@ __device__ __forceinline__ void relu_ln_bwd_rows(const float* sDH, const float* 
         const int c = l + 32 * j;
         float dh = sDH ? sDH[row * ld + c] : sDy[row] * w3[c];
         if constexpr (DROP) {
-            dh *= rh_keep(layer == 1 ? ks.h1 : ks.h2, b0 + row, H, c);
+            dh *= ro_keep(site, b0 + row, H, c);
             sDHm[row * ld + c] = dh;
         }
         xh[j] = sXH[row * ld + c];
@@ -246,8 +149,8 @@ __device__ __forceinline__ void relu_ln_bwd_rows(const float* sDH, const float* 
         s1 += dxh[j];
         s2 = fmaf(dxh[j], xh[j], s2);
     }
-    s1 = half_sum(s1) * (1.0f / H);
-    s2 = half_sum(s2) * (1.0f / H);
+    s1 = ro_half_sum(s1) * (1.0f / H);
+    s2 = ro_half_sum(s2) * (1.0f / H);
     const float rstd = sRstd[row];
 #pragma unroll
     for (int j = 0; j < CPT; ++j) {
@@ -261,16 +164,16 @@ __device__ __forceinline__ void relu_ln_bwd_rows(const float* sDH, const float* 
 template <int H>
 __device__ __forceinline__ void ln_param_sums(const float* sDH, const float* __restrict__ w3, const float* sDy,
                                               const float* sXH, const float* sDZ, int ld, float* __restrict__ out) {
-    static_assert(3 * H <= RH_THREADS, "one thread per (quantity, column)");
+    static_assert(3 * H <= RO_THREADS, "one thread per (quantity, column)");
     const int t = threadIdx.x;
     if (t >= 3 * H) return;
     const int which = t / H, c = t - which * H;
     float s = 0.f;
     if (which == 0) {
-        for (int m = 0; m < RH_ROWS; ++m) s += sDZ[m * ld + c];
+        for (int m = 0; m < RO_ROWS; ++m) s += sDZ[m * ld + c];
     } else {
         const float wc = sDH ? 0.f : w3[c];
-        for (int m = 0; m < RH_ROWS; ++m) {
+        for (int m = 0; m < RO_ROWS; ++m) {
             const float dh = sDH ? sDH[m * ld + c] : sDy[m] * wc;
             s += which == 1 ? dh * sXH[m * ld + c] : dh;
         }
@@ -281,18 +184,18 @@ __device__ __forceinline__ void ln_param_sums(const float* sDH, const float* __r
 template <int C, int H>
 struct RhLds {
     static constexpr int LX = C + 4, LH = H + 4;
-    static constexpr int X = 0, DX = X + RH_ROWS * LX, A1 = DX + RH_ROWS * LX, XH1 = A1 + RH_ROWS * LH,
-                         H1 = XH1 + RH_ROWS * LH, A2 = H1 + RH_ROWS * LH, XH2 = A2 + RH_ROWS * LH,
-                         H2 = XH2 + RH_ROWS * LH, DZ2 = H2 + RH_ROWS * LH, DH1 = DZ2 + RH_ROWS * LH,
-                         DZ1 = DH1 + RH_ROWS * LH, STAT = DZ1 + RH_ROWS * LH, VEC = STAT + 4 * RH_ROWS,
+    static constexpr int X = 0, DX = X + RO_ROWS * LX, A1 = DX + RO_ROWS * LX, XH1 = A1 + RO_ROWS * LH,
+                         H1 = XH1 + RO_ROWS * LH, A2 = H1 + RO_ROWS * LH, XH2 = A2 + RO_ROWS * LH,
+                         H2 = XH2 + RO_ROWS * LH, DZ2 = H2 + RO_ROWS * LH, DH1 = DZ2 + RO_ROWS * LH,
+                         DZ1 = DH1 + RO_ROWS * LH, STAT = DZ1 + RO_ROWS * LH, VEC = STAT + 4 * RO_ROWS,
                          TOTAL = VEC + 7 * H + 4;   // VEC: b1 g1 be1 b2 g2 be2 w3 b3
 };
 
 template <int C, int H, bool DROP = false>
-__global__ void __launch_bounds__(RH_THREADS)
-k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n_graphs, int n_real, RhWeights w,
+__global__ void __launch_bounds__(RO_THREADS)
+k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n_graphs, int n_real, RoWeights w,
               RhArgs<DROP> ra, const float* __restrict__ target, float* __restrict__ y, float* __restrict__ loss,
-              float* __restrict__ dX, RhSlabs slab, float* __restrict__ loss_part, int* __restrict__ state) {
+              float* __restrict__ dX, RoSlabs slab, float* __restrict__ loss_part, int* __restrict__ state) {
     using L = RhLds<C, H>;
     constexpr int LX = L::LX, LH = L::LH;
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
@@ -308,13 +211,13 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     float* sDH1 = s_mem + L::DH1;
     float* sDZ1 = s_mem + L::DZ1;
     float* sR1 = s_mem + L::STAT;
-    float* sR2 = sR1 + RH_ROWS;
-    float* sDy = sR2 + RH_ROWS;
-    float* sSq = sDy + RH_ROWS;
+    float* sR2 = sR1 + RO_ROWS;
+    float* sDy = sR2 + RO_ROWS;
+    float* sSq = sDy + RO_ROWS;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b0 = blockIdx.x * RH_ROWS;
+    const int b0 = blockIdx.x * RO_ROWS;
     const bool train = target != nullptr;
     const float eps = ra.eps;
     RH_STAMP(0);
@@ -323,18 +226,18 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     float* sV = s_mem + L::VEC;
     const float *vb1 = sV, *vg1 = sV + H, *vbe1 = sV + 2 * H, *vb2 = sV + 3 * H, *vg2 = sV + 4 * H,
                 *vbe2 = sV + 5 * H, *vw3 = sV + 6 * H, *vb3 = sV + 7 * H;
-    constexpr int VPT = (7 * H + RH_THREADS - 1) / RH_THREADS;
+    constexpr int VPT = (7 * H + RO_THREADS - 1) / RO_THREADS;
     float vreg[VPT];
     {
         const float* src[7] = {w.b1, w.g1, w.be1, w.b2, w.g2, w.be2, w.w3};
 #pragma unroll
         for (int k = 0; k < VPT; ++k) {
-            const int i = threadIdx.x + k * RH_THREADS;
+            const int i = threadIdx.x + k * RO_THREADS;
             vreg[k] = i < 7 * H ? src[i / H][i % H] : 0.f;
         }
     }
     const float vb3_reg = w.b3[0];
-    static_assert(H / 16 <= RH_WAVES && C / 16 <= 2 * RH_WAVES, "one H tile, two C tiles per wavefront");
+    static_assert(H / 16 <= RO_WAVES && C / 16 <= 2 * RO_WAVES, "one H tile, two C tiles per wavefront");
     const bool has_h_tile = wave < H / 16;
     float4 bw1[C / 16];
     if (has_h_tile) wt_tile_load<C>(w.w1, wave, lane, bw1);
@@ -364,11 +267,11 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
 #pragma unroll
             for (int u = 0; u < DEEP; ++u) {
                 if (n0 + u * AP < end0) {
-                    if constexpr (DROP) rh_mask4<C>(ks.x, n0 + u * AP, cl, v0[u]);
+                    if constexpr (DROP) ro_mask4<C>(ks.x, n0 + u * AP, cl, v0[u]);
                     f4_add(acc0, v0[u]);
                 }
                 if (n1 + u * AP < end1) {
-                    if constexpr (DROP) rh_mask4<C>(ks.x, n1 + u * AP, cl, v1[u]);
+                    if constexpr (DROP) ro_mask4<C>(ks.x, n1 + u * AP, cl, v1[u]);
                     f4_add(acc1, v1[u]);
                 }
             }
@@ -387,7 +290,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     }
 #pragma unroll
     for (int k = 0; k < VPT; ++k) {
-        const int i = threadIdx.x + k * RH_THREADS;
+        const int i = threadIdx.x + k * RO_THREADS;
         if (i < 7 * H) sV[i] = vreg[k];
     }
     if (threadIdx.x == 0) sV[7 * H] = vb3_reg;
@@ -403,7 +306,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     }
     __syncthreads();
     RH_STAMP(3);
-    relu_ln_rows<H, DROP>(sA1, vb1, vg1, vbe1, sXH1, sH1, sR1, LH, eps, ks, 1, b0);
+    ro_relu_ln_rows<H, DROP>(sA1, vb1, vg1, vbe1, sXH1, sH1, sR1, LH, eps, ks, 1, b0);
     __syncthreads();
     RH_STAMP(4);
     float cw2[H / 4];
@@ -413,7 +316,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     }
     __syncthreads();
     RH_STAMP(5);
-    relu_ln_rows<H, DROP>(sA2, vb2, vg2, vbe2, sXH2, sH2, sR2, LH, eps, ks, 2, b0);
+    ro_relu_ln_rows<H, DROP>(sA2, vb2, vg2, vbe2, sXH2, sH2, sR2, LH, eps, ks, 2, b0);
     __syncthreads();
     RH_STAMP(6);
     {
@@ -422,7 +325,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < CPT; ++j) s = fmaf(sH2[row * LH + l + 32 * j], vw3[l + 32 * j], s);
-        s = half_sum(s) + vb3[0];
+        s = ro_half_sum(s) + vb3[0];
         if (l == 0) {
             const int b = b0 + row;
             if (b < n_graphs) y[b] = s;
@@ -449,11 +352,11 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
         const int t = threadIdx.x;
         if (t < H) {
             float s = 0.f;
-            for (int m = 0; m < RH_ROWS; ++m) s = fmaf(sDy[m], sH2[m * LH + t], s);
+            for (int m = 0; m < RO_ROWS; ++m) s = fmaf(sDy[m], sH2[m * LH + t], s);
             v3[t] = s;
         } else if (t == H) {
             float s = 0.f, e = 0.f;
-            for (int m = 0; m < RH_ROWS; ++m) { s += sDy[m]; e += sSq[m]; }
+            for (int m = 0; m < RO_ROWS; ++m) { s += sDy[m]; e += sSq[m]; }
             v3[H] = s;
             v3[H + 1] = 0.f; v3[H + 2] = 0.f; v3[H + 3] = 0.f;
             // agent-scope atomic store: visible to the other XCDs without a cache write-back; it has long
@@ -464,13 +367,13 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     __syncthreads();
     RH_STAMP(8);
     float cw1a[H / 4], cw1b[H / 4];   // W1 columns of this wavefront's (up to) two C tiles, for dx
-    const bool has_c0 = wave < C / 16, has_c1 = wave + RH_WAVES < C / 16;
+    const bool has_c0 = wave < C / 16, has_c1 = wave + RO_WAVES < C / 16;
     if (has_h_tile) w_cols_mma<H>(sDZ2, LH, cw2, sDH1, LH, wave, lane);
     if (has_c0) w_cols_load<H, C>(w.w1, wave, lane, cw1a);
-    if (has_c1) w_cols_load<H, C>(w.w1, wave + RH_WAVES, lane, cw1b);
+    if (has_c1) w_cols_load<H, C>(w.w1, wave + RO_WAVES, lane, cw1b);
     if constexpr (DROP) ln_param_sums<H>(sDZ1, nullptr, nullptr, sXH2, sDZ2, LH, slab.v2 + wg * 3 * H);
     else ln_param_sums<H>(nullptr, vw3, sDy, sXH2, sDZ2, LH, slab.v2 + wg * 3 * H);
-    outer_rows<H, H>(sDZ2, LH, sH1, LH, slab.w2 + wg * H * H, wave, lane);
+    ro_outer_rows<H, H>(sDZ2, LH, sH1, LH, slab.w2 + wg * H * H, wave, lane);
     RH_STAMP(9);
     __syncthreads();
     RH_STAMP(10);
@@ -478,7 +381,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     __syncthreads();
     RH_STAMP(11);
     if (has_c0) w_cols_mma<H>(sDZ1, LH, cw1a, sDX, LX, wave, lane);
-    if (has_c1) w_cols_mma<H>(sDZ1, LH, cw1b, sDX, LX, wave + RH_WAVES, lane);
+    if (has_c1) w_cols_mma<H>(sDZ1, LH, cw1b, sDX, LX, wave + RO_WAVES, lane);
     __syncthreads();
     RH_STAMP(12);
 
@@ -491,7 +394,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
         const int beg = rowptr[b], end = rowptr[b + 1];
         for (int n = beg + sub; n < end; n += AP) {
             float4 gn = g;
-            if constexpr (DROP) rh_mask4<C>(ks.x, n, cl, gn);
+            if constexpr (DROP) ro_mask4<C>(ks.x, n, cl, gn);
             *reinterpret_cast<float4*>(dX + (int64_t)n * C + 4 * cl) = gn;
         }
     }
@@ -499,7 +402,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     RH_STAMP(13);
     // ---- the two large gradient slabs last: nothing in this kernel waits for them
     ln_param_sums<H>(sDH1, nullptr, nullptr, sXH1, sDZ1, LH, slab.v1 + wg * 3 * H);
-    outer_rows<H, C>(sDZ1, LH, sX, LX, slab.w1 + wg * (int64_t)H * C, wave, lane);
+    ro_outer_rows<H, C>(sDZ1, LH, sX, LX, slab.w1 + wg * (int64_t)H * C, wave, lane);
     RH_STAMP(14);
 
     // ---- loss = sum of the workgroups' partials / n_real, by the last workgroup to arrive, in workgroup order
@@ -517,30 +420,9 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     }
 }
 
-struct RhPlan {
-    int n_wg;
-    size_t off_w1, off_w2, off_v1, off_v2, off_v3, off_loss, off_discard, total;   // in floats
-};
-
-RhPlan rh_plan(int n_graphs, int C, int H) {
-    RhPlan p;
-    p.n_wg = (n_graphs + RH_ROWS - 1) / RH_ROWS;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-    p.off_w1 = take((size_t)p.n_wg * H * C);
-    p.off_w2 = take((size_t)p.n_wg * H * H);
-    p.off_v1 = take((size_t)p.n_wg * 3 * H);
-    p.off_v2 = take((size_t)p.n_wg * 3 * H);
-    p.off_v3 = take((size_t)p.n_wg * (H + 4));
-    p.off_loss = take((size_t)p.n_wg);
-    p.off_discard = take(4);
-    p.total = o;
-    return p;
-}
-
 template <int C, int H, bool DROP>
-int rh_launch(const float* x, const int32_t* rowptr, int n_graphs, int n_real, const RhWeights& w, const RhArgs<DROP>& ra,
-              const float* target, float* y, float* loss, float* dx, const RhSlabs& slab, float* loss_part, int* state,
+int rh_launch(const float* x, const int32_t* rowptr, int n_graphs, int n_real, const RoWeights& w, const RhArgs<DROP>& ra,
+              const float* target, float* y, float* loss, float* dx, const RoSlabs& slab, float* loss_part, int* state,
               int n_wg, hipStream_t stream) {
     constexpr size_t lds = (size_t)RhLds<C, H>::TOTAL * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS budget");
@@ -551,7 +433,7 @@ int rh_launch(const float* x, const int32_t* rowptr, int n_graphs, int n_real, c
             return EQH_ERR_LAUNCH;
         attr_set = true;
     }
-    hipLaunchKernelGGL((k_readout_mse<C, H, DROP>), dim3(n_wg), dim3(RH_THREADS), lds, stream, x, rowptr, n_graphs, n_real, w,
+    hipLaunchKernelGGL((k_readout_mse<C, H, DROP>), dim3(n_wg), dim3(RO_THREADS), lds, stream, x, rowptr, n_graphs, n_real, w,
                        ra, target, y, loss, dx, slab, loss_part, state);
     EQH_CHECK_LAUNCH();
     return EQH_OK;
@@ -571,7 +453,7 @@ extern "C" int hg_readout_mse_supported(int32_t C, int32_t H) {
 
 extern "C" size_t hg_readout_mse_workspace_bytes(int32_t n_graphs, int32_t C, int32_t H) {
     if (n_graphs <= 0 || !hg_readout_mse_supported(C, H)) return 0;
-    return rh_plan(n_graphs, C, H).total * sizeof(float);
+    return ro_plan(n_graphs, C, H).total * sizeof(float);
 }
 
 namespace {
@@ -584,30 +466,17 @@ int readout_mse(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t
                 void* stream_) {
     if (n_graphs < 0 || n_real < 0 || n_real > n_graphs || !hg_readout_mse_supported(C, H)) return EQH_ERR_ARG;
     if (n_graphs == 0) return EQH_OK;
-    if (!x || !rowptr || !weights || !y) return EQH_ERR_ARG;
-    for (int i = 0; i < 10; ++i)
-        if (!weights[i]) return EQH_ERR_ARG;
-    if (!eqh_aligned16(x) || !eqh_aligned16(weights[0]) || !eqh_aligned16(weights[4])) return EQH_ERR_ALIGN;
+    const RoPlan p = ro_plan(n_graphs, C, H);
+    int rc = ro_check_args(!x || !rowptr || !y, !eqh_aligned16(x), weights, target, n_real, !dx, !eqh_aligned16(dx), loss,
+                           dweights, workspace, workspace_bytes, p.total * sizeof(float), state);
+    if (rc) return rc;
     const bool train = target != nullptr;
-    if (train) {
-        if (n_real == 0 || !loss || !dx || !dweights || !workspace || !state) return EQH_ERR_ARG;
-        for (int i = 0; i < 10; ++i)
-            if (!dweights[i]) return EQH_ERR_ARG;
-        if (!eqh_aligned16(dx) || !eqh_aligned16(workspace)) return EQH_ERR_ALIGN;
-        if (workspace_bytes < hg_readout_mse_workspace_bytes(n_graphs, C, H)) return EQH_ERR_ARG;
-    }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const RhPlan p = rh_plan(n_graphs, C, H);
     float* ws = static_cast<float*>(workspace);
-    RhWeights w{weights[0], weights[1], weights[2], weights[3], weights[4],
-                weights[5], weights[6], weights[7], weights[8], weights[9]};
-    RhSlabs slab{nullptr, nullptr, nullptr, nullptr, nullptr};
-    float* loss_part = nullptr;
-    if (train) {
-        slab = RhSlabs{ws + p.off_w1, ws + p.off_w2, ws + p.off_v1, ws + p.off_v2, ws + p.off_v3};
-        loss_part = ws + p.off_loss;
-    }
-    int rc = EQH_ERR_ARG;
+    const RoWeights w = ro_weights(weights);
+    const RoSlabs slab = ro_slabs(ws, p, train);
+    float* loss_part = train ? ws + p.off_loss : nullptr;
+    rc = EQH_ERR_ARG;
 #define RH_CASE(CC, HH)                                                                                           \
     if (C == CC && H == HH)                                                                                       \
         rc = rh_launch<CC, HH, DROP>(x, rowptr, n_graphs, n_real, w, ra, target, y, loss, dx, slab, loss_part, state, \
@@ -615,20 +484,7 @@ int readout_mse(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t
     RH_CASE(64, 64) RH_CASE(64, 128) RH_CASE(128, 64) RH_CASE(128, 128) RH_CASE(256, 64) RH_CASE(256, 128)
 #undef RH_CASE
     if (rc || !train) return rc;
-    // parameter gradients: fixed-order sums over the workgroup slabs (deferred into the step's batched
-    // reduction when that is active)
-    rc = eqh_reduce_slabs_async(slab.w1, p.n_wg, (int64_t)H * C, dweights[0], stream, accumulate);
-    if (rc) return rc;
-    rc = eqh_reduce_slabs_async(slab.w2, p.n_wg, (int64_t)H * H, dweights[4], stream, accumulate);
-    if (rc) return rc;
-    rc = eqh_reduce_slabs3_async(slab.v1, p.n_wg, 3 * (int64_t)H, dweights[1], dweights[2], dweights[3], H, H,
-                                 accumulate, stream);
-    if (rc) return rc;
-    rc = eqh_reduce_slabs3_async(slab.v2, p.n_wg, 3 * (int64_t)H, dweights[5], dweights[6], dweights[7], H, H,
-                                 accumulate, stream);
-    if (rc) return rc;
-    return eqh_reduce_slabs3_async(slab.v3, p.n_wg, (int64_t)H + 4, dweights[8], dweights[9], ws + p.off_discard, H, 1,
-                                   accumulate, stream);
+    return ro_reduce_head_slabs(slab, p, C, H, dweights, ws + p.off_discard, accumulate, stream);
 }
 
 }  // namespace
@@ -646,9 +502,7 @@ extern "C" int hg_readout_mse_drop_f32(const float* x, const int32_t* rowptr, in
                                        float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
                                        size_t workspace_bytes, int32_t* state, float p_x, float p_h, const int64_t* seed_x,
                                        const int64_t* seed_h1, const int64_t* seed_h2, void* stream_) {
-    // 0 <= p < 1 (a NaN fails the comparison), checked first; a call without an active site belongs to hg_readout_mse_f32
-    if (!(p_x >= 0.f && p_x < 1.f) || !(p_h >= 0.f && p_h < 1.f) || (p_x == 0.f && p_h == 0.f)) return EQH_ERR_ARG;
-    if ((p_x > 0.f && !seed_x) || (p_h > 0.f && (!seed_h1 || !seed_h2))) return EQH_ERR_ARG;
+    if (int rc = ro_check_drop(p_x, p_h, seed_x != nullptr, seed_h1 && seed_h2)) return rc;
     const RhArgs<true> ra{eps, drop_threshold(p_x), drop_threshold(p_h), drop_inv_keep(p_x), drop_inv_keep(p_h),
                           seed_x, seed_h1, seed_h2};
     return readout_mse<true>(x, rowptr, n_graphs, n_real, C, H, weights, ra, target, y, loss, dx, dweights, accumulate,

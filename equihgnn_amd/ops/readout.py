@@ -118,57 +118,87 @@ def _readout_state(device):
     return _READOUT_STATE[key]
 
 
+def _head_forward(ctx, entry, pools, rows, n_graphs, n_real, C, target, eps, unit_grad, params, drop, weights):
+    """What the forward() of both heads does around its one launch, ``entry``_f32 or (``drop`` given) ``entry``_drop_f32:
+    ``pools`` are the entry's leading arguments (the rows and their per-molecule lists), ``rows`` the fp32 row tensors that get a
+    gradient.  The gradients are computed here; the parameter gradients go straight into their persistent accumulators when
+    ``unit_grad`` says the incoming gradient is the implicit 1 of ``loss.backward()`` and every parameter has one.
+    ``drop`` = (p_x, p_h, *seeds): the seeds are int64 device tensors the kernel reads, so nothing is kept for the backward."""
+    dev = rows[0].device
+    target = _f32c(target)
+    ws_t = [_f32c(w.detach()) for w in weights]
+    H = ws_t[0].shape[0]
+    L = hip.lib()
+    vp = ctypes.c_void_p * 10
+    y = torch.empty(n_graphs, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    d_rows = [torch.empty_like(r) for r in rows]
+    ws_bytes = getattr(L, entry + "_workspace_bytes")(n_graphs, C, H)
+    ws = _workspace(ws_bytes, dev)
+    tg = [_acc_target(w) for w in params] if unit_grad else [None]
+    in_place = all(t is not None for t in tg)
+    grads = tg if in_place else [torch.empty_like(w) for w in ws_t]
+    args = (*pools, n_graphs, n_real, C, H, vp(*[w.data_ptr() for w in ws_t]), float(eps), _ptr(target), _ptr(y), _ptr(loss),
+            *[_ptr(d) for d in d_rows], vp(*[g.data_ptr() for g in grads]), 1 if in_place else 0, _ptr(ws), ws_bytes,
+            _ptr(_readout_state(dev)))
+    name = entry + "_f32"
+    if drop is not None:
+        name = entry + "_drop_f32"
+        args += (drop[0], drop[1], *[_ptr(s) for s in drop[2:]])
+    hip.check(getattr(L, name)(*args, _stream(dev)), name)
+    ctx.unit_grad, ctx.in_place, ctx.n_rows = unit_grad, in_place, len(rows)
+    ctx.targets = tg if (unit_grad and not in_place) else [None] * 10
+    ctx.held = (*d_rows,) if in_place else (*d_rows, *grads)
+    ctx.mark_non_differentiable(y)
+    ctx.set_materialize_grads(False)        # (no zero-filled gradient tensor for the predictions: one launch per step)
+    return loss, y
+
+
+def _head_backward(ctx, dloss, n_other):
+    """Hands out what _head_forward computed -- scaled by the incoming gradient unless ``unit_grad``.  ``n_other``: forward()'s
+    arguments between the rows and the ten weights, which get no gradient."""
+    held, n_rows = ctx.held, ctx.n_rows
+    if dloss is None:
+        return (None,) * (n_rows + n_other + 10)
+    if not ctx.unit_grad:
+        held = tuple(h * dloss for h in held)
+    dws = (None,) * 10 if ctx.in_place else tuple(_hand_out([g.view_as(g) for g in held[n_rows:]], ctx.targets))
+    return (*held[:n_rows], *(None,) * n_other, *dws)
+
+
 class _ReadoutMse(torch.autograd.Function):
     """pool -> MLP(C -> H -> H -> 1, LN) -> MSE with loss, dx and all parameter gradients from ONE launch
-    (hg_readout_mse_f32).  The gradients are computed in forward(); backward() hands them out -- scaled by the
-    incoming gradient unless ``unit_grad`` says it is the implicit 1 of ``loss.backward()``, in which case the
-    parameter gradients may already have been added to their persistent accumulators.
-    ``drop`` = (p_x, p_h, seed_x, seed_h1, seed_h2) or None: the launch under training dropout (hg_readout_mse_drop_f32);
-    the seeds are int64 device tensors the kernel reads, so nothing is kept for the backward."""
+    (hg_readout_mse_f32): _head_forward / _head_backward.
+    ``drop`` = (p_x, p_h, seed_x, seed_h1, seed_h2) or None: the launch under training dropout (hg_readout_mse_drop_f32)."""
 
     @staticmethod
     def forward(ctx, x, rowptr, n_graphs, n_real, target, eps, unit_grad, params, drop, *weights):
         _require_gpu(x, "readout_mse")
-        dev = x.device
-        x, target = _f32c(x), _f32c(target)
-        ws_t = [_f32c(w.detach()) for w in weights]
-        H, C = ws_t[0].shape
-        L = hip.lib()
-        vp = ctypes.c_void_p * 10
-        y = torch.empty(n_graphs, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dx = torch.empty_like(x)
-        ws_bytes = L.hg_readout_mse_workspace_bytes(n_graphs, C, H)
-        ws = _workspace(ws_bytes, dev)
-        tg = [_acc_target(w) for w in params] if unit_grad else [None]
-        in_place = all(t is not None for t in tg)
-        grads = tg if in_place else [torch.empty_like(w) for w in ws_t]
-        args = (_ptr(x), _ptr(rowptr), n_graphs, n_real, C, H, vp(*[w.data_ptr() for w in ws_t]), float(eps), _ptr(target),
-                _ptr(y), _ptr(loss), _ptr(dx), vp(*[g.data_ptr() for g in grads]), 1 if in_place else 0, _ptr(ws), ws_bytes,
-                _ptr(_readout_state(dev)))
-        if drop is None:
-            hip.check(L.hg_readout_mse_f32(*args, _stream(dev)), "hg_readout_mse_f32")
-        else:
-            p_x, p_h, seed_x, seed_h1, seed_h2 = drop
-            hip.check(L.hg_readout_mse_drop_f32(*args, p_x, p_h, _ptr(seed_x), _ptr(seed_h1), _ptr(seed_h2), _stream(dev)),
-                      "hg_readout_mse_drop_f32")
-        ctx.unit_grad, ctx.in_place = unit_grad, in_place
-        ctx.targets = tg if (unit_grad and not in_place) else [None] * 10
-        ctx.held = (dx,) if in_place else (dx, *grads)
-        ctx.mark_non_differentiable(y)
-        ctx.set_materialize_grads(False)        # (no zero-filled gradient tensor for the predictions: one launch per step)
-        return loss, y
+        x = _f32c(x)
+        return _head_forward(ctx, "hg_readout_mse", (_ptr(x), _ptr(rowptr)), (x,), n_graphs, n_real, weights[0].shape[1], target,
+                             eps, unit_grad, params, drop, weights)
 
     @staticmethod
     def backward(ctx, dloss, _dy):
-        held = ctx.held
-        if dloss is None:
-            return (None,) * 19
-        if not ctx.unit_grad:
-            held = tuple(h * dloss for h in held)
-        dx = held[0]
-        dws = (None,) * 10 if ctx.in_place else tuple(_hand_out([g.view_as(g) for g in held[1:]], ctx.targets))
-        return (dx, None, None, None, None, None, None, None, None, *dws)
+        return _head_backward(ctx, dloss, 8)
+
+
+class _ReadoutPairMse(torch.autograd.Function):
+    """[node pool | order > 2 hyperedge pool] -> MLP(2C -> H -> H -> 1, LN) -> MSE with loss, dx, de and all parameter gradients
+    from ONE launch (hg_readout_pair_mse_f32): _ReadoutMse for the paired tail.
+    ``drop`` = (p_x, p_h, seed_x, seed_e, seed_h1, seed_h2) or None (hg_readout_pair_mse_drop_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, e, rowptr, he_pool, e_order, n_graphs, n_real, target, eps, unit_grad, params, drop, *weights):
+        _require_gpu(x, "readout_pair_mse")
+        x, e = _f32c(x), _f32c(e)
+        pools = (_ptr(x), _ptr(rowptr), _ptr(e), _ptr(he_pool.rowptr), _ptr(he_pool.perm), _ptr(e_order), e.shape[0])
+        return _head_forward(ctx, "hg_readout_pair_mse", pools, (x, e), n_graphs, n_real, x.shape[1], target, eps, unit_grad,
+                             params, drop, weights)
+
+    @staticmethod
+    def backward(ctx, dloss, _dy):
+        return _head_backward(ctx, dloss, 10)
 
 
 def _head_drop_p(mlp) -> float:
@@ -176,19 +206,62 @@ def _head_drop_p(mlp) -> float:
     return float(mlp.dropout) if (mlp.training and mlp.dropout > 0) else 0.0
 
 
-def _head_shape_ok(x, mlp) -> bool:
+def _mlp_ok(mlp, c_in: int, C: int, entry: str) -> bool:
+    """The head's side of the question (no tensor, no device): three Linears c_in -> H -> H -> 1, LayerNorm behind both hidden
+    layers with one eps, no InputNorm, (C, H) the kernel behind ``entry`` is built for."""
     lins = getattr(mlp, "lins", None)
-    if lins is None or len(lins) != 3 or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32:
+    if lins is None or len(lins) != 3:
         return False
     norms = mlp.normalizations
     if mlp.InputNorm or not all(isinstance(n, torch.nn.LayerNorm) for n in norms[1:]):
         return False
-    H, C = lins[0].weight.shape
-    if lins[1].weight.shape != (H, H) or lins[2].weight.shape != (1, H) or x.shape[1] != C:
+    H = lins[0].weight.shape[0]
+    if lins[0].weight.shape != (H, c_in) or lins[1].weight.shape != (H, H) or lins[2].weight.shape != (1, H):
         return False
     if norms[1].eps != norms[2].eps:
         return False
-    return bool(hip.lib().hg_readout_mse_supported(C, H))
+    return bool(getattr(hip.lib(), entry)(C, H))
+
+
+def _rows_ok(*rows) -> bool:
+    return all(t.is_cuda and t.dim() == 2 and t.dtype == torch.float32 and t.shape[1] == rows[0].shape[1] for t in rows)
+
+
+def _drop_allowed(p_x: float, p_h: float) -> bool:
+    """Whether a head may take its dropout form: ops.FUSED_DROPOUT and ops.READOUT_DROPOUT on, at least one probability above 0
+    and both below 1."""
+    return bool(_rows.FUSED_DROPOUT and READOUT_DROPOUT) and 0.0 <= p_x < 1.0 and p_h < 1.0 and (p_x > 0.0 or p_h > 0.0)
+
+
+def _mlp_weights(mlp) -> tuple:
+    """The ten weights of the head's MLP in the entries' order; its leaf parameters are registered for the in-place gradient
+    accumulators."""
+    lins, norms = mlp.lins, mlp.normalizations
+    weights = (lins[0].weight, lins[0].bias, norms[1].weight, norms[1].bias, lins[1].weight, lins[1].bias,
+               norms[2].weight, norms[2].bias, lins[2].weight, lins[2].bias)
+    if torch.is_grad_enabled():
+        for w in weights:
+            if w.requires_grad and w.is_leaf:
+                (LINEAR_PARAMS if w.dim() == 2 else ACC_PARAMS)[id(w)] = w
+    return weights
+
+
+def _head_drop(name: str, device, p_x: float, mlp, seeds, n_pre: int):
+    """The ``drop`` argument of a head's Function: None without an active site, else (p_x, p_h, *seeds) with the seeds drawn
+    through ``_dropout_seed`` in the order of the separate launches -- the ``n_pre`` pre-pool sites (only when ``p_x`` > 0),
+    hidden layer 1, hidden layer 2 -- unless ``seeds`` gives them."""
+    p_x, p_h = float(p_x), _head_drop_p(mlp)
+    if not (0.0 <= p_x < 1.0 and p_h < 1.0):
+        raise ValueError(f"{name}: dropout probabilities have to be in [0, 1), but got p_x = {p_x}, p_h = {p_h}")
+    if p_x == 0.0 and p_h == 0.0:
+        return None
+    if seeds is None:
+        seeds = [_dropout_seed(device, p) for p in (p_x,) * n_pre + (p_h, p_h)]
+    return (p_x, p_h, *seeds)
+
+
+def _head_shape_ok(x, mlp) -> bool:
+    return _rows_ok(x) and _mlp_ok(mlp, x.shape[1], x.shape[1], "hg_readout_mse_supported")
 
 
 def readout_mse_supported(x, mlp) -> bool:
@@ -199,12 +272,8 @@ def readout_mse_supported(x, mlp) -> bool:
 
 def readout_mse_drop_supported(x, mlp, p_x: float = 0.0) -> bool:
     """Whether ops.readout_mse takes this head UNDER an active dropout -- ``p_x`` in front of the pool, the head's own behind
-    its hidden layers: the shapes of readout_mse_supported, ops.FUSED_DROPOUT and ops.READOUT_DROPOUT on, at least one
-    probability above 0 and both below 1."""
-    p_x, p_h = float(p_x), _head_drop_p(mlp)
-    if not (_rows.FUSED_DROPOUT and READOUT_DROPOUT) or not (0.0 <= p_x < 1.0 and p_h < 1.0) or (p_x == 0.0 and p_h == 0.0):
-        return False
-    return _head_shape_ok(x, mlp)
+    its hidden layers: the shapes of readout_mse_supported and _drop_allowed."""
+    return _drop_allowed(float(p_x), _head_drop_p(mlp)) and _head_shape_ok(x, mlp)
 
 
 def readout_mse(x, pool_rowptr, mlp, target, n_real=None, unit_grad=False, p_x=0.0, seeds=None):
@@ -216,115 +285,28 @@ def readout_mse(x, pool_rowptr, mlp, target, n_real=None, unit_grad=False, p_x=0
     ``seeds`` = (seed_x, seed_h1, seed_h2) gives them (int64 [1] device tensors; None for a site that is off)."""
     n_graphs = pool_rowptr.shape[0] - 1
     n_real = n_graphs if n_real is None else int(n_real)
-    lins, norms = mlp.lins, mlp.normalizations
-    weights = (lins[0].weight, lins[0].bias, norms[1].weight, norms[1].bias, lins[1].weight, lins[1].bias,
-               norms[2].weight, norms[2].bias, lins[2].weight, lins[2].bias)
-    if torch.is_grad_enabled():
-        for w in weights:
-            if w.requires_grad and w.is_leaf:
-                (LINEAR_PARAMS if w.dim() == 2 else ACC_PARAMS)[id(w)] = w
-    p_x, p_h = float(p_x), _head_drop_p(mlp)
-    if not (0.0 <= p_x < 1.0 and p_h < 1.0):
-        raise ValueError(f"readout_mse: dropout probabilities have to be in [0, 1), but got p_x = {p_x}, p_h = {p_h}")
-    drop = None
-    if p_x > 0.0 or p_h > 0.0:
-        if seeds is None:
-            seed_x = _dropout_seed(x.device, p_x)
-            seeds = (seed_x, _dropout_seed(x.device, p_h), _dropout_seed(x.device, p_h))
-        drop = (p_x, p_h, *seeds)
-    return _ReadoutMse.apply(x, pool_rowptr, n_graphs, n_real, target, norms[1].eps, unit_grad, weights, drop, *weights)
-
-
-class _ReadoutPairMse(torch.autograd.Function):
-    """[node pool | order > 2 hyperedge pool] -> MLP(2C -> H -> H -> 1, LN) -> MSE with loss, dx, de and all parameter gradients
-    from ONE launch (hg_readout_pair_mse_f32): _ReadoutMse for the paired tail.  The gradients are computed in forward();
-    backward() hands them out, scaled by the incoming gradient unless ``unit_grad``.
-    ``drop`` = (p_x, p_h, seed_x, seed_e, seed_h1, seed_h2) or None (hg_readout_pair_mse_drop_f32)."""
-
-    @staticmethod
-    def forward(ctx, x, e, rowptr, he_pool, e_order, n_graphs, n_real, target, eps, unit_grad, params, drop, *weights):
-        _require_gpu(x, "readout_pair_mse")
-        dev = x.device
-        x, e, target = _f32c(x), _f32c(e), _f32c(target)
-        ws_t = [_f32c(w.detach()) for w in weights]
-        H, C = ws_t[0].shape[0], x.shape[1]
-        L = hip.lib()
-        vp = ctypes.c_void_p * 10
-        y = torch.empty(n_graphs, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        dx, de = torch.empty_like(x), torch.empty_like(e)
-        ws_bytes = L.hg_readout_pair_mse_workspace_bytes(n_graphs, C, H)
-        ws = _workspace(ws_bytes, dev)
-        tg = [_acc_target(w) for w in params] if unit_grad else [None]
-        in_place = all(t is not None for t in tg)
-        grads = tg if in_place else [torch.empty_like(w) for w in ws_t]
-        args = (_ptr(x), _ptr(rowptr), _ptr(e), _ptr(he_pool.rowptr), _ptr(he_pool.perm), _ptr(e_order), e.shape[0], n_graphs,
-                n_real, C, H, vp(*[w.data_ptr() for w in ws_t]), float(eps), _ptr(target), _ptr(y), _ptr(loss), _ptr(dx),
-                _ptr(de), vp(*[g.data_ptr() for g in grads]), 1 if in_place else 0, _ptr(ws), ws_bytes,
-                _ptr(_readout_state(dev)))
-        if drop is None:
-            hip.check(L.hg_readout_pair_mse_f32(*args, _stream(dev)), "hg_readout_pair_mse_f32")
-        else:
-            p_x, p_h, seed_x, seed_e, seed_h1, seed_h2 = drop
-            hip.check(L.hg_readout_pair_mse_drop_f32(*args, p_x, p_h, _ptr(seed_x), _ptr(seed_e), _ptr(seed_h1), _ptr(seed_h2),
-                                                     _stream(dev)), "hg_readout_pair_mse_drop_f32")
-        ctx.unit_grad, ctx.in_place = unit_grad, in_place
-        ctx.targets = tg if (unit_grad and not in_place) else [None] * 10
-        ctx.held = (dx, de) if in_place else (dx, de, *grads)
-        ctx.mark_non_differentiable(y)
-        ctx.set_materialize_grads(False)
-        return loss, y
-
-    @staticmethod
-    def backward(ctx, dloss, _dy):
-        held = ctx.held
-        if dloss is None:
-            return (None,) * 22
-        if not ctx.unit_grad:
-            held = tuple(h * dloss for h in held)
-        dx, de = held[0], held[1]
-        dws = (None,) * 10 if ctx.in_place else tuple(_hand_out([g.view_as(g) for g in held[2:]], ctx.targets))
-        return (dx, de, None, None, None, None, None, None, None, None, None, None, *dws)
+    weights = _mlp_weights(mlp)
+    drop = _head_drop("readout_mse", x.device, p_x, mlp, seeds, 1)
+    return _ReadoutMse.apply(x, pool_rowptr, n_graphs, n_real, target, mlp.normalizations[1].eps, unit_grad, weights, drop,
+                             *weights)
 
 
 def _pair_mlp_ok(mlp, C: int) -> bool:
-    """The head's side of the question (no tensor, no device): three Linears 2C -> H -> H -> 1, LayerNorm behind both hidden
-    layers with one eps, no InputNorm, (C, H) the kernel is built for."""
-    lins = getattr(mlp, "lins", None)
-    if lins is None or len(lins) != 3:
-        return False
-    norms = mlp.normalizations
-    if mlp.InputNorm or not all(isinstance(n, torch.nn.LayerNorm) for n in norms[1:]):
-        return False
-    H = lins[0].weight.shape[0]
-    if lins[0].in_features != 2 * C or lins[1].weight.shape != (H, H) or lins[2].weight.shape != (1, H):
-        return False
-    if norms[1].eps != norms[2].eps:
-        return False
-    return bool(hip.lib().hg_readout_pair_mse_supported(C, H))
-
-
-def _pair_head_shape_ok(x, e, mlp) -> bool:
-    for t in (x, e):
-        if not t.is_cuda or t.dim() != 2 or t.dtype != torch.float32:
-            return False
-    return e.shape[1] == x.shape[1] and _pair_mlp_ok(mlp, x.shape[1])
+    """_mlp_ok for the paired head: the first Linear on 2C inputs."""
+    return _mlp_ok(mlp, 2 * C, C, "hg_readout_pair_mse_supported")
 
 
 def readout_pair_mse_supported(x, e, mlp) -> bool:
     """Whether ops.readout_pair_mse takes this head without dropout: x [N, C] and e [M, C] 2-D fp32 device rows, MLP of three
     Linears (the first on 2C inputs) with LayerNorm hidden layers and one output, no active dropout, widths the kernel is built
     for (C in 64 / 128 / 256, hidden width 128 / 256)."""
-    return _head_drop_p(mlp) == 0.0 and _pair_head_shape_ok(x, e, mlp)
+    return _head_drop_p(mlp) == 0.0 and _rows_ok(x, e) and _pair_mlp_ok(mlp, x.shape[1])
 
 
 def readout_pair_mse_drop_supported(x, e, mlp, p_x: float = 0.0) -> bool:
     """... UNDER an active dropout (``p_x`` on x and e in front of the pools, the head's own behind its hidden layers): the shapes
-    of readout_pair_mse_supported, ops.FUSED_DROPOUT and ops.READOUT_DROPOUT on, a probability above 0, both below 1."""
-    p_x, p_h = float(p_x), _head_drop_p(mlp)
-    if not (_rows.FUSED_DROPOUT and READOUT_DROPOUT) or not (0.0 <= p_x < 1.0 and p_h < 1.0) or (p_x == 0.0 and p_h == 0.0):
-        return False
-    return _pair_head_shape_ok(x, e, mlp)
+    of readout_pair_mse_supported and _drop_allowed."""
+    return _drop_allowed(float(p_x), _head_drop_p(mlp)) and _rows_ok(x, e) and _pair_mlp_ok(mlp, x.shape[1])
 
 
 def readout_pair_mse(x, e, index, n_e, e_order, mlp, target, n_real=None, unit_grad=False, p_x=0.0, seeds=None):
@@ -344,22 +326,7 @@ def readout_pair_mse(x, e, index, n_e, e_order, mlp, target, n_real=None, unit_g
     if e_order.dtype != torch.int64:
         raise TypeError(f"readout_pair_mse: e_order must be int64, got {e_order.dtype}")
     n_real = n_graphs if n_real is None else int(n_real)
-    lins, norms = mlp.lins, mlp.normalizations
-    weights = (lins[0].weight, lins[0].bias, norms[1].weight, norms[1].bias, lins[1].weight, lins[1].bias,
-               norms[2].weight, norms[2].bias, lins[2].weight, lins[2].bias)
-    if torch.is_grad_enabled():
-        for w in weights:
-            if w.requires_grad and w.is_leaf:
-                (LINEAR_PARAMS if w.dim() == 2 else ACC_PARAMS)[id(w)] = w
-    p_x, p_h = float(p_x), _head_drop_p(mlp)
-    if not (0.0 <= p_x < 1.0 and p_h < 1.0):
-        raise ValueError(f"readout_pair_mse: dropout probabilities have to be in [0, 1), but got p_x = {p_x}, p_h = {p_h}")
-    drop = None
-    if p_x > 0.0 or p_h > 0.0:
-        if seeds is None:
-            seed_x = _dropout_seed(x.device, p_x)
-            seed_e = _dropout_seed(x.device, p_x)
-            seeds = (seed_x, seed_e, _dropout_seed(x.device, p_h), _dropout_seed(x.device, p_h))
-        drop = (p_x, p_h, *seeds)
-    return _ReadoutPairMse.apply(x, e, index.pool.rowptr, he_pool, e_order.contiguous(), n_graphs, n_real, target, norms[1].eps,
-                                 unit_grad, weights, drop, *weights)
+    weights = _mlp_weights(mlp)
+    drop = _head_drop("readout_pair_mse", x.device, p_x, mlp, seeds, 2)
+    return _ReadoutPairMse.apply(x, e, index.pool.rowptr, he_pool, e_order.contiguous(), n_graphs, n_real, target,
+                                 mlp.normalizations[1].eps, unit_grad, weights, drop, *weights)
