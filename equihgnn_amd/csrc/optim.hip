@@ -19,7 +19,10 @@
 //   reads anyway.  eqh_swap_f32 exchanges two flat buffers in place (live parameters <-> their average around an evaluation).
 // eqh_copy_many: up to 64 small device-to-device copies in one launch (gradients that autograd allocated,
 //   packed into the flat gradient buffer).
+// eqh_mse_fwd_bwd / eqh_smooth_l1_fwd_bwd: a batch's loss and its gradient in one launch of one workgroup (k_mse; k_smooth_l1
+//   for the l1 / smooth-l1 / Huber family of loss_family.h).
 #include "common.h"
+#include "loss_family.h"
 
 namespace {
 
@@ -309,12 +312,44 @@ k_mse(const float* __restrict__ pred, const float* __restrict__ target, int n, f
     if (threadIdx.x == 0) loss[0] = s_sum[0] * inv_n;
 }
 
+// k_mse for the family of loss_family.h: the same element-to-thread assignment and the same tree.  The gradient is
+// slope / n by a division, so the linear branch gives the correctly rounded +-scale / n.
+__global__ void __launch_bounds__(1024)
+k_smooth_l1(const float* __restrict__ pred, const float* __restrict__ target, int n, float beta, float scale,
+            float* __restrict__ loss, float* __restrict__ grad) {
+    __shared__ float s_sum[1024];
+    const float fn = (float)n;
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n; i += 1024) {   // fixed assignment and tree: reproducible
+        float term, slope;
+        sl1_term_slope(pred[i] - target[i], beta, scale, term, slope);
+        acc += term;
+        grad[i] = slope / fn;
+    }
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) s_sum[threadIdx.x] += s_sum[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = s_sum[0] / fn;
+}
+
 }  // namespace
 
 extern "C" int eqh_mse_fwd_bwd(const float* pred, const float* target, int32_t n, float* loss, float* grad,
                                void* stream_) {
     if (n <= 0 || n > 65536 || !pred || !target || !loss || !grad) return EQH_ERR_ARG;
     hipLaunchKernelGGL(k_mse, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream_), pred, target, (int)n, loss, grad);
+    EQH_CHECK_LAUNCH();
+    return EQH_OK;
+}
+
+extern "C" int eqh_smooth_l1_fwd_bwd(const float* pred, const float* target, int32_t n, float beta, float scale, float* loss,
+                                     float* grad, void* stream_) {
+    if (n <= 0 || n > 65536 || !pred || !target || !loss || !grad || !sl1_args_ok(beta, scale)) return EQH_ERR_ARG;
+    hipLaunchKernelGGL(k_smooth_l1, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream_), pred, target, (int)n, beta, scale,
+                       loss, grad);
     EQH_CHECK_LAUNCH();
     return EQH_OK;
 }

@@ -191,10 +191,10 @@ struct RhLds {
                          TOTAL = VEC + 7 * H + 4;   // VEC: b1 g1 be1 b2 g2 be2 w3 b3
 };
 
-template <int C, int H, bool DROP = false>
+template <int C, int H, bool DROP = false, bool SL1 = false>
 __global__ void __launch_bounds__(RO_THREADS)
 k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n_graphs, int n_real, RoWeights w,
-              RhArgs<DROP> ra, const float* __restrict__ target, float* __restrict__ y, float* __restrict__ loss,
+              RoLossArgs<RhArgs<DROP>, SL1> ra, const float* __restrict__ target, float* __restrict__ y, float* __restrict__ loss,
               float* __restrict__ dX, RoSlabs slab, float* __restrict__ loss_part, int* __restrict__ state) {
     using L = RhLds<C, H>;
     constexpr int LX = L::LX, LH = L::LH;
@@ -332,8 +332,14 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
             float dy = 0.f, sq = 0.f;
             if (train && b < n_real) {
                 const float d = s - target[b];
+                if constexpr (SL1) {
+                    float slope;
+                    sl1_term_slope(d, ra.beta, ra.scale, sq, slope);
+                    dy = slope / (float)n_real;
+                } else {
                 dy = 2.0f * d / (float)n_real;
                 sq = d * d;
+                }
             }
             sDy[row] = dy;
             sSq[row] = sq;
@@ -347,7 +353,7 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     const int64_t wg = blockIdx.x;
     // (DROP: the masked dh2 goes to sDZ1, which is free until the LayerNorm-1 backward two barriers on)
     relu_ln_bwd_rows<H, DROP>(nullptr, vw3, sDy, sA2, sXH2, vg2, sR2, sDZ2, LH, ks, 2, b0, sDZ1);
-    {   // dw3 | db3 | pad, and the squared-error partial (row order)
+    {   // dw3 | db3 | pad, and the squared-error partial (SL1: the sum of the rows' loss terms), in row order
         float* v3 = slab.v3 + wg * (H + 4);
         const int t = threadIdx.x;
         if (t < H) {
@@ -420,20 +426,21 @@ k_readout_mse(const float* __restrict__ X, const int* __restrict__ rowptr, int n
     }
 }
 
-template <int C, int H, bool DROP>
-int rh_launch(const float* x, const int32_t* rowptr, int n_graphs, int n_real, const RoWeights& w, const RhArgs<DROP>& ra,
+template <int C, int H, bool DROP, bool SL1>
+int rh_launch(const float* x, const int32_t* rowptr, int n_graphs, int n_real, const RoWeights& w,
+              const RoLossArgs<RhArgs<DROP>, SL1>& ra,
               const float* target, float* y, float* loss, float* dx, const RoSlabs& slab, float* loss_part, int* state,
               int n_wg, hipStream_t stream) {
     constexpr size_t lds = (size_t)RhLds<C, H>::TOTAL * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS budget");
     static bool attr_set = false;
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_readout_mse<C, H, DROP>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_readout_mse<C, H, DROP, SL1>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return EQH_ERR_LAUNCH;
         attr_set = true;
     }
-    hipLaunchKernelGGL((k_readout_mse<C, H, DROP>), dim3(n_wg), dim3(RO_THREADS), lds, stream, x, rowptr, n_graphs, n_real, w,
+    hipLaunchKernelGGL((k_readout_mse<C, H, DROP, SL1>), dim3(n_wg), dim3(RO_THREADS), lds, stream, x, rowptr, n_graphs, n_real, w,
                        ra, target, y, loss, dx, slab, loss_part, state);
     EQH_CHECK_LAUNCH();
     return EQH_OK;
@@ -458,10 +465,11 @@ extern "C" size_t hg_readout_mse_workspace_bytes(int32_t n_graphs, int32_t C, in
 
 namespace {
 
-// hg_readout_mse_f32 (DROP = false) and hg_readout_mse_drop_f32 (DROP = true): one host function
-template <bool DROP>
+// hg_readout_mse_f32 (DROP = false) and hg_readout_mse_drop_f32 (DROP = true), and their hg_readout_sl1_* twins (SL1 = true):
+// one host function
+template <bool DROP, bool SL1>
 int readout_mse(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C, int32_t H,
-                const float* const* weights, const RhArgs<DROP>& ra, const float* target, float* y, float* loss, float* dx,
+                const float* const* weights, const RoLossArgs<RhArgs<DROP>, SL1>& ra, const float* target, float* y, float* loss, float* dx,
                 float* const* dweights, int32_t accumulate, void* workspace, size_t workspace_bytes, int32_t* state,
                 void* stream_) {
     if (n_graphs < 0 || n_real < 0 || n_real > n_graphs || !hg_readout_mse_supported(C, H)) return EQH_ERR_ARG;
@@ -479,8 +487,8 @@ int readout_mse(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t
     rc = EQH_ERR_ARG;
 #define RH_CASE(CC, HH)                                                                                           \
     if (C == CC && H == HH)                                                                                       \
-        rc = rh_launch<CC, HH, DROP>(x, rowptr, n_graphs, n_real, w, ra, target, y, loss, dx, slab, loss_part, state, \
-                                     p.n_wg, stream);
+        rc = rh_launch<CC, HH, DROP, SL1>(x, rowptr, n_graphs, n_real, w, ra, target, y, loss, dx, slab, loss_part, \
+                                          state, p.n_wg, stream);
     RH_CASE(64, 64) RH_CASE(64, 128) RH_CASE(128, 64) RH_CASE(128, 128) RH_CASE(256, 64) RH_CASE(256, 128)
 #undef RH_CASE
     if (rc || !train) return rc;
@@ -493,7 +501,7 @@ extern "C" int hg_readout_mse_f32(const float* x, const int32_t* rowptr, int32_t
                                   int32_t H, const float* const* weights, float eps, const float* target, float* y,
                                   float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
                                   size_t workspace_bytes, int32_t* state, void* stream_) {
-    return readout_mse<false>(x, rowptr, n_graphs, n_real, C, H, weights, RhArgs<false>{eps}, target, y, loss, dx, dweights,
+    return readout_mse<false, false>(x, rowptr, n_graphs, n_real, C, H, weights, RhArgs<false>{eps}, target, y, loss, dx, dweights,
                               accumulate, workspace, workspace_bytes, state, stream_);
 }
 
@@ -505,6 +513,31 @@ extern "C" int hg_readout_mse_drop_f32(const float* x, const int32_t* rowptr, in
     if (int rc = ro_check_drop(p_x, p_h, seed_x != nullptr, seed_h1 && seed_h2)) return rc;
     const RhArgs<true> ra{eps, drop_threshold(p_x), drop_threshold(p_h), drop_inv_keep(p_x), drop_inv_keep(p_h),
                           seed_x, seed_h1, seed_h2};
-    return readout_mse<true>(x, rowptr, n_graphs, n_real, C, H, weights, ra, target, y, loss, dx, dweights, accumulate,
+    return readout_mse<true, false>(x, rowptr, n_graphs, n_real, C, H, weights, ra, target, y, loss, dx, dweights, accumulate,
                              workspace, workspace_bytes, state, stream_);
+}
+
+// The same two launches with the loss family of loss_family.h in the place of the squared error (SL1 forms of the kernel):
+// beta >= 0 and scale > 0, both finite, checked with the entry's own arguments ahead of any launch.
+extern "C" int hg_readout_sl1_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C,
+                                  int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                                  float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
+                                  size_t workspace_bytes, int32_t* state, float beta, float scale, void* stream_) {
+    if (!sl1_args_ok(beta, scale)) return EQH_ERR_ARG;
+    return readout_mse<false, true>(x, rowptr, n_graphs, n_real, C, H, weights, ro_sl1_args(RhArgs<false>{eps}, beta, scale),
+                                    target, y, loss, dx, dweights, accumulate, workspace, workspace_bytes, state, stream_);
+}
+
+extern "C" int hg_readout_sl1_drop_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C,
+                                       int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                                       float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
+                                       size_t workspace_bytes, int32_t* state, float p_x, float p_h, const int64_t* seed_x,
+                                       const int64_t* seed_h1, const int64_t* seed_h2, float beta, float scale,
+                                       void* stream_) {
+    if (!sl1_args_ok(beta, scale)) return EQH_ERR_ARG;
+    if (int rc = ro_check_drop(p_x, p_h, seed_x != nullptr, seed_h1 && seed_h2)) return rc;
+    const RhArgs<true> ra{eps, drop_threshold(p_x), drop_threshold(p_h), drop_inv_keep(p_x), drop_inv_keep(p_h),
+                          seed_x, seed_h1, seed_h2};
+    return readout_mse<true, true>(x, rowptr, n_graphs, n_real, C, H, weights, ro_sl1_args(ra, beta, scale), target, y, loss,
+                                   dx, dweights, accumulate, workspace, workspace_bytes, state, stream_);
 }

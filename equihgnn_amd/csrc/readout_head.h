@@ -27,12 +27,36 @@
 // set of locals the kernel has at that point); they stay written out in the kernels.  The LayerNorm backward stays apart too:
 // readout.hip's stores the masked dh unconditionally, the paired kernel's only where it has a buffer, and one body with a
 // nullable destination put a null test into k_readout_mse's DROP forms.
+//
+// Other losses (template flag SL1 of the kernels, entries hg_readout_sl1_* / hg_readout_pair_sl1_*): the family of
+// loss_family.h in the place of the squared error -- the two statements that form a row's dy and its loss term, under
+// `if constexpr (SL1)`, with the MSE statements literally where they were.  The partial is then the workgroup's sum of terms.
+// beta and scale travel behind the kernel's own argument block (RoLossArgs), so an MSE form keeps its block as it is.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "drop_hash.h"
+#include "loss_family.h"
 #include "mfma.h"
 
 namespace {
+
+// a head's argument block A (RhArgs / RpArgs) with the family's two floats behind it -- for the SL1 forms only
+template <class A>
+struct RoSl1Args : A {
+    float beta, scale;
+};
+template <class A, bool SL1>
+using RoLossArgs = std::conditional_t<SL1, RoSl1Args<A>, A>;
+template <class A>
+inline RoSl1Args<A> ro_sl1_args(const A& a, float beta, float scale) {
+    RoSl1Args<A> r;
+    static_cast<A&>(r) = a;
+    r.beta = beta;
+    r.scale = scale;
+    return r;
+}
 
 constexpr int RO_THREADS = 512;
 constexpr int RO_WAVES = RO_THREADS / 64;

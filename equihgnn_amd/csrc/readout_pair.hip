@@ -311,9 +311,10 @@ struct RpLds {
     static_assert(RO_ROWS * LX <= 4 * HB, "the pooled gradient fits the four H buffers it overwrites");
 };
 
-template <int C, int H, bool DROP = false>
+template <int C, int H, bool DROP = false, bool SL1 = false>
 __global__ void __launch_bounds__(RO_THREADS)
-k_readout_pair_mse(RpPools in, int n_graphs, int n_real, RoWeights w, RpArgs<DROP> ra, const float* __restrict__ target,
+k_readout_pair_mse(RpPools in, int n_graphs, int n_real, RoWeights w, RoLossArgs<RpArgs<DROP>, SL1> ra,
+                   const float* __restrict__ target,
                    float* __restrict__ y, float* __restrict__ loss, float* __restrict__ dX, float* __restrict__ dE,
                    RoSlabs slab, float* __restrict__ loss_part, int* __restrict__ state) {
     using L = RpLds<C, H>;
@@ -392,8 +393,14 @@ k_readout_pair_mse(RpPools in, int n_graphs, int n_real, RoWeights w, RpArgs<DRO
             float dy = 0.f, sq = 0.f;
             if (train && b < n_real) {
                 const float d = s - target[b];
+                if constexpr (SL1) {
+                    float slope;
+                    sl1_term_slope(d, ra.beta, ra.scale, sq, slope);
+                    dy = slope / (float)n_real;
+                } else {
                 dy = 2.0f * d / (float)n_real;
                 sq = d * d;
+                }
             }
             sDy[row] = dy;
             sSq[row] = sq;
@@ -405,7 +412,7 @@ k_readout_pair_mse(RpPools in, int n_graphs, int n_real, RoWeights w, RpArgs<DRO
     // ---- backward
     const int64_t wg = blockIdx.x;
     rp_relu_ln_bwd_rows<H, DROP>(nullptr, vw3, sDy, sA2, sXH2, vg2, sR2, LH, ks, 2, b0);      // a2 -> dZ2
-    {   // dw3 | db3 | pad, and the squared-error partial (row order)
+    {   // dw3 | db3 | pad, and the squared-error partial (SL1: the sum of the rows' loss terms), in row order
         float* v3 = slab.v3 + wg * (H + 4);
         const int t = threadIdx.x;
         if (t < H) {
@@ -497,20 +504,20 @@ k_readout_pair_mse(RpPools in, int n_graphs, int n_real, RoWeights w, RpArgs<DRO
     }
 }
 
-template <int C, int H, bool DROP>
-int rp_launch(const RpPools& in, int n_graphs, int n_real, const RoWeights& w, const RpArgs<DROP>& ra, const float* target,
-              float* y, float* loss, float* dx, float* de, const RoSlabs& slab, float* loss_part, int* state, int n_wg,
+template <int C, int H, bool DROP, bool SL1>
+int rp_launch(const RpPools& in, int n_graphs, int n_real, const RoWeights& w, const RoLossArgs<RpArgs<DROP>, SL1>& ra,
+              const float* target, float* y, float* loss, float* dx, float* de, const RoSlabs& slab, float* loss_part, int* state, int n_wg,
               hipStream_t stream) {
     constexpr size_t lds = (size_t)RpLds<C, H>::TOTAL * sizeof(float);
     static_assert(lds <= 160 * 1024, "LDS budget");
     static bool attr_set = false;
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_readout_pair_mse<C, H, DROP>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_readout_pair_mse<C, H, DROP, SL1>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return EQH_ERR_LAUNCH;
         attr_set = true;
     }
-    hipLaunchKernelGGL((k_readout_pair_mse<C, H, DROP>), dim3(n_wg), dim3(RO_THREADS), lds, stream, in, n_graphs, n_real, w, ra,
+    hipLaunchKernelGGL((k_readout_pair_mse<C, H, DROP, SL1>), dim3(n_wg), dim3(RO_THREADS), lds, stream, in, n_graphs, n_real, w, ra,
                        target, y, loss, dx, de, slab, loss_part, state);
     EQH_CHECK_LAUNCH();
     return EQH_OK;
@@ -529,10 +536,11 @@ extern "C" size_t hg_readout_pair_mse_workspace_bytes(int32_t n_graphs, int32_t 
 
 namespace {
 
-// hg_readout_pair_mse_f32 (DROP = false) and hg_readout_pair_mse_drop_f32 (DROP = true): one host function
-template <bool DROP>
+// hg_readout_pair_mse_f32 (DROP = false) and hg_readout_pair_mse_drop_f32 (DROP = true), and their hg_readout_pair_sl1_* twins
+// (SL1 = true): one host function
+template <bool DROP, bool SL1>
 int readout_pair_mse(const RpPools& in, int32_t n_graphs, int32_t n_real, int32_t C, int32_t H, const float* const* weights,
-                     const RpArgs<DROP>& ra, const float* target, float* y, float* loss, float* dx, float* de,
+                     const RoLossArgs<RpArgs<DROP>, SL1>& ra, const float* target, float* y, float* loss, float* dx, float* de,
                      float* const* dweights, int32_t accumulate, void* workspace, size_t workspace_bytes, int32_t* state,
                      void* stream_) {
     if (n_graphs < 0 || n_real < 0 || n_real > n_graphs || in.n_e < 0 || !hg_readout_pair_mse_supported(C, H))
@@ -553,7 +561,7 @@ int readout_pair_mse(const RpPools& in, int32_t n_graphs, int32_t n_real, int32_
     rc = EQH_ERR_ARG;
 #define RP_CASE(CC, HH)                                                                                               \
     if (C == CC && H == HH)                                                                                           \
-        rc = rp_launch<CC, HH, DROP>(in, n_graphs, n_real, w, ra, target, y, loss, dx, de, slab, loss_part, state, p.n_wg, \
+        rc = rp_launch<CC, HH, DROP, SL1>(in, n_graphs, n_real, w, ra, target, y, loss, dx, de, slab, loss_part, state, p.n_wg, \
                                      stream);
     RP_CASE(64, 128) RP_CASE(64, 256) RP_CASE(128, 128) RP_CASE(128, 256) RP_CASE(256, 128) RP_CASE(256, 256)
 #undef RP_CASE
@@ -570,7 +578,7 @@ extern "C" int hg_readout_pair_mse_f32(const float* x, const int32_t* rowptr, co
                                        float* const* dweights, int32_t accumulate, void* workspace, size_t workspace_bytes,
                                        int32_t* state, void* stream_) {
     const RpPools in{x, rowptr, e, e_rowptr, e_perm, e_order, n_e};
-    return readout_pair_mse<false>(in, n_graphs, n_real, C, H, weights, RpArgs<false>{eps}, target, y, loss, dx, de, dweights,
+    return readout_pair_mse<false, false>(in, n_graphs, n_real, C, H, weights, RpArgs<false>{eps}, target, y, loss, dx, de, dweights,
                                    accumulate, workspace, workspace_bytes, state, stream_);
 }
 
@@ -586,6 +594,38 @@ extern "C" int hg_readout_pair_mse_drop_f32(const float* x, const int32_t* rowpt
     const RpArgs<true> ra{eps, drop_threshold(p_x), drop_threshold(p_h), drop_inv_keep(p_x), drop_inv_keep(p_h),
                           seed_x, seed_e, seed_h1, seed_h2};
     const RpPools in{x, rowptr, e, e_rowptr, e_perm, e_order, n_e};
-    return readout_pair_mse<true>(in, n_graphs, n_real, C, H, weights, ra, target, y, loss, dx, de, dweights, accumulate,
+    return readout_pair_mse<true, false>(in, n_graphs, n_real, C, H, weights, ra, target, y, loss, dx, de, dweights, accumulate,
                                   workspace, workspace_bytes, state, stream_);
+}
+
+// The same two launches with the loss family of loss_family.h in the place of the squared error (SL1 forms of the kernel):
+// beta >= 0 and scale > 0, both finite, checked with the entry's own arguments ahead of any launch.
+extern "C" int hg_readout_pair_sl1_f32(const float* x, const int32_t* rowptr, const float* e, const int32_t* e_rowptr,
+                                       const int32_t* e_perm, const int64_t* e_order, int32_t n_e, int32_t n_graphs,
+                                       int32_t n_real, int32_t C, int32_t H, const float* const* weights, float eps,
+                                       const float* target, float* y, float* loss, float* dx, float* de,
+                                       float* const* dweights, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                                       int32_t* state, float beta, float scale, void* stream_) {
+    if (!sl1_args_ok(beta, scale)) return EQH_ERR_ARG;
+    const RpPools in{x, rowptr, e, e_rowptr, e_perm, e_order, n_e};
+    return readout_pair_mse<false, true>(in, n_graphs, n_real, C, H, weights, ro_sl1_args(RpArgs<false>{eps}, beta, scale),
+                                         target, y, loss, dx, de, dweights, accumulate, workspace, workspace_bytes, state,
+                                         stream_);
+}
+
+extern "C" int hg_readout_pair_sl1_drop_f32(const float* x, const int32_t* rowptr, const float* e, const int32_t* e_rowptr,
+                                            const int32_t* e_perm, const int64_t* e_order, int32_t n_e, int32_t n_graphs,
+                                            int32_t n_real, int32_t C, int32_t H, const float* const* weights, float eps,
+                                            const float* target, float* y, float* loss, float* dx, float* de,
+                                            float* const* dweights, int32_t accumulate, void* workspace,
+                                            size_t workspace_bytes, int32_t* state, float p_x, float p_h,
+                                            const int64_t* seed_x, const int64_t* seed_e, const int64_t* seed_h1,
+                                            const int64_t* seed_h2, float beta, float scale, void* stream_) {
+    if (!sl1_args_ok(beta, scale)) return EQH_ERR_ARG;
+    if (int rc = ro_check_drop(p_x, p_h, seed_x && seed_e, seed_h1 && seed_h2)) return rc;
+    const RpArgs<true> ra{eps, drop_threshold(p_x), drop_threshold(p_h), drop_inv_keep(p_x), drop_inv_keep(p_h),
+                          seed_x, seed_e, seed_h1, seed_h2};
+    const RpPools in{x, rowptr, e, e_rowptr, e_perm, e_order, n_e};
+    return readout_pair_mse<true, true>(in, n_graphs, n_real, C, H, weights, ro_sl1_args(ra, beta, scale), target, y, loss, dx,
+                                        de, dweights, accumulate, workspace, workspace_bytes, state, stream_);
 }

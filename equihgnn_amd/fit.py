@@ -581,8 +581,13 @@ class Fitter:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  std: Optional[float] = None, patience_lr: int = 10, patience_stop: int = 50,
                  step_factory: Callable = TrainStep, metric_seed: int = 0, clip_gnorm: Optional[float] = None,
-                 device_metrics: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False):
-        """``ema_decay`` / ``ema_warmup``: the training step keeps an exponential moving average of the weights
+                 device_metrics: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                 loss: str = "mse", loss_beta: float = 1.0):
+        """``loss`` / ``loss_beta``: the training loss of the step (``TrainStep`` / ``GraphedTrainStep(loss=.., loss_beta=..)``:
+        "mse", "l1", "smooth_l1" with its beta, "huber" with its delta), checked here by ``ops.loss_spec`` and handed to
+        ``step_factory`` only when it is not "mse", so a factory without the keywords keeps working.  ``train_loss`` in the
+        history is then that loss; validation, the scheduler, early stopping and ``best_state`` stay on ``mae_mean``.
+        ``ema_decay`` / ``ema_warmup``: the training step keeps an exponential moving average of the weights
         (``TrainStep`` / ``GraphedTrainStep(ema_decay=..)``; handed to ``step_factory`` only when given, as ``clip_gnorm``),
         and every evaluation -- the per-epoch validation and ``test`` -- runs inside ``step.averaged()``: the scheduler, early
         stopping and ``best_val_mae`` follow the averaged weights, and ``best_state`` is the state dict taken inside that
@@ -603,6 +608,11 @@ class Fitter:
         self.device_metrics = bool(device_metrics)
         self.host_reads = 0
         extra = {} if clip_gnorm is None else {"clip_gnorm": clip_gnorm}
+        from .ops.readout import loss_spec
+        loss_spec(loss, loss_beta)
+        self.loss, self.loss_beta = loss, float(loss_beta)
+        if loss != "mse":
+            extra.update(loss=loss, loss_beta=self.loss_beta)
         if self.ema_decay is not None:
             extra.update(ema_decay=self.ema_decay, ema_warmup=bool(ema_warmup))
         if self.device_metrics:

@@ -512,13 +512,19 @@ def pool_sum(x, index: HyperIndex):
     return ops.reduce_entries(x, index.pool, index.batch32, "sum")
 
 
+def head_spec(head):
+    """The loss of head = (target, n_real[, unit_grad[, spec]]): its fourth element, an ``ops.loss_spec`` -- missing or None is
+    the MSE."""
+    return head[3] if len(head) > 3 else None
+
+
 def head_loss(out, head):
-    """``out`` itself, or with head = (target, n_real[, unit_grad]) the training loss of main.py:49-63:
-    F.mse_loss over the first n_real molecules (the rest of a padded batch is padding)."""
+    """``out`` itself, or with head = (target, n_real[, unit_grad[, spec]]) the training loss of main.py:49-63 over the first
+    n_real molecules (the rest of a padded batch is padding): F.mse_loss, or the loss of ``spec`` (ops.regression_loss)."""
     if head is None:
         return out
     nb = head[1] or out.shape[0]
-    return ops.mse_loss(out[:nb], head[0][:nb])
+    return ops.regression_loss(out[:nb], head[0][:nb], head_spec(head))
 
 
 def readout(mlp_out, x, index: HyperIndex, taps=None, head=None, p_x=0.0, drop=None):
@@ -535,7 +541,7 @@ def readout(mlp_out, x, index: HyperIndex, taps=None, head=None, p_x=0.0, drop=N
         plain = p_x == 0.0 and ops.readout_mse_supported(x2, mlp_out)
         if head[0].is_cuda and (plain or ops.readout_mse_drop_supported(x2, mlp_out, p_x)):
             loss, _ = ops.readout_mse(x2, index.pool.rowptr, mlp_out, head[0], head[1],
-                                      unit_grad=bool(head[2]) if len(head) > 2 else False, p_x=p_x)
+                                      unit_grad=bool(head[2]) if len(head) > 2 else False, p_x=p_x, loss=head_spec(head))
             ops.signal_point("after_readout")
             return loss
     if drop is not None:

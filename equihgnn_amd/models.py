@@ -21,7 +21,7 @@ from . import ops
 from .equiformer import Equiformer
 from .faformer import FAFormer
 from .index import HyperIndex
-from .layers import (EGNN, MLP, AtomEncoder, BondEncoder, MHNNConv, MHNNSConv, batch_norm_rows, head_loss, pool_sum, readout,
+from .layers import (EGNN, MLP, AtomEncoder, BondEncoder, MHNNConv, MHNNSConv, batch_norm_rows, head_loss, head_spec, pool_sum, readout,
                      real_row_mask)
 from .registry import registry
 from .se3_transformer import SE3Transformer
@@ -217,7 +217,8 @@ class _PairedBase(_Wrapper):
                     elif self._one_launch_head(x, e, taps, head):
                         # the last application's two dropouts, the pools, the head, the loss and their backward: one launch
                         loss, _ = ops.readout_pair_mse(x, e, index, data.n_e, data.e_order, self.mlp_out, head[0], head[1],
-                                                       unit_grad=bool(head[2]) if len(head) > 2 else False, p_x=self._drop_p)
+                                                       unit_grad=bool(head[2]) if len(head) > 2 else False, p_x=self._drop_p,
+                                                       loss=head_spec(head))
                         return loss
                     x, e = self._drop(x), self._drop(e)
             both = self._pool(x, e, index, data)

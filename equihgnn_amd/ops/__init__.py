@@ -75,6 +75,7 @@ from .readout import (  # noqa: F401
     _MseLoss, mse_loss, _READOUT_STATE, _readout_state, _ReadoutMse, readout_mse_supported, readout_mse, _PoolPair, pool_pair,
     pool_pair_bytes, readout_mse_drop_supported, READOUT_DROPOUT, _ReadoutPairMse, readout_pair_mse,
     readout_pair_mse_supported, readout_pair_mse_drop_supported, PAIRED_READOUT,
+    LOSS_KINDS, loss_spec, regression_loss, torch_loss, _SmoothL1Loss,
 )
 from .se3 import (  # noqa: F401
     _RowGemm, _RowGemm2, _RadialWeightLayout, radial_weight_layout, _AttnPool, attn_pool_supported, attn_pool,

@@ -1,11 +1,12 @@
-"""Readout heads (pool + output MLP + MSE in one launch: the S / M tails' and the paired tail's), the paired node /
-high-order-hyperedge pool and the fused MSE loss.
+"""Readout heads (pool + output MLP + loss in one launch: the S / M tails' and the paired tail's), the paired node /
+high-order-hyperedge pool and the fused losses: the MSE, and the L1 / smooth-L1 / Huber family (``loss_spec``).
 
 Part of equihgnn_amd.ops (host-side operators over libequihgnn_hip.so; no CPU fallback).
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import torch
@@ -55,6 +56,90 @@ def mse_loss(pred, target):
     if pred.is_cuda and pred.dtype == torch.float32 and 0 < pred.numel() <= 65536 and not target.requires_grad:
         return _MseLoss.apply(pred.reshape(-1), target.reshape(-1))
     return F.mse_loss(pred, target)
+
+
+LOSS_KINDS = ("mse", "l1", "smooth_l1", "huber")
+
+
+def loss_spec(kind: str, beta: float = 1.0):
+    """The training loss ``kind`` as the heads and ``regression_loss`` take it: None for "mse", else (beta, scale) of the family
+    term(d) = scale * (|d| < beta ? 0.5 d^2 / beta : |d| - 0.5 beta) (csrc/loss_family.h):
+    "l1" -> (0, 1), ``beta`` ignored; "smooth_l1" -> (beta, 1), F.smooth_l1_loss(beta=beta), beta >= 0;
+    "huber" -> (delta, delta) with delta = ``beta`` > 0, F.huber_loss(delta=delta).  ValueError for anything else."""
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"loss_spec: unknown loss {kind!r}, expected one of {LOSS_KINDS}")
+    if kind == "mse":
+        return None
+    if kind == "l1":
+        return (0.0, 1.0)
+    try:
+        b = float(beta)
+    except (TypeError, ValueError):
+        raise ValueError(f"loss_spec: beta must be a number, got {beta!r}") from None
+    if not math.isfinite(b) or b < 0.0:
+        raise ValueError(f"loss_spec: beta must be finite and >= 0, got {beta!r}")
+    if kind == "huber":
+        if b <= 0.0:
+            raise ValueError(f"loss_spec: huber needs delta > 0, got {beta!r}")
+        return (b, b)
+    return (b, 1.0)
+
+
+def _checked_spec(spec, who: str):
+    """A spec handed to an operator directly: None, or two finite floats with beta >= 0 and scale > 0."""
+    if spec is None:
+        return None
+    beta, scale = float(spec[0]), float(spec[1])
+    if not (math.isfinite(beta) and math.isfinite(scale) and beta >= 0.0 and scale > 0.0):
+        raise ValueError(f"{who}: loss spec (beta, scale) must be finite with beta >= 0 and scale > 0, got {spec!r}")
+    return (beta, scale)
+
+
+def torch_loss(pred, target, spec):
+    """The spec's loss through torch.nn.functional (any tensor): what the fused launches are tested against."""
+    if spec is None:
+        return F.mse_loss(pred, target)
+    beta, scale = spec
+    if beta == 0.0:
+        return F.l1_loss(pred, target) if scale == 1.0 else scale * F.l1_loss(pred, target)
+    if scale == 1.0:
+        return F.smooth_l1_loss(pred, target, beta=beta)
+    if scale == beta:
+        return F.huber_loss(pred, target, delta=beta)
+    return scale * F.smooth_l1_loss(pred, target, beta=beta)
+
+
+class _SmoothL1Loss(torch.autograd.Function):
+    """The family's mean loss with forward value and gradient from ONE launch (eqh_smooth_l1_fwd_bwd): _MseLoss's twin."""
+
+    @staticmethod
+    def forward(ctx, pred, target, beta, scale):
+        _require_gpu(pred, "regression_loss")
+        pred, target = _f32c(pred), _f32c(target)
+        n = pred.numel()
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        grad = torch.empty_like(pred)
+        hip.check(hip.lib().eqh_smooth_l1_fwd_bwd(_ptr(pred), _ptr(target), n, beta, scale, _ptr(loss), _ptr(grad),
+                                                  _stream(pred.device)), "eqh_smooth_l1_fwd_bwd")
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (grad,) = ctx.saved_tensors
+        return grad * dloss, None, None, None
+
+
+def regression_loss(pred, target, spec=None):
+    """The training loss of ``spec`` (``loss_spec``): None is ``mse_loss``, unchanged; otherwise the mean of the family's terms,
+    from one launch under mse_loss's conditions (1-D fp32 device tensors of up to 65 536 values), else through torch."""
+    if spec is None:
+        return mse_loss(pred, target)
+    beta, scale = _checked_spec(spec, "regression_loss")
+    if (pred.is_cuda and pred.dtype == torch.float32 and 0 < pred.numel() <= 65536 and not target.requires_grad
+            and pred.shape == target.shape):
+        return _SmoothL1Loss.apply(pred.reshape(-1), target.reshape(-1), beta, scale)
+    return torch_loss(pred, target, (beta, scale))
 
 
 def pool_pair_bytes(N: int, M: int, B: int, C: int) -> tuple:
@@ -118,8 +203,9 @@ def _readout_state(device):
     return _READOUT_STATE[key]
 
 
-def _head_forward(ctx, entry, pools, rows, n_graphs, n_real, C, target, eps, unit_grad, params, drop, weights):
-    """What the forward() of both heads does around its one launch, ``entry``_f32 or (``drop`` given) ``entry``_drop_f32:
+def _head_forward(ctx, entry, pools, rows, n_graphs, n_real, C, target, eps, unit_grad, params, drop, weights, loss_fam=None):
+    """What the forward() of both heads does around its one launch, ``entry``_f32 or (``drop`` given) ``entry``_drop_f32 -- with
+    ``loss_fam`` = (beta, scale) the ``sl1`` twin of either, the two floats in front of the stream:
     ``pools`` are the entry's leading arguments (the rows and their per-molecule lists), ``rows`` the fp32 row tensors that get a
     gradient.  The gradients are computed here; the parameter gradients go straight into their persistent accumulators when
     ``unit_grad`` says the incoming gradient is the implicit 1 of ``loss.backward()`` and every parameter has one.
@@ -145,6 +231,9 @@ def _head_forward(ctx, entry, pools, rows, n_graphs, n_real, C, target, eps, uni
     if drop is not None:
         name = entry + "_drop_f32"
         args += (drop[0], drop[1], *[_ptr(s) for s in drop[2:]])
+    if loss_fam is not None:
+        name = name.replace("_mse", "_sl1")
+        args += (loss_fam[0], loss_fam[1])
     hip.check(getattr(L, name)(*args, _stream(dev)), name)
     ctx.unit_grad, ctx.in_place, ctx.n_rows = unit_grad, in_place, len(rows)
     ctx.targets = tg if (unit_grad and not in_place) else [None] * 10
@@ -169,36 +258,38 @@ def _head_backward(ctx, dloss, n_other):
 class _ReadoutMse(torch.autograd.Function):
     """pool -> MLP(C -> H -> H -> 1, LN) -> MSE with loss, dx and all parameter gradients from ONE launch
     (hg_readout_mse_f32): _head_forward / _head_backward.
-    ``drop`` = (p_x, p_h, seed_x, seed_h1, seed_h2) or None: the launch under training dropout (hg_readout_mse_drop_f32)."""
+    ``drop`` = (p_x, p_h, seed_x, seed_h1, seed_h2) or None: the launch under training dropout (hg_readout_mse_drop_f32).
+    ``loss_fam`` = (beta, scale) or None: the family of ``loss_spec`` in the place of the MSE (hg_readout_sl1_f32 / _drop_f32)."""
 
     @staticmethod
-    def forward(ctx, x, rowptr, n_graphs, n_real, target, eps, unit_grad, params, drop, *weights):
+    def forward(ctx, x, rowptr, n_graphs, n_real, target, eps, unit_grad, params, drop, loss_fam, *weights):
         _require_gpu(x, "readout_mse")
         x = _f32c(x)
         return _head_forward(ctx, "hg_readout_mse", (_ptr(x), _ptr(rowptr)), (x,), n_graphs, n_real, weights[0].shape[1], target,
-                             eps, unit_grad, params, drop, weights)
+                             eps, unit_grad, params, drop, weights, loss_fam)
 
     @staticmethod
     def backward(ctx, dloss, _dy):
-        return _head_backward(ctx, dloss, 8)
+        return _head_backward(ctx, dloss, 9)
 
 
 class _ReadoutPairMse(torch.autograd.Function):
     """[node pool | order > 2 hyperedge pool] -> MLP(2C -> H -> H -> 1, LN) -> MSE with loss, dx, de and all parameter gradients
     from ONE launch (hg_readout_pair_mse_f32): _ReadoutMse for the paired tail.
-    ``drop`` = (p_x, p_h, seed_x, seed_e, seed_h1, seed_h2) or None (hg_readout_pair_mse_drop_f32)."""
+    ``drop`` = (p_x, p_h, seed_x, seed_e, seed_h1, seed_h2) or None (hg_readout_pair_mse_drop_f32); ``loss_fam`` = (beta, scale)
+    or None (hg_readout_pair_sl1_f32 / _drop_f32)."""
 
     @staticmethod
-    def forward(ctx, x, e, rowptr, he_pool, e_order, n_graphs, n_real, target, eps, unit_grad, params, drop, *weights):
+    def forward(ctx, x, e, rowptr, he_pool, e_order, n_graphs, n_real, target, eps, unit_grad, params, drop, loss_fam, *weights):
         _require_gpu(x, "readout_pair_mse")
         x, e = _f32c(x), _f32c(e)
         pools = (_ptr(x), _ptr(rowptr), _ptr(e), _ptr(he_pool.rowptr), _ptr(he_pool.perm), _ptr(e_order), e.shape[0])
         return _head_forward(ctx, "hg_readout_pair_mse", pools, (x, e), n_graphs, n_real, x.shape[1], target, eps, unit_grad,
-                             params, drop, weights)
+                             params, drop, weights, loss_fam)
 
     @staticmethod
     def backward(ctx, dloss, _dy):
-        return _head_backward(ctx, dloss, 10)
+        return _head_backward(ctx, dloss, 11)
 
 
 def _head_drop_p(mlp) -> float:
@@ -276,19 +367,21 @@ def readout_mse_drop_supported(x, mlp, p_x: float = 0.0) -> bool:
     return _drop_allowed(float(p_x), _head_drop_p(mlp)) and _head_shape_ok(x, mlp)
 
 
-def readout_mse(x, pool_rowptr, mlp, target, n_real=None, unit_grad=False, p_x=0.0, seeds=None):
+def readout_mse(x, pool_rowptr, mlp, target, n_real=None, unit_grad=False, p_x=0.0, seeds=None, loss=None):
     """(loss, predictions) of the readout head: x [N, C] node rows, pool_rowptr int32 [B+1] (sorted ``batch``),
     ``mlp`` the output MLP, ``target`` [>= n_real]; loss = mean over the first n_real molecules.
     Under training dropout (``p_x`` > 0: dropout of the node rows in front of the pool; the head's own probability when it is
     training) the launch is the dropout form, see readout_mse_drop_supported.  Its seeds are drawn through ``_dropout_seed`` in
     the order pre-pool (only when ``p_x`` > 0), hidden layer 1, hidden layer 2 -- the order of the separate launches -- unless
-    ``seeds`` = (seed_x, seed_h1, seed_h2) gives them (int64 [1] device tensors; None for a site that is off)."""
+    ``seeds`` = (seed_x, seed_h1, seed_h2) gives them (int64 [1] device tensors; None for a site that is off).
+    ``loss``: None for the MSE, or a ``loss_spec`` (beta, scale): the same launch with that loss (hg_readout_sl1_*)."""
+    loss = _checked_spec(loss, "readout_mse")
     n_graphs = pool_rowptr.shape[0] - 1
     n_real = n_graphs if n_real is None else int(n_real)
     weights = _mlp_weights(mlp)
     drop = _head_drop("readout_mse", x.device, p_x, mlp, seeds, 1)
     return _ReadoutMse.apply(x, pool_rowptr, n_graphs, n_real, target, mlp.normalizations[1].eps, unit_grad, weights, drop,
-                             *weights)
+                             loss, *weights)
 
 
 def _pair_mlp_ok(mlp, C: int) -> bool:
@@ -309,14 +402,16 @@ def readout_pair_mse_drop_supported(x, e, mlp, p_x: float = 0.0) -> bool:
     return _drop_allowed(float(p_x), _head_drop_p(mlp)) and _rows_ok(x, e) and _pair_mlp_ok(mlp, x.shape[1])
 
 
-def readout_pair_mse(x, e, index, n_e, e_order, mlp, target, n_real=None, unit_grad=False, p_x=0.0, seeds=None):
+def readout_pair_mse(x, e, index, n_e, e_order, mlp, target, n_real=None, unit_grad=False, p_x=0.0, seeds=None, loss=None):
     """(loss, predictions) of the paired tail's head: x [N, C] node rows and e [M, C] hyperedge rows of the batch of ``index``
     (its atom pool and, from ``n_e``, its hyperedge pool), ``e_order`` int64 [M] (only hyperedges of order > 2 are pooled),
     ``mlp`` the output MLP on [B, 2C], ``target`` [>= n_real]; loss = mean over the first n_real molecules.
     Under training dropout (``p_x`` > 0 on x and on e in front of the pools; the head's own probability when it is training)
     the launch is the dropout form.  Its seeds are drawn through ``_dropout_seed`` in the order x, e (both only when ``p_x`` >
     0), hidden layer 1, hidden layer 2 -- the order of the separate launches -- unless ``seeds`` = (seed_x, seed_e, seed_h1,
-    seed_h2) gives them (int64 [1] device tensors; None for a site that is off)."""
+    seed_h2) gives them (int64 [1] device tensors; None for a site that is off).
+    ``loss``: None for the MSE, or a ``loss_spec`` (beta, scale): the same launch with that loss (hg_readout_pair_sl1_*)."""
+    loss = _checked_spec(loss, "readout_pair_mse")
     if x.dim() != 2 or e.dim() != 2 or x.shape[1] != e.shape[1]:
         raise ValueError(f"readout_pair_mse: x [N, C] and e [M, C] of one width, got {tuple(x.shape)} and {tuple(e.shape)}")
     he_pool, _ = index.hyperedge_pool(n_e)
@@ -329,4 +424,4 @@ def readout_pair_mse(x, e, index, n_e, e_order, mlp, target, n_real=None, unit_g
     weights = _mlp_weights(mlp)
     drop = _head_drop("readout_pair_mse", x.device, p_x, mlp, seeds, 2)
     return _ReadoutPairMse.apply(x, e, index.pool.rowptr, he_pool, e_order.contiguous(), n_graphs, n_real, target,
-                                 mlp.normalizations[1].eps, unit_grad, weights, drop, *weights)
+                                 mlp.normalizations[1].eps, unit_grad, weights, drop, loss, *weights)

@@ -112,6 +112,17 @@ class _Averaged:
         return sd
 
 
+def _torch_loss(kind: str, beta: float) -> Callable:
+    """The ``torch.nn.functional`` loss of ``TrainStep(loss=kind, loss_beta=beta)`` as f(pred, target)."""
+    if kind == "mse":
+        return F.mse_loss
+    if kind == "l1":
+        return F.l1_loss
+    if kind == "smooth_l1":
+        return lambda pred, target: F.smooth_l1_loss(pred, target, beta=beta)
+    return lambda pred, target: F.huber_loss(pred, target, delta=beta)
+
+
 class TrainStep(_Averaged):
     """``loss = step(data)``; ``data.y`` is the target.  Model-agnostic (the gloo tests drive it
     with the CPU oracle, the GPU path with the HIP models)."""
@@ -119,8 +130,11 @@ class TrainStep(_Averaged):
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, on_batch: Optional[Callable] = None,
                  clip_gnorm: Optional[float] = None, loss_readout: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
-        """``clip_gnorm``: clip the rank-averaged gradient by its global L2 norm before the update
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, loss: str = "mse", loss_beta: float = 1.0):
+        """``loss`` / ``loss_beta``: the training loss -- "mse" (the reference's, main.py:49-63), "l1", "smooth_l1" (``loss_beta``
+        its beta >= 0) or "huber" (``loss_beta`` its delta > 0); "mse" and "l1" ignore ``loss_beta``.  Checked by
+        ``ops.loss_spec`` and fixed at construction; the step calls the matching ``torch.nn.functional`` loss.
+        ``clip_gnorm``: clip the rank-averaged gradient by its global L2 norm before the update
         (``torch.nn.utils.clip_grad_norm_``; the reference's ``--clip_gnorm``, main.py:175, which its Trainer never
         receives -- so the default, and the reference's behaviour, is off).  ``loss_readout``: keep {sum, count} of the
         steps' losses in ``loss_sum``, 2 doubles on the model's device (a GPU), added to by one launch behind every step's
@@ -131,6 +145,9 @@ class TrainStep(_Averaged):
         min(ema_decay, (1 + t) / (10 + t)).  ``averaged()`` exchanges the ``p.data`` of the live parameters with the shadows;
         ``ema_state_dict()`` returns the averaged state.  ``None``: no shadows, the step of before."""
         self.model = model
+        from .ops.readout import loss_spec
+        self.loss, self.loss_beta, self.loss_spec = loss, float(loss_beta), loss_spec(loss, loss_beta)
+        self._loss_fn = _torch_loss(loss, self.loss_beta)
         self.ema_decay, self.ema_warmup = _checked_decay("TrainStep", ema_decay), bool(ema_warmup)
         self.ema_shadows: Optional[list] = None         # one tensor per live parameter, in self.flat.params' order
         self.ema_updates = 0                            # t of the last update of the average
@@ -150,7 +167,7 @@ class TrainStep(_Averaged):
         """Discover which parameters receive a gradient, then lay out the flat buffer."""
         for p in self.model.parameters():
             p.grad = None
-        loss = F.mse_loss(self.model(data), data.y)
+        loss = self._loss_fn(self.model(data), data.y)
         loss.backward()
         live = [p for p in self.model.parameters() if p.grad is not None]
         first = [p.grad.clone() for p in live]
@@ -172,7 +189,7 @@ class TrainStep(_Averaged):
             loss = self._first_step(data)
         else:
             self.flat.zero_()
-            loss = F.mse_loss(self.model(data), data.y)
+            loss = self._loss_fn(self.model(data), data.y)
             loss.backward()
         if self.loss_readout:
             _accumulate_loss(self, loss)
@@ -360,8 +377,13 @@ class GraphedTrainStep(_Averaged):
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, collective: bool = True, keep_grads: bool = False,
                  force_collective: bool = False, graph_collective: bool = True, clip_gnorm: Optional[float] = None,
-                 loss_readout: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False):
-        """``ema_decay`` / ``ema_warmup``: keep an exponential moving average of ``pflat`` (``FlatAdam(ema_decay=..)``: a fifth
+                 loss_readout: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                 loss: str = "mse", loss_beta: float = 1.0):
+        """``loss`` / ``loss_beta``: the training loss, as ``TrainStep``'s -- "mse", "l1", "smooth_l1" (beta) or "huber" (delta).
+        Anything but "mse" travels as an ``ops.loss_spec`` in the head tuple, so the fused read-out heads take their ``sl1`` forms
+        and the other models end in ``ops.regression_loss``: the launch count of the step is that of "mse".  Fixed at
+        construction (beta and scale are kernel arguments of the captured graphs).
+        ``ema_decay`` / ``ema_warmup``: keep an exponential moving average of ``pflat`` (``FlatAdam(ema_decay=..)``: a fifth
         stream of the update launch, no launch more in the step; every rank forms the same average from the same averaged
         gradient, without a collective).  Fixed at construction (kernel arguments of the captured graphs).  ``averaged()``
         then exchanges ``pflat`` and the average in place by ONE launch on the current stream (eqh_swap_f32) and exchanges
@@ -384,6 +406,8 @@ class GraphedTrainStep(_Averaged):
         process group has ONE rank -- how the path is exercised on a one-GPU box.  ``graph_collective=False``: never
         capture the collective (always graph A -> eager all-reduce -> graph B)."""
         self.model, self.lr, self.wd = model, lr, weight_decay
+        from .ops.readout import loss_spec
+        self.loss, self.loss_beta, self.loss_spec = loss, float(loss_beta), loss_spec(loss, loss_beta)
         self.clip_gnorm = clip_gnorm
         self.ema_decay, self.ema_warmup = _checked_decay("GraphedTrainStep", ema_decay), bool(ema_warmup)
         self.loss_readout = bool(loss_readout)
@@ -526,8 +550,12 @@ class GraphedTrainStep(_Averaged):
         if self.fused_head and data.y.is_cuda:
             # pool + output MLP + MSE and their backward in one launch; the gradient that loss.backward()
             # feeds in is the implicit 1, so the head's parameter gradients go straight to the accumulators
+            if self.loss_spec is not None:
+                return self.model(data, head=(data.y, nb, True, self.loss_spec))
             return self.model(data, head=(data.y, nb, True))
         out = self.model(data)[:nb]
+        if self.loss_spec is not None:
+            return ops.regression_loss(out, data.y[:nb], self.loss_spec)
         return ops.mse_loss(out, data.y[:nb]) if out.is_cuda else F.mse_loss(out, data.y[:nb])
 
     def _fwd_bwd(self, data):

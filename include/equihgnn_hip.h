@@ -88,6 +88,14 @@ int eqh_swap_f32(float* a, float* b, int64_t n, void* stream);
 /* Mean-squared-error loss of main.py:36,49-63 and its gradient in one launch: loss[0] = mean((pred - target)^2)
  * over n values, grad[i] = 2 (pred[i] - target[i]) / n.  n <= 65536 (one workgroup; a batch of molecules). */
 int eqh_mse_fwd_bwd(const float* pred, const float* target, int32_t n, float* loss, float* grad, void* stream);
+/* The same launch for the L1 / smooth-L1 / Huber family.  With d = pred[i] - target[i] and a = |d|:
+ *   loss[0] = mean of  scale * (a < beta ? 0.5 d^2 / beta : a - 0.5 beta),
+ *   grad[i] = scale * (a < beta ? d / beta : sign(d)) / n,   sign(0) = 0
+ * (beta = 0, scale = 1: L1; scale = 1: F.smooth_l1_loss(beta); beta = scale = delta: F.huber_loss(delta)).  One workgroup, the
+ * fixed reduction order of eqh_mse_fwd_bwd; n <= 65536.  EQH_ERR_ARG ahead of the launch: a NULL pointer, beta < 0,
+ * scale <= 0, a beta or scale that is not finite. */
+int eqh_smooth_l1_fwd_bwd(const float* pred, const float* target, int32_t n, float beta, float scale, float* loss,
+                          float* grad, void* stream);
 /* An epoch's loss and bootstrap metrics kept in device memory and read once per epoch (main.py:37-42,65-76,90-110:
  * BootStrapper(MeanAbsoluteError / MeanSquaredError, num_bootstraps = 50), Poisson(1) resampling of every update).
  *   eqh_bootstrap_update: one batch of n predictions / targets into `acc`, [3, 64] doubles (rows sum w |e|, sum w e^2,
@@ -1109,6 +1117,18 @@ int hg_readout_mse_drop_f32(const float* x, const int32_t* rowptr, int32_t n_gra
                             float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
                             size_t workspace_bytes, int32_t* state, float p_x, float p_h, const int64_t* seed_x,
                             const int64_t* seed_h1, const int64_t* seed_h2, void* stream);
+/* Both launches with the loss family of eqh_smooth_l1_fwd_bwd (beta, scale) over the first n_real molecules in the place of
+ * the MSE; every other argument, hg_readout_mse_supported and hg_readout_mse_workspace_bytes as above.  EQH_ERR_ARG (checked
+ * first): beta < 0, scale <= 0, a beta or scale that is not finite. */
+int hg_readout_sl1_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C,
+                       int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                       float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
+                       size_t workspace_bytes, int32_t* state, float beta, float scale, void* stream);
+int hg_readout_sl1_drop_f32(const float* x, const int32_t* rowptr, int32_t n_graphs, int32_t n_real, int32_t C,
+                            int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                            float* loss, float* dx, float* const* dweights, int32_t accumulate, void* workspace,
+                            size_t workspace_bytes, int32_t* state, float p_x, float p_h, const int64_t* seed_x,
+                            const int64_t* seed_h1, const int64_t* seed_h2, float beta, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The same head for the paired tail (mhnn.py:58,72, equihnn_fa_former.py:99-101), one launch (csrc/readout_pair.hip):
@@ -1141,6 +1161,19 @@ int hg_readout_pair_mse_drop_f32(const float* x, const int32_t* rowptr, const fl
                                  float* const* dweights, int32_t accumulate, void* workspace, size_t workspace_bytes,
                                  int32_t* state, float p_x, float p_h, const int64_t* seed_x, const int64_t* seed_e,
                                  const int64_t* seed_h1, const int64_t* seed_h2, void* stream);
+/* Both launches with the loss family of eqh_smooth_l1_fwd_bwd (beta, scale) in the place of the MSE, as hg_readout_sl1_*. */
+int hg_readout_pair_sl1_f32(const float* x, const int32_t* rowptr, const float* e, const int32_t* e_rowptr,
+                            const int32_t* e_perm, const int64_t* e_order, int32_t n_e, int32_t n_graphs, int32_t n_real,
+                            int32_t C, int32_t H, const float* const* weights, float eps, const float* target, float* y,
+                            float* loss, float* dx, float* de, float* const* dweights, int32_t accumulate, void* workspace,
+                            size_t workspace_bytes, int32_t* state, float beta, float scale, void* stream);
+int hg_readout_pair_sl1_drop_f32(const float* x, const int32_t* rowptr, const float* e, const int32_t* e_rowptr,
+                                 const int32_t* e_perm, const int64_t* e_order, int32_t n_e, int32_t n_graphs,
+                                 int32_t n_real, int32_t C, int32_t H, const float* const* weights, float eps,
+                                 const float* target, float* y, float* loss, float* dx, float* de,
+                                 float* const* dweights, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                                 int32_t* state, float p_x, float p_h, const int64_t* seed_x, const int64_t* seed_e,
+                                 const int64_t* seed_h1, const int64_t* seed_h2, float beta, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Elementwise passes of FAFormer's SwiGLU MLP (fa_former_layer.py:241-289) and its 8-frame average (:61-120):
