@@ -19,6 +19,9 @@
 //   reads anyway.  eqh_swap_f32 exchanges two flat buffers in place (live parameters <-> their average around an evaluation).
 // eqh_copy_many: up to 64 small device-to-device copies in one launch (gradients that autograd allocated,
 //   packed into the flat gradient buffer).
+// eqh_add_many: the adding form, dst[i] += src[i] on k_copy_many's grid, for a step that accumulates the gradients of several
+//   micro-batches; one more column of workgroups clears a second buffer, as k_adam does (the merged weights' scratch, which
+//   no update clears between two micro-batches).
 // eqh_mse_fwd_bwd / eqh_smooth_l1_fwd_bwd: a batch's loss and its gradient in one launch of one workgroup (k_mse; k_smooth_l1
 //   for the l1 / smooth-l1 / Huber family of loss_family.h).
 #include "common.h"
@@ -473,6 +476,78 @@ extern "C" int eqh_copy_many(int32_t count, const float* const* src, float* cons
         if (most == 0) continue;
         const int by = (int)((most + 4095) / 4096 < 256 ? (most + 4095) / 4096 : 256);  // 16 floats per thread and pass
         hipLaunchKernelGGL(k_copy_many, dim3(m, by), dim3(256), 0, stream, b);
+        EQH_CHECK_LAUNCH();
+    }
+    return EQH_OK;
+}
+
+namespace {
+
+// k_copy_many's adding twin: workgroup column e < b.count adds entry e, column b.count clears zero_also (zero_n floats, a
+// multiple of 4, 16-byte aligned: checked on the host).  64-bit trip variables: an entry may hold up to 2^31 - 1 floats.
+struct AddBatch {
+    const float* src[COPY_MAX];
+    float* dst[COPY_MAX];
+    int n[COPY_MAX];
+    int count;
+    float* zero_also;
+    int64_t zero_n;
+};
+
+__global__ void __launch_bounds__(256) k_add_many(AddBatch b) {
+    const int64_t first = (int64_t)blockIdx.y * 256 + threadIdx.x, stride = (int64_t)gridDim.y * 256;
+    if ((int)blockIdx.x >= b.count) {
+        for (int64_t i = first; i < (b.zero_n >> 2); i += stride) reinterpret_cast<float4*>(b.zero_also)[i] = f4_zero();
+        return;
+    }
+    const float* __restrict__ s = b.src[blockIdx.x];
+    float* __restrict__ d = b.dst[blockIdx.x];
+    const int64_t n = b.n[blockIdx.x];
+    if ((((uintptr_t)s | (uintptr_t)d) & 15) == 0) {  // float4 body, scalar tail
+        const int64_t n4 = n >> 2;
+        for (int64_t i = first; i < n4; i += stride) {
+            const float4 x = reinterpret_cast<const float4*>(s)[i];
+            float4 y = reinterpret_cast<float4*>(d)[i];
+            y.x += x.x; y.y += x.y; y.z += x.z; y.w += x.w;
+            reinterpret_cast<float4*>(d)[i] = y;
+        }
+        if (blockIdx.y == 0)
+            for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += 256) d[i] += s[i];
+    } else {
+        for (int64_t i = first; i < n; i += stride) d[i] += s[i];
+    }
+}
+
+}  // namespace
+
+// The adding form of eqh_copy_many, with k_adam's second job: the first launch also clears zero_also.  Every argument is
+// checked before the first launch.
+extern "C" int eqh_add_many(int32_t count, const float* const* src, float* const* dst, const int64_t* n,
+                            float* zero_also, int64_t zero_also_n, void* stream_) {
+    if (count < 0 || (count > 0 && (!src || !dst || !n))) return EQH_ERR_ARG;
+    if (zero_also_n < 0 || (zero_also_n & 3) || (zero_also_n > 0 && !zero_also) || !eqh_aligned16(zero_also)) return EQH_ERR_ARG;
+    for (int i = 0; i < count; ++i)
+        if (n[i] < 0 || n[i] >= ((int64_t)1 << 31) || (n[i] > 0 && (!src[i] || !dst[i]))) return EQH_ERR_ARG;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int64_t zero_n = zero_also_n;
+    for (int i0 = 0; i0 < count || zero_n > 0; i0 += COPY_MAX) {
+        AddBatch b;
+        const int m = (count - i0 < COPY_MAX) ? (count - i0 > 0 ? count - i0 : 0) : COPY_MAX;
+        int64_t most = zero_n;
+        for (int i = 0; i < m; ++i) {
+            b.src[i] = src[i0 + i];
+            b.dst[i] = dst[i0 + i];
+            b.n[i] = (int)n[i0 + i];
+            if (n[i0 + i] > most) most = n[i0 + i];
+        }
+        b.count = m;
+        b.zero_also = zero_also;
+        b.zero_n = zero_n;
+        const bool clear = zero_n > 0;
+        zero_n = 0;
+        if (most == 0) continue;
+        const int by = (int)((most + 4095) / 4096 < 256 ? (most + 4095) / 4096 : 256);  // 16 floats per thread and pass
+        hipLaunchKernelGGL(k_add_many, dim3(m + (clear ? 1 : 0), by), dim3(256), 0, stream, b);
         EQH_CHECK_LAUNCH();
     }
     return EQH_OK;

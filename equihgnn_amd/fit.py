@@ -33,7 +33,7 @@ import weakref
 import atexit
 
 from .batch import HBatch, HMol, MolStore, bucket_sizes, collate, shard_indices, shard_permutation
-from .trainer import GraphedTrainStep, TrainStep, _checked_decay, _world, with_next
+from .trainer import GraphedTrainStep, TrainStep, _checked_accum, _checked_decay, _world, with_next
 
 
 # ------------------------------------------------------------------------------------------------
@@ -582,8 +582,13 @@ class Fitter:
                  std: Optional[float] = None, patience_lr: int = 10, patience_stop: int = 50,
                  step_factory: Callable = TrainStep, metric_seed: int = 0, clip_gnorm: Optional[float] = None,
                  device_metrics: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                 loss: str = "mse", loss_beta: float = 1.0):
-        """``loss`` / ``loss_beta``: the training loss of the step (``TrainStep`` / ``GraphedTrainStep(loss=.., loss_beta=..)``:
+                 loss: str = "mse", loss_beta: float = 1.0, accum_steps: int = 1):
+        """``accum_steps`` = k: one optimiser step per k training batches (``TrainStep`` / ``GraphedTrainStep(accum_steps=k)``;
+        handed to ``step_factory`` only when k > 1, as ``clip_gnorm``).  After an epoch's last training batch, before the
+        validation pass, ``step.flush()`` closes a group the epoch left open.  ``train_loss`` stays the mean over the
+        batches; every history row then carries ``optimizer_steps``, the updates of that epoch (without accumulation the
+        rows are those of before: every batch is an optimiser step).
+        ``loss`` / ``loss_beta``: the training loss of the step (``TrainStep`` / ``GraphedTrainStep(loss=.., loss_beta=..)``:
         "mse", "l1", "smooth_l1" with its beta, "huber" with its delta), checked here by ``ops.loss_spec`` and handed to
         ``step_factory`` only when it is not "mse", so a factory without the keywords keeps working.  ``train_loss`` in the
         history is then that loss; validation, the scheduler, early stopping and ``best_state`` stay on ``mae_mean``.
@@ -608,6 +613,9 @@ class Fitter:
         self.device_metrics = bool(device_metrics)
         self.host_reads = 0
         extra = {} if clip_gnorm is None else {"clip_gnorm": clip_gnorm}
+        self.accum_steps = _checked_accum("Fitter", accum_steps)
+        if self.accum_steps > 1:
+            extra["accum_steps"] = self.accum_steps
         from .ops.readout import loss_spec
         loss_spec(loss, loss_beta)
         self.loss, self.loss_beta = loss, float(loss_beta)
@@ -689,6 +697,7 @@ class Fitter:
         bad = 0
         for epoch in range(epochs):
             tot, n = 0.0, 0
+            updates0 = getattr(self.step, "updates", 0)
             # device_metrics: the step adds its loss to its own ``loss_sum`` (loss_readout); nothing is read per batch, so the
             # host goes on to stage batch t + 1 while step t runs
             keep = (lambda loss: 0.0) if self.device_metrics else self._loss_to_host
@@ -700,6 +709,8 @@ class Fitter:
                 for data in train_loader:
                     tot += keep(self.step.step(data))
                     n += 1
+            if self.accum_steps > 1:
+                self.step.flush()               # a group the epoch left open: its update runs before the validation pass
             if self.device_metrics and n:       # ONE read of {sum, count} per epoch, then the pair starts again
                 tot, seen = self.step.loss_sum.tolist()
                 self.host_reads += 1
@@ -715,6 +726,8 @@ class Fitter:
             lr_now = self.step.opt.param_groups[0]["lr"] if self.step.opt is not None else self.lr
             res.history.append({"epoch": epoch, "train_loss": tot / max(n, 1), "lr": float(lr_now),
                                 **{"val_" + k: v for k, v in val.items()}})
+            if self.accum_steps > 1:            # (without accumulation every batch is an optimiser step: the rows of before)
+                res.history[-1].update(optimizer_steps=int(self.step.updates - updates0))
             readout = getattr(self.step, "grad_norm", None) if self.clip_gnorm is not None else None
             if readout is not None:         # ONE read of the step's readout per epoch, then its running pair starts again
                 _, _, seen, clipped = readout.tolist()

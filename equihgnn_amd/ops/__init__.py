@@ -49,7 +49,7 @@ from .panel import (  # noqa: F401
 )
 from .grads import (  # noqa: F401
     GradFan, _FanSource, fanout, WGRAD_ON_SIDE_STREAM, _WGRAD_STREAMS, wgrad_stream, join_wgrad_stream,
-    defer_begin, wgrad_batch, colsum_batch, defer_flush, copy_many, colsum, USE_WGRAD_KERNEL, DEFER_WGRAD,
+    defer_begin, wgrad_batch, colsum_batch, defer_flush, copy_many, add_many, colsum, USE_WGRAD_KERNEL, DEFER_WGRAD,
     _wgrad_shape_ok, _wgrad_ok, _wgrad_deferred, wgrad, _linear_weight_grad, MergedScratch, _merged_acc,
 )
 from .linears import (  # noqa: F401

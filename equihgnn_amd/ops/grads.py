@@ -236,6 +236,24 @@ def copy_many(dsts, srcs):
                                       i64(*[d.numel() for d in dsts]), _stream(dsts[0].device)), "eqh_copy_many")
 
 
+def add_many(dsts, srcs, zero_also=None):
+    """dst[i].add_(src[i]) for lists of contiguous fp32 device tensors, in one launch (eqh_add_many), which also clears
+    ``zero_also`` (a contiguous fp32 tensor of a multiple of 4 elements) when one is given -- also with empty lists."""
+    n = len(dsts)
+    if n == 0 and zero_also is None:
+        return
+    srcs = [_f32c(t) for t in srcs]
+    vp, i64 = ctypes.c_void_p * n, ctypes.c_int64 * n
+    for d, t in zip(dsts, srcs):
+        assert d.is_contiguous() and d.numel() == t.numel() and d.dtype == torch.float32
+    if zero_also is not None:
+        assert zero_also.is_contiguous() and zero_also.dtype == torch.float32
+    dev = dsts[0].device if n else zero_also.device
+    hip.check(hip.lib().eqh_add_many(n, vp(*[t.data_ptr() for t in srcs]), vp(*[d.data_ptr() for d in dsts]),
+                                     i64(*[d.numel() for d in dsts]), _ptr(zero_also) if zero_also is not None else None,
+                                     zero_also.numel() if zero_also is not None else 0, _stream(dev)), "eqh_add_many")
+
+
 def colsum(x, rowptr=None, weight_mode: int = 0, into=None, scale: float = 1.0):
     """scale * sum_r w_r x[r, :] for a 2-D fp32 matrix through hg_colsum_f32 (bias gradients).  ``rowptr`` +
     ``weight_mode`` (1: [row non-empty], 2: row length) give the row weights; ``into`` is an accumulator

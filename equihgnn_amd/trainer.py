@@ -60,6 +60,13 @@ def _checked_decay(who: str, decay) -> Optional[float]:
     return d
 
 
+def _checked_accum(who: str, k) -> int:
+    """``accum_steps`` as an integer >= 1 (a bool, a float or a string is not one)."""
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1:
+        raise ValueError(f"{who}: accum_steps must be an integer >= 1 (got {k!r})")
+    return k
+
+
 def ema_decay_at(decay: float, t: int, warmup: bool) -> float:
     """d_t of update t = 1, 2, ..: ``decay``, or with ``warmup`` min(decay, (1 + t) / (10 + t)) (torch_ema / timm)."""
     return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
@@ -130,8 +137,17 @@ class TrainStep(_Averaged):
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, on_batch: Optional[Callable] = None,
                  clip_gnorm: Optional[float] = None, loss_readout: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = False, loss: str = "mse", loss_beta: float = 1.0):
-        """``loss`` / ``loss_beta``: the training loss -- "mse" (the reference's, main.py:49-63), "l1", "smooth_l1" (``loss_beta``
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, loss: str = "mse", loss_beta: float = 1.0,
+                 accum_steps: int = 1):
+        """``accum_steps`` = k: one optimiser step per k calls of ``step()`` (Lightning's ``accumulate_grad_batches``, DDP under
+        ``no_sync``).  Every call is one micro-batch and returns that micro-batch's own loss; its gradient is added into the
+        flat buffer, which is cleared only in front of a group's first micro-batch.  The k-th call closes the group: ONE
+        in-place multiply of the buffer by 1 / k, then the rank average (one collective per group), clip, update and average
+        of the weights, once.  ``flush()`` closes an open group early with the same 1 / k (the end of an epoch); ``micro`` is
+        the position inside the group, ``updates`` the number of optimiser steps taken.  The weights do not move inside a
+        group, so ``averaged()`` and ``ema_state_dict()`` never see a half-applied state and need no refusal of their own.
+        k = 1 (default): the step of before, without the multiply.
+        ``loss`` / ``loss_beta``: the training loss -- "mse" (the reference's, main.py:49-63), "l1", "smooth_l1" (``loss_beta``
         its beta >= 0) or "huber" (``loss_beta`` its delta > 0); "mse" and "l1" ignore ``loss_beta``.  Checked by
         ``ops.loss_spec`` and fixed at construction; the step calls the matching ``torch.nn.functional`` loss.
         ``clip_gnorm``: clip the rank-averaged gradient by its global L2 norm before the update
@@ -145,6 +161,9 @@ class TrainStep(_Averaged):
         min(ema_decay, (1 + t) / (10 + t)).  ``averaged()`` exchanges the ``p.data`` of the live parameters with the shadows;
         ``ema_state_dict()`` returns the averaged state.  ``None``: no shadows, the step of before."""
         self.model = model
+        self.accum_steps = _checked_accum("TrainStep", accum_steps)
+        self.micro = 0                                  # micro-batches in the open group (0: none is open)
+        self.updates = 0                                # optimiser steps taken
         from .ops.readout import loss_spec
         self.loss, self.loss_beta, self.loss_spec = loss, float(loss_beta), loss_spec(loss, loss_beta)
         self._loss_fn = _torch_loss(loss, self.loss_beta)
@@ -188,18 +207,36 @@ class TrainStep(_Averaged):
         if self.flat is None:
             loss = self._first_step(data)
         else:
-            self.flat.zero_()
+            if self.micro == 0:
+                self.flat.zero_()
             loss = self._loss_fn(self.model(data), data.y)
-            loss.backward()
+            loss.backward()         # (into the views of the flat buffer: added to what the group's earlier micro-batches left)
         if self.loss_readout:
             _accumulate_loss(self, loss)
+        self.micro += 1
+        if self.micro == self.accum_steps:
+            self._close_group()
+        return loss.detach()
+
+    def _close_group(self):
+        if self.accum_steps > 1:
+            self.flat.flat.mul_(1.0 / self.accum_steps)
         self.flat.all_reduce_mean()
         if self.clip_gnorm is not None:
             self._clip()
         self.opt.step()
         if self.ema_decay is not None:
             self._ema_update()
-        return loss.detach()
+        self.micro = 0
+        self.updates += 1
+
+    def flush(self):
+        """Close an open group early: the update runs on what the group holds, still scaled 1 / ``accum_steps``.  Nothing
+        when no group is open."""
+        if self._averaging:
+            raise RuntimeError("TrainStep.flush(): inside averaged() the parameters hold the average, not the live weights")
+        if self.micro:
+            self._close_group()
 
     @torch.no_grad()
     def _ema_update(self):
@@ -374,12 +411,27 @@ class GraphedTrainStep(_Averaged):
     and the fused Adam therefore each see a single tensor.
     """
 
+    accum_steps = 1     # (micro-batches per optimiser step; set by __init__)
+
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, collective: bool = True, keep_grads: bool = False,
                  force_collective: bool = False, graph_collective: bool = True, clip_gnorm: Optional[float] = None,
                  loss_readout: bool = False, ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                 loss: str = "mse", loss_beta: float = 1.0):
-        """``loss`` / ``loss_beta``: the training loss, as ``TrainStep``'s -- "mse", "l1", "smooth_l1" (beta) or "huber" (delta).
+                 loss: str = "mse", loss_beta: float = 1.0, accum_steps: int = 1):
+        """``accum_steps`` = k > 1: one optimiser step per k calls of ``step()``, as ``TrainStep(accum_steps=k)``.  Two kinds of
+        graph: one ACCUMULATE graph per bucket -- the backward graph of the split form, closed by eqh_add_many instead of
+        eqh_copy_many: the gradients autograd allocates are ADDED into their ``gflat`` slots, and the same launch clears the
+        merged weights' scratch, which no update clears between two micro-batches -- and ONE UPDATE graph shared by all
+        buckets: ``opt.step()`` (with ``clip_gnorm`` / ``ema_decay`` their forms of it) behind the gradient all-reduce, which is
+        its first node where the backend can be captured (``collective_mode``, settled among the ranks at that capture) and
+        runs eagerly in front of it otherwise.  A group's last micro-step replays both; the gradient scale of the update is
+        1 / (k * world).  The first group's update runs eagerly, as the first step's does for k = 1; the update graph is
+        captured at the next one.  ``flush()`` closes an open group early with the same scale; ``micro`` is the position
+        inside the group, ``updates`` the optimiser steps taken (the device counter of ``FlatAdam`` agrees).  With
+        ``keep_grads`` ``gflat`` holds the unscaled sum over the group after its last micro-step, and ``step()`` clears it in
+        front of a group's first micro-step.  The weights do not move inside a group: ``averaged()`` and
+        ``ema_state_dict()`` need no refusal of their own while one is open.  k = 1 (default): the graphs and launches of before.
+        ``loss`` / ``loss_beta``: the training loss, as ``TrainStep``'s -- "mse", "l1", "smooth_l1" (beta) or "huber" (delta).
         Anything but "mse" travels as an ``ops.loss_spec`` in the head tuple, so the fused read-out heads take their ``sl1`` forms
         and the other models end in ``ops.regression_loss``: the launch count of the step is that of "mse".  Fixed at
         construction (beta and scale are kernel arguments of the captured graphs).
@@ -406,6 +458,10 @@ class GraphedTrainStep(_Averaged):
         process group has ONE rank -- how the path is exercised on a one-GPU box.  ``graph_collective=False``: never
         capture the collective (always graph A -> eager all-reduce -> graph B)."""
         self.model, self.lr, self.wd = model, lr, weight_decay
+        self.accum_steps = _checked_accum("GraphedTrainStep", accum_steps)
+        self.micro = 0                      # micro-batches in the open group (0: none is open)
+        self.updates = 0                    # optimiser steps taken
+        self._g_update = None               # accum_steps > 1: the update graph shared by all buckets (_capture_update)
         from .ops.readout import loss_spec
         self.loss, self.loss_beta, self.loss_spec = loss, float(loss_beta), loss_spec(loss, loss_beta)
         self.clip_gnorm = clip_gnorm
@@ -510,6 +566,7 @@ class GraphedTrainStep(_Averaged):
                 del p._eqh_gbuf
         self.gb_params, self.slots, self.live = [], {}, None
         self._alt_slots, self._cal = None, None
+        self._g_update = None
 
     def _buffer_snapshot(self):
         return [b.detach().clone() for b in self.model.buffers()]
@@ -604,7 +661,19 @@ class GraphedTrainStep(_Averaged):
             p.grad = p._eqh_gbuf
         if self.gflat is None:
             return
-        if self.others:
+        if self.accum_steps > 1:
+            # the adding form: the slots hold what the group's earlier micro-batches left.  The same launch clears the merged
+            # weights' scratch, handed on to the parameters by defer_flush just now: the next micro-batch accumulates into zeros
+            from . import ops
+            scratch = None if self.keep_grads else self.scratch.buf
+            grads = [p.grad for p in self.others]
+            if scratch is not None:
+                lo, hi = scratch.data_ptr(), scratch.data_ptr() + 4 * scratch.numel()
+                if any(lo <= g.data_ptr() < hi for g in grads):
+                    raise RuntimeError("GraphedTrainStep: a parameter's gradient lies inside the merged weights' scratch, "
+                                       "which the adding launch clears")
+            ops.add_many(self.other_slots, grads, zero_also=scratch)
+        elif self.others:
             from . import ops
             ops.copy_many(self.other_slots, [p.grad for p in self.others])
 
@@ -678,6 +747,13 @@ class GraphedTrainStep(_Averaged):
                             ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
         self.opt.zero_grad_in_step = not self.keep_grads
         self.opt.zero_also = lambda: self.scratch.buf
+        if self.accum_steps > 1:
+            # micro-step 1 of group 1: gflat holds this micro-batch's gradient and nothing is updated.  The group's close
+            # (_close_group, eager for the first group) makes the all-reduce that creates the communicator
+            self.opt.grad_scale = 1.0 / (self.accum_steps * self._w())
+            self.micro = 1
+            return loss.detach()
+        self.updates += 1
         if self._multi():
             dist.all_reduce(self.gflat, op=dist.ReduceOp.SUM)     # (eager: also creates the communicator before any capture)
             self.opt.grad_scale = 1.0 / self._w()     # the average is folded into the update
@@ -690,9 +766,11 @@ class GraphedTrainStep(_Averaged):
         split form.  (A method so that the two-rank tests can stand in a backend that refuses on one rank.)"""
         dist.all_reduce(self.gflat, op=dist.ReduceOp.SUM)
 
-    def _capture_pass(self, static, in_graph: bool):
+    def _capture_pass(self, static, in_graph: bool, update: bool = True):
         """One capture of the step for the static batch.  ``in_graph``: buffer broadcast, all-reduce and update are nodes of
-        the one graph; else the graph ends after the backward pass and the update is a second graph (g_opt).  Raises
+        the one graph; else the graph ends after the backward pass and the update is a second graph (g_opt).
+        ``update=False`` (with ``in_graph=False``; accum_steps > 1): the accumulate graph -- the backward pass alone, whatever
+        the number of ranks: no update in it, no g_opt beside it, and no clearing of ``wflat`` at its head.  Raises
         ``CollectiveCaptureRefused`` when -- and only when -- a captured collective call failed; an error of a kernel launch
         or of an argument check anywhere else in the pass propagates as itself (the split form would hit it too)."""
         from . import ops
@@ -716,7 +794,7 @@ class GraphedTrainStep(_Averaged):
                     except RuntimeError as exc:
                         refused = exc
                 if refused is None:
-                    if self.wflat is not None and self.keep_grads:
+                    if self.wflat is not None and self.keep_grads and update:
                         self.wflat.zero_()
                     sig = self._signal if getattr(static, "_index_is_live", False) else None
                     if sig is not None:
@@ -738,7 +816,7 @@ class GraphedTrainStep(_Averaged):
                             self._captured_all_reduce()
                         except RuntimeError as exc:
                             refused = exc
-                    if refused is None and (in_graph or not multi):
+                    if update and refused is None and (in_graph or not multi):
                         self.opt.step()     # nothing the host must do between backward and update: one graph, one launch
         except RuntimeError:
             if refused is None:
@@ -747,7 +825,7 @@ class GraphedTrainStep(_Averaged):
         if refused is not None:
             raise CollectiveCaptureRefused(f"{type(refused).__name__}: {refused}") from refused
         g_opt = None
-        if multi and not in_graph:
+        if update and multi and not in_graph:
             g_opt = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g_opt, capture_error_mode="thread_local"):
                 self.opt.step()
@@ -770,6 +848,9 @@ class GraphedTrainStep(_Averaged):
         # segfaults on ROCm 7.2): collect them first (a capture is rare and costs ~0.3 s anyway)
         import gc
         gc.collect()
+        # accum_steps > 1: a bucket first met in the middle of a group -- the warm-up passes below clear wflat and write
+        # gradients of their own over what the group has summed so far: set it aside, put it back behind the capture
+        held = self.gflat.clone() if self.accum_steps > 1 else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         snap = self._buffer_snapshot()
@@ -796,6 +877,12 @@ class GraphedTrainStep(_Averaged):
         self._signal_reached = self._signal_name is not None
         self.scratch.freeze()          # its address is about to become part of a graph
         prefetch = self._capture_index(static) if self._prefetch_on else None
+        if held is not None:
+            # the accumulate graph: the backward pass alone on every rank; the collective belongs to the update graph
+            g_bwd, _, loss = self._capture_pass(static, False, update=False)
+            self.gflat.copy_(held)      # (the scratch is empty already: the adding launch of every pass clears it)
+            return {"static": static, "bwd": g_bwd, "opt": None, "loss": loss, "mode": "split" if multi else "none",
+                    "prefetch": prefetch}
         mode = "none"
         if multi:
             mode = "in_graph" if (self.graph_collective and dist.get_backend() in self.in_graph_backends
@@ -907,6 +994,84 @@ class GraphedTrainStep(_Averaged):
         return {"staged": staged, "g_index": g_index, "ix_staged": ix_staged, "live": live, "dsts": dsts, "srcs": srcs,
                 "stream": stream, "free": free, "ready": None, "ready_ev": ready, "holds": None, "light": light}
 
+    def _capture_update_pass(self, in_graph: bool):
+        """One capture of the update graph (accum_steps > 1): ``opt.step()`` -- the sum-of-squares launch and the clip form with
+        ``clip_gnorm``, the EMA form with ``ema_decay`` -- behind the gradient all-reduce when ``in_graph``.  Raises
+        ``CollectiveCaptureRefused`` when, and only when, the captured collective call failed (as ``_capture_pass``)."""
+        g = torch.cuda.CUDAGraph()
+        refused = None
+        try:
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                if in_graph:
+                    try:
+                        self._captured_all_reduce()
+                    except RuntimeError as exc:
+                        refused = exc
+                if refused is None:
+                    self.opt.step()
+        except RuntimeError:
+            if refused is None:
+                raise
+        if refused is not None:
+            raise CollectiveCaptureRefused(f"{type(refused).__name__}: {refused}") from refused
+        return g
+
+    def _capture_update(self):
+        """The update graph shared by all buckets, captured at the second close of a group (the first ran eagerly: every
+        launch of the update and the communicator exist).  The ranks settle ``collective_mode`` here as ``_capture`` does
+        for k = 1: "in_graph" only if every rank captured the collective, else the all-reduce stays in front of the graph."""
+        import gc
+        gc.collect()
+        multi = self._multi()
+        mode = "none"
+        if multi:
+            mode = "in_graph" if (self.graph_collective and dist.get_backend() in self.in_graph_backends) else "split"
+        g = None
+        if mode == "in_graph":
+            try:
+                g = self._capture_update_pass(True)
+            except CollectiveCaptureRefused as exc:
+                self.capture_error = str(exc)
+                torch.cuda.synchronize()
+                mode = "split"
+                gc.collect()        # (the abandoned graph is destroyed now, not inside the next capture)
+        if multi and not self._mode_agreed:
+            agreed = self._agree_on_mode(mode)
+            self._mode_agreed = True
+            if agreed != mode:
+                self.capture_error = "another rank could not capture the collective"
+                g, mode = None, agreed
+                gc.collect()
+        if g is None:
+            g = self._capture_update_pass(False)
+        self.collective_mode = mode
+        self._g_update = g
+
+    def _close_group(self):
+        """accum_steps > 1: the one collective and the one update of a group, on the sum ``gflat`` holds (scaled
+        1 / (accum_steps * world) inside the update).  Eager for the first group, the replayed update graph from then on."""
+        if self._g_update is None and self.updates > 0:
+            self._capture_update()
+        self.opt.sync_lr()
+        if self._g_update is None:
+            if self._multi():
+                dist.all_reduce(self.gflat, op=dist.ReduceOp.SUM)
+            self.opt.step()
+        else:
+            if self.collective_mode == "split":
+                dist.all_reduce(self.gflat, op=dist.ReduceOp.SUM)
+            self._g_update.replay()
+        self.micro = 0
+        self.updates += 1
+
+    def flush(self):
+        """Close an open group early (the end of an epoch): the update runs on what the group holds, with the scale of a
+        full group.  Nothing when no group is open (always so for accum_steps = 1)."""
+        if self._averaging:
+            raise RuntimeError("GraphedTrainStep.flush(): inside averaged() pflat holds the average, not the live weights")
+        if self.micro:
+            self._close_group()
+
     @property
     def ema_flat(self) -> Optional[torch.Tensor]:
         """With ``ema_decay``: the average of ``pflat``, same length and element order (the optimiser's ``state["ema"]``);
@@ -955,6 +1120,12 @@ class GraphedTrainStep(_Averaged):
 
     CAL_WARM, CAL_STEPS = 3, 12          # replays before a timed window, steps in it
 
+    def _cal_steps(self) -> int:
+        """Steps in a timed window: CAL_STEPS, rounded up to whole groups of ``accum_steps`` -- any run of whole groups holds
+        the same number of update launches, wherever in a group it starts, so both forms are timed over the same work."""
+        k = self.accum_steps
+        return (self.CAL_STEPS + k - 1) // k * k
+
     def _calibrate(self, key):
         """Auto policy, called at the head of every graphed step until the decision: per form, one capture step, CAL_WARM
         replays, then CAL_STEPS steps between two device synchronisations (wall clock: the two streams overlap, so no single
@@ -972,12 +1143,13 @@ class GraphedTrainStep(_Averaged):
             return
         c["n"] += 1
         first_timed = 1 + self.CAL_WARM + 1
+        steps = self._cal_steps()
         if c["n"] == first_timed:
             torch.cuda.synchronize()
             c["t0"] = time.perf_counter()
-        elif c["n"] == first_timed + self.CAL_STEPS:
+        elif c["n"] == first_timed + steps:
             torch.cuda.synchronize()
-            c["t"][c["form"]] = (time.perf_counter() - c["t0"]) / self.CAL_STEPS * 1e3
+            c["t"][c["form"]] = (time.perf_counter() - c["t0"]) / steps * 1e3
             if c["form"] == "built_ahead":  # now the other form: every bucket is captured again, the graphs so far are kept aside
                 self._alt_slots, self.slots = self.slots, {}
                 self._prefetch_on = False
@@ -997,7 +1169,7 @@ class GraphedTrainStep(_Averaged):
         gc.collect()                         # (dropped graphs are destroyed now, not inside a later capture)
         self.calibration = {"built_ahead_ms": None if t is None else round(t["built_ahead"], 4),
                             "in_step_ms": None if t is None else round(t["in_step"], 4),
-                            "steps_per_window": self.CAL_STEPS, "chosen": "built_ahead" if ahead else "in_step"}
+                            "steps_per_window": self._cal_steps(), "chosen": "built_ahead" if ahead else "in_step"}
         self._cal = None
 
     @staticmethod
@@ -1096,12 +1268,20 @@ class GraphedTrainStep(_Averaged):
         self.opt.sync_lr()
         if self._has_buffers and slot["mode"] != "in_graph":
             self.sync_buffers()
+        if self.accum_steps > 1 and self.keep_grads and self.micro == 0:
+            self.gflat.zero_()            # (no update clears it: in front of a group's first micro-step, not inside the graph)
         slot["bwd"].replay()
         if pf is not None:
             self._signal.posted += 1      # (one post per replay of a step graph with a live index)
-        if slot["opt"] is not None:
-            dist.all_reduce(self.gflat, op=dist.ReduceOp.SUM)
-            slot["opt"].replay()
+        if self.accum_steps > 1:
+            self.micro += 1
+            if self.micro == self.accum_steps:
+                self._close_group()
+        else:
+            self.updates += 1
+            if slot["opt"] is not None:
+                dist.all_reduce(self.gflat, op=dist.ReduceOp.SUM)
+                slot["opt"].replay()
         if self.loss_readout:
             _accumulate_loss(self, slot["loss"])     # (the replay's static loss scalar, read before the next replay writes it)
         if next_data is not None:

@@ -47,6 +47,14 @@ int eqh_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, 
                   const float* lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                   void* state, int32_t zero_grad, float* zero_also, int64_t zero_also_n, void* stream);
 int eqh_copy_many(int32_t count, const float* const* src, float* const* dst, const int64_t* n, void* stream);
+/* eqh_add_many: the adding form, dst[i][j] += src[i][j] (one fp32 add per element; float4 where both pointers of an entry are
+ * 16-byte aligned, scalar otherwise), for a step that accumulates the gradients of several micro-batches; as eqh_copy_many it
+ * takes any count, 64 entries per launch.  The first launch also clears zero_also[0 .. zero_also_n), as eqh_adam_step does
+ * (accumulators that no update clears between two micro-batches); with count == 0 it does only that.  The ranges must not
+ * overlap.  EQH_ERR_ARG before anything is launched: count < 0, a null list with count > 0, an n[i] outside [0, 2^31), a null
+ * entry with n[i] > 0, zero_also_n < 0 or no multiple of 4, zero_also null with zero_also_n > 0 or not 16-byte aligned. */
+int eqh_add_many(int32_t count, const float* const* src, float* const* dst, const int64_t* n,
+                 float* zero_also, int64_t zero_also_n, void* stream);
 /* The same update behind torch.nn.utils.clip_grad_norm_(max_norm, norm_type = 2, error_if_nonfinite = False) of
  * grad * grad_scale, in two launches and without a host round trip (both capturable):
  *   eqh_grad_sumsq: sum of grad[i]^2 accumulated in double, one double partial per workgroup of a fixed grid into
