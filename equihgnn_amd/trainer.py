@@ -11,7 +11,9 @@ produces (the reference's dead branches, which is why main.py:281 needs
 from __future__ import annotations
 
 import contextlib
+import gc
 import inspect
+import types
 from typing import Callable, Optional
 
 import torch
@@ -21,6 +23,7 @@ import torch.nn.functional as F
 
 from .precision import (get_float32_matmul_precision, get_float32_matmul_precision_edges,
                         get_float32_matmul_precision_panels, get_float32_matmul_precision_wgrads)
+from .prefetch import BucketPrefetch, FormCalibration, batch_token, copy_into_static, static_copy_of
 
 
 def _world() -> int:
@@ -72,15 +75,30 @@ def ema_decay_at(decay: float, t: int, warmup: bool) -> float:
     return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
 
 
-class _Averaged:
-    """What TrainStep and GraphedTrainStep share of the weight average (``ema_decay``): ``averaged()`` and
-    ``ema_state_dict()``.  The step class says how the live and the averaged values change places (``_ema_exchange``, its own
-    inverse) and where each averaged parameter lies (``_ema_of``: id(parameter) -> tensor, live parameters only).  Only
-    parameters that receive a gradient are averaged (the others never change: they are their own average); buffers are not
-    (an evaluation on the average reads the live BatchNorm statistics)."""
+class _StepBase:
+    """What TrainStep and GraphedTrainStep share.  The groups of ``accum_steps`` micro-batches: ``micro``, ``updates``,
+    ``flush()``; the step class closes a group (``_close_group``).  The weight average (``ema_decay``): ``averaged()`` and
+    ``ema_state_dict()``; the step class says how the live and the averaged values change places (``_ema_exchange``, its own
+    inverse), where each averaged parameter lies (``_ema_of``: id(parameter) -> tensor, live parameters only) and what holds
+    the average meanwhile (``_holds``).  Only parameters that receive a gradient are averaged (the others never change: they
+    are their own average); buffers are not (an evaluation on the average reads the live BatchNorm statistics)."""
 
     ema_decay: Optional[float] = None
     _averaging = False
+    accum_steps = 1     # micro-batches per optimiser step
+    micro = 0           # micro-batches in the open group (0: none is open)
+    updates = 0         # optimiser steps taken
+
+    def _refuse_averaging(self, what: str):
+        if self._averaging:
+            raise RuntimeError(f"{type(self).__name__}.{what}: inside averaged() {self._holds} the average, not the live weights")
+
+    def flush(self):
+        """Close an open group early (the end of an epoch): the update runs on what the group holds, still scaled
+        1 / ``accum_steps``.  Nothing when no group is open (always so for accum_steps = 1)."""
+        self._refuse_averaging("flush()")
+        if self.micro:
+            self._close_group()
 
     def _ema_ready(self, what: str):
         if self.ema_decay is None:
@@ -130,9 +148,11 @@ def _torch_loss(kind: str, beta: float) -> Callable:
     return lambda pred, target: F.huber_loss(pred, target, delta=beta)
 
 
-class TrainStep(_Averaged):
+class TrainStep(_StepBase):
     """``loss = step(data)``; ``data.y`` is the target.  Model-agnostic (the gloo tests drive it
     with the CPU oracle, the GPU path with the HIP models)."""
+
+    _holds = "the parameters hold"
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, on_batch: Optional[Callable] = None,
@@ -162,8 +182,6 @@ class TrainStep(_Averaged):
         ``ema_state_dict()`` returns the averaged state.  ``None``: no shadows, the step of before."""
         self.model = model
         self.accum_steps = _checked_accum("TrainStep", accum_steps)
-        self.micro = 0                                  # micro-batches in the open group (0: none is open)
-        self.updates = 0                                # optimiser steps taken
         from .ops.readout import loss_spec
         self.loss, self.loss_beta, self.loss_spec = loss, float(loss_beta), loss_spec(loss, loss_beta)
         self._loss_fn = _torch_loss(loss, self.loss_beta)
@@ -200,8 +218,7 @@ class TrainStep(_Averaged):
         return loss
 
     def step(self, data) -> torch.Tensor:
-        if self._averaging:
-            raise RuntimeError("TrainStep.step(): inside averaged() the parameters hold the average, not the live weights")
+        self._refuse_averaging("step()")
         if self.on_batch is not None:
             self.on_batch(data)
         if self.flat is None:
@@ -229,14 +246,6 @@ class TrainStep(_Averaged):
             self._ema_update()
         self.micro = 0
         self.updates += 1
-
-    def flush(self):
-        """Close an open group early: the update runs on what the group holds, still scaled 1 / ``accum_steps``.  Nothing
-        when no group is open."""
-        if self._averaging:
-            raise RuntimeError("TrainStep.flush(): inside averaged() the parameters hold the average, not the live weights")
-        if self.micro:
-            self._close_group()
 
     @torch.no_grad()
     def _ema_update(self):
@@ -387,10 +396,39 @@ def with_next(batches):
 
 
 class CollectiveCaptureRefused(RuntimeError):
-    """The process-group backend could not record a collective into a hipGraph (raised by GraphedTrainStep._capture_pass)."""
+    """The process-group backend could not record a collective into a hipGraph (raised by ``capture_graph``)."""
 
 
-class GraphedTrainStep(_Averaged):
+def capture_graph(body, graph=None, context=None):
+    """``body(collective)`` captured into a hipGraph: (the graph, what ``body`` returned).  ``collective(call)`` makes a
+    collective call of the process group and says whether the backend recorded it; the body ends at the first False.
+    Raises ``CollectiveCaptureRefused`` when -- and only when -- such a call failed with a RuntimeError (RCCL:
+    ``DistBackendError``); an error of a kernel launch or of an argument check anywhere else in the body propagates as
+    itself (a capture without the collective would hit it too).  ``graph`` / ``context``: stand-ins (tests without a device)."""
+    g = torch.cuda.CUDAGraph() if graph is None else graph
+    refused = []
+
+    def collective(call) -> bool:
+        try:
+            call()
+        except RuntimeError as exc:
+            refused.append(exc)
+        return not refused
+    out = None
+    try:
+        # thread_local: the RCCL watchdog thread may query events while this thread captures
+        with (context or torch.cuda.graph)(g, capture_error_mode="thread_local"):
+            out = body(collective)
+    except RuntimeError:
+        if not refused:
+            raise
+        # (the refused collective also invalidated the capture: ending it raised again -- the refusal is the cause)
+    if refused:
+        raise CollectiveCaptureRefused(f"{type(refused[0]).__name__}: {refused[0]}") from refused[0]
+    return g, out
+
+
+class GraphedTrainStep(_StepBase):
     """TrainStep with the launch-bound part captured in hipGraphs.
 
     forward + MSE + backward (≈700 kernel launches for egnn_equihnns, including the per-batch index
@@ -411,7 +449,8 @@ class GraphedTrainStep(_Averaged):
     and the fused Adam therefore each see a single tensor.
     """
 
-    accum_steps = 1     # (micro-batches per optimiser step; set by __init__)
+    _holds = "pflat holds"
+    CAL_WARM, CAL_STEPS = FormCalibration.CAL_WARM, FormCalibration.CAL_STEPS
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 0.0,
                  broadcast_from_rank0: bool = True, collective: bool = True, keep_grads: bool = False,
@@ -459,8 +498,6 @@ class GraphedTrainStep(_Averaged):
         capture the collective (always graph A -> eager all-reduce -> graph B)."""
         self.model, self.lr, self.wd = model, lr, weight_decay
         self.accum_steps = _checked_accum("GraphedTrainStep", accum_steps)
-        self.micro = 0                      # micro-batches in the open group (0: none is open)
-        self.updates = 0                    # optimiser steps taken
         self._g_update = None               # accum_steps > 1: the update graph shared by all buckets (_capture_update)
         from .ops.readout import loss_spec
         self.loss, self.loss_beta, self.loss_spec = loss, float(loss_beta), loss_spec(loss, loss_beta)
@@ -492,10 +529,10 @@ class GraphedTrainStep(_Averaged):
         self.prefetch_policy = ("off" if os.environ.get("EQH_NO_INDEX_PREFETCH") else
                                 "on" if os.environ.get("EQH_INDEX_PREFETCH") else "auto")
         self._prefetch_on = self.prefetch_policy != "off"
-        self._cal = None                    # calibration state (auto policy): see _calibrate
-        self._alt_slots = None              # the captured steps of the form that is not running, while calibrating
+        self.form_calibration = None        # FormCalibration, from the first graphed step to the decision; holds the other form's graphs
         self.calibration = None             # {"built_ahead_ms": .., "in_step_ms": .., "chosen": ..} once decided
-        self.index_build_us = None          # the index graph alone, timed at the first capture (_capture_index)
+        self.index_build_us = None          # the index graph alone, timed at the latest capture (BucketPrefetch.capture)
+        self._prefetch_stream = None        # the side stream the buckets' index graphs replay on
         self.signal_in_model = not os.environ.get("EQH_PREFETCH_AT_HEAD")    # start the next index at the model's ops.signal_point()
         # which of the marked points releases it.  Measured at the BASELINE batch (same box, ms per step): index at the head
         # of the step graph 1.137; built ahead and released at the step's head 1.138 (it then competes with the chip-filling
@@ -565,7 +602,7 @@ class GraphedTrainStep(_Averaged):
             if hasattr(p, "_eqh_gbuf"):
                 del p._eqh_gbuf
         self.gb_params, self.slots, self.live = [], {}, None
-        self._alt_slots, self._cal = None, None
+        self.form_calibration = None
         self._g_update = None
 
     def _buffer_snapshot(self):
@@ -771,59 +808,44 @@ class GraphedTrainStep(_Averaged):
         the one graph; else the graph ends after the backward pass and the update is a second graph (g_opt).
         ``update=False`` (with ``in_graph=False``; accum_steps > 1): the accumulate graph -- the backward pass alone, whatever
         the number of ranks: no update in it, no g_opt beside it, and no clearing of ``wflat`` at its head.  Raises
-        ``CollectiveCaptureRefused`` when -- and only when -- a captured collective call failed; an error of a kernel launch
-        or of an argument check anywhere else in the pass propagates as itself (the split form would hit it too)."""
+        ``CollectiveCaptureRefused`` as ``capture_graph`` does."""
         from . import ops
         multi = self._multi()
         for p in self.model.parameters():
             p.grad = None
-        g_bwd = torch.cuda.CUDAGraph()
         tl = ops.TIMELINE            # bench.py's in-graph kernel timing: only the captured pass is recorded
         if tl is not None:
             tl.reset()
-        refused = None
-        try:
-            # thread_local: the RCCL watchdog thread may query events while this thread captures
-            with torch.cuda.graph(g_bwd, capture_error_mode="thread_local"):
-                if tl is not None:
-                    for _ in range(4):
-                        tl.pair("stamp_pair")
-                if in_graph and self._has_buffers:
-                    try:
-                        self.sync_buffers()
-                    except RuntimeError as exc:
-                        refused = exc
-                if refused is None:
-                    if self.wflat is not None and self.keep_grads and update:
-                        self.wflat.zero_()
-                    sig = self._signal if getattr(static, "_index_is_live", False) else None
-                    if sig is not None:
-                        # the post that releases the NEXT batch's index build: where the model marks it (ops.signal_point:
-                        # behind the EGNN edge kernel, when the chip stops being full), else at the head of the step
-                        sig.armed, sig.at = True, self._signal_name
-                        ops.SIGNAL = sig
-                        if not (self.signal_in_model and self._signal_reached):
-                            sig.post()
-                    try:
-                        loss = self._loss_backward(static)
-                    finally:
-                        if sig is not None:
-                            ops.SIGNAL = None
-                            if sig.armed:       # (cannot happen after the probe; a step without its post would stall the next index build until the wait's timeout)
-                                sig.post()
-                    if in_graph:
-                        try:
-                            self._captured_all_reduce()
-                        except RuntimeError as exc:
-                            refused = exc
-                    if update and refused is None and (in_graph or not multi):
-                        self.opt.step()     # nothing the host must do between backward and update: one graph, one launch
-        except RuntimeError:
-            if refused is None:
-                raise
-            # (the refused collective also invalidated the capture: ending it raised again -- the refusal is the cause)
-        if refused is not None:
-            raise CollectiveCaptureRefused(f"{type(refused).__name__}: {refused}") from refused
+
+        def body(collective):
+            if tl is not None:
+                for _ in range(4):
+                    tl.pair("stamp_pair")
+            if in_graph and self._has_buffers and not collective(self.sync_buffers):
+                return None
+            if self.wflat is not None and self.keep_grads and update:
+                self.wflat.zero_()
+            sig = self._signal if getattr(static, "_index_is_live", False) else None
+            if sig is not None:
+                # the post that releases the NEXT batch's index build: where the model marks it (ops.signal_point:
+                # behind the EGNN edge kernel, when the chip stops being full), else at the head of the step
+                sig.armed, sig.at = True, self._signal_name
+                ops.SIGNAL = sig
+                if not (self.signal_in_model and self._signal_reached):
+                    sig.post()
+            try:
+                loss = self._loss_backward(static)
+            finally:
+                if sig is not None:
+                    ops.SIGNAL = None
+                    if sig.armed:       # (cannot happen after the probe; a step without its post would stall the next index build until the wait's timeout)
+                        sig.post()
+            if in_graph and not collective(self._captured_all_reduce):
+                return loss
+            if update and (in_graph or not multi):
+                self.opt.step()     # nothing the host must do between backward and update: one graph, one launch
+            return loss
+        g_bwd, loss = capture_graph(body)
         g_opt = None
         if update and multi and not in_graph:
             g_opt = torch.cuda.CUDAGraph()
@@ -846,7 +868,6 @@ class GraphedTrainStep(_Averaged):
         # autograd graphs of earlier eager passes that are only kept alive by reference cycles hold AccumulateGrad nodes bound
         # to the stream they ran on; a capture that meets one is invalidated (and capture_end of an invalidated capture
         # segfaults on ROCm 7.2): collect them first (a capture is rare and costs ~0.3 s anyway)
-        import gc
         gc.collect()
         # accum_steps > 1: a bucket first met in the middle of a group -- the warm-up passes below clear wflat and write
         # gradients of their own over what the group has summed so far: set it aside, put it back behind the capture
@@ -855,13 +876,7 @@ class GraphedTrainStep(_Averaged):
         side.wait_stream(torch.cuda.current_stream())
         snap = self._buffer_snapshot()
         from . import ops
-
-        class _Probe:       # which signal points does this model's step reach (ops.signal_point)?
-            armed = False
-
-            def __init__(self):
-                self.seen = set()
-        probe = _Probe()
+        probe = types.SimpleNamespace(armed=False, seen=set())     # which signal points does this model's step reach?
         with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture requires
             for _ in range(2):
                 ops.SIGNAL = probe
@@ -876,13 +891,30 @@ class GraphedTrainStep(_Averaged):
         self._signal_name = next((n for n in self.signal_at.split(",") if n in probe.seen), None)
         self._signal_reached = self._signal_name is not None
         self.scratch.freeze()          # its address is about to become part of a graph
-        prefetch = self._capture_index(static) if self._prefetch_on else None
+        prefetch = BucketPrefetch.capture(static, self._prefetch_stream, self._signal) if self._prefetch_on else None
+        if prefetch is not None:
+            self._prefetch_stream, self._signal, self.index_build_us = prefetch.stream, prefetch.signal, prefetch.index_build_us
         if held is not None:
             # the accumulate graph: the backward pass alone on every rank; the collective belongs to the update graph
-            g_bwd, _, loss = self._capture_pass(static, False, update=False)
+            g_bwd, g_opt, loss = self._capture_pass(static, False, update=False)
+            mode = "split" if multi else "none"
             self.gflat.copy_(held)      # (the scratch is empty already: the adding launch of every pass clears it)
-            return {"static": static, "bwd": g_bwd, "opt": None, "loss": loss, "mode": "split" if multi else "none",
-                    "prefetch": prefetch}
+        else:
+            g_bwd, g_opt, loss = self._settle_mode(lambda in_graph: self._capture_pass(static, in_graph),
+                                                   abandoned=lambda: self._buffer_restore(snap))
+            mode = self.collective_mode
+            if self.wflat is not None and not self.keep_grads:
+                self.wflat.zero_()       # what the captured update leaves behind after every replay: zeros to accumulate into
+                if self.scratch.buf is not None:
+                    self.scratch.buf.zero_()
+        return {"static": static, "bwd": g_bwd, "opt": g_opt, "loss": loss, "mode": mode, "prefetch": prefetch}
+
+    def _settle_mode(self, capture: Callable, abandoned: Callable = lambda: None):
+        """``capture(in_graph=True)``, with the gradient all-reduce inside the graph, where that is possible and every rank
+        can, else ``capture(False)``: returns what the capture that stays returned and sets ``collective_mode``.  The ranks
+        settle the form at their FIRST capture (``_agree_on_mode``): a refusal there takes every rank to "split", a refusal
+        later is an error.  ``abandoned()`` runs behind an in-graph capture that does not stay (it moved the model's buffers)."""
+        multi = self._multi()
         mode = "none"
         if multi:
             mode = "in_graph" if (self.graph_collective and dist.get_backend() in self.in_graph_backends
@@ -891,14 +923,14 @@ class GraphedTrainStep(_Averaged):
         cap = None
         if mode == "in_graph":
             try:
-                cap = self._capture_pass(static, True)
+                cap = capture(True)
             except CollectiveCaptureRefused as exc:    # the split form is always available -- if every rank takes it
                 if not first:
                     raise RuntimeError("GraphedTrainStep: the ranks agreed on the in-graph all-reduce at the first capture "
                                        f"and this rank can no longer capture it ({exc})") from exc
                 self.capture_error = str(exc)
                 torch.cuda.synchronize()
-                self._buffer_restore(snap)
+                abandoned()
                 mode = "split"
             if mode == "split":
                 # the abandoned pass's CUDAGraph sits in the exception's traceback (a reference cycle): destroy it NOW --
@@ -910,142 +942,25 @@ class GraphedTrainStep(_Averaged):
             if agreed != mode:         # this rank captured the collective, another one could not: drop the graph, follow
                 self.capture_error = "another rank could not capture the collective"
                 cap, mode = None, agreed
-                self._buffer_restore(snap)
+                abandoned()
                 gc.collect()
         if cap is None:
-            cap = self._capture_pass(static, False)
-        g_bwd, g_opt, loss = cap
+            cap = capture(False)
         self.collective_mode = mode
-        if self.wflat is not None and not self.keep_grads:
-            self.wflat.zero_()       # what the captured update leaves behind after every replay: zeros to accumulate into
-            if self.scratch.buf is not None:
-                self.scratch.buf.zero_()
-        return {"static": static, "bwd": g_bwd, "opt": g_opt, "loss": loss, "mode": mode, "prefetch": prefetch}
-
-    def _capture_index(self, static):
-        """Set up the index prefetch of one bucket, or return None when the model's index cannot be built ahead (no index
-        on the batch, or a neighbour search on coordinates other than the batch's own ``pos``).
-
-        ``staged``: a second packed copy of the static batch that a step's successor is written into; ``g_index``: a hipGraph
-        that builds the staged batch's HyperIndex (CSR sorts, kNN, transposed kNN CSR) -- replayed on ``stream`` beside the
-        running step; ``live``: a clone of that index, installed on the static batch, which is ALL the step graph reads;
-        ``dsts / srcs``: the tensor pairs (index tensors + the batch's flat buffer) that ONE batched copy at the head of
-        every step moves from staged to live (3 MB, ~4.4 us).  One step graph per bucket as before (two step graphs over two
-        sets of live buffers would save the copy and double the captures and the graphs' memory)."""
-        from .index import HyperIndex
-        ixw = getattr(static, "_hyper_index", None)
-        flat = getattr(static, "_flat", None)
-        if ixw is None or flat is None or not static.pos.is_cuda:
-            return None
-        want = (static.pos.data_ptr(), tuple(static.pos.shape), static.pos.dtype)
-        keys = list(ixw._knn.keys())
-        if any(ixw._knn_pos.get(k) != want for k in keys) or any(static.pos.shape[0] - 1 < k for k, m in keys if m == 1):
-            return None
-        rkeys = list(getattr(ixw, "_radius_args", {}).items())      # (r, k) -> (coordinates, RBF means, betas): ViSNet
-        if any(at != want for _, (at, _m, _b) in rkeys):
-            return None
-        staged = static.packed()
-        staged.num_real_graphs = getattr(static, "num_real_graphs", None)
-        from . import ops
-        if self._signal is None:
-            self._signal = ops.StepSignal(static.pos.device)
-        stream = getattr(self, "_prefetch_stream", None)
-        if stream is None:
-            stream = self._prefetch_stream = torch.cuda.Stream()
-
-        def build():
-            staged._hyper_index = None
-            ix = HyperIndex.from_batch(staged)
-            for k, m in keys:
-                ix.knn(staged.pos, k, m)
-            for (r, k), (_at, means, betas) in rkeys:
-                ix.radius(staged.pos, r, k, means, betas)
-            return ix
-        stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(stream):
-            build()                                  # (warm-up on the stream the graph will be replayed on)
-        torch.cuda.current_stream().wait_stream(stream)
-        g_index = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_index, capture_error_mode="thread_local"):
-            ix_staged = build()
-        # the index graph alone (reported by bench.py; a pure function of the staged batch)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            g_index.replay()
-            e0.record(stream)
-            for _ in range(3):
-                g_index.replay()
-            e1.record(stream)
-        e1.synchronize()
-        self.index_build_us = e0.elapsed_time(e1) * 1e3 / 3
-        live, dsts, srcs = ix_staged.live_clone(static)
-        static._hyper_index, static._index_is_live = live, True
-        as_words = lambda t: t.view(torch.float32) if t.dtype != torch.float32 else t
-        nf = flat.numel() // 4 * 4
-        dsts = [as_words(t).reshape(-1) for t in dsts] + [flat[:nf].view(torch.float32)]
-        srcs = [as_words(t).reshape(-1) for t in srcs] + [staged._flat[:nf].view(torch.float32)]
-        # (ops.StreamEvent: no system-scope fence -- a torch.cuda.Event recorded at the head of every step writes the L2 back and
-        # invalidates it; EQH_TORCH_EVENTS=1 restores those for A/B runs)
-        import os
-        light = not os.environ.get("EQH_TORCH_EVENTS")
-        free = ops.StreamEvent() if light else torch.cuda.Event()
-        free.record(torch.cuda.current_stream())
-        ready = ops.StreamEvent() if light else None
-        return {"staged": staged, "g_index": g_index, "ix_staged": ix_staged, "live": live, "dsts": dsts, "srcs": srcs,
-                "stream": stream, "free": free, "ready": None, "ready_ev": ready, "holds": None, "light": light}
-
-    def _capture_update_pass(self, in_graph: bool):
-        """One capture of the update graph (accum_steps > 1): ``opt.step()`` -- the sum-of-squares launch and the clip form with
-        ``clip_gnorm``, the EMA form with ``ema_decay`` -- behind the gradient all-reduce when ``in_graph``.  Raises
-        ``CollectiveCaptureRefused`` when, and only when, the captured collective call failed (as ``_capture_pass``)."""
-        g = torch.cuda.CUDAGraph()
-        refused = None
-        try:
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                if in_graph:
-                    try:
-                        self._captured_all_reduce()
-                    except RuntimeError as exc:
-                        refused = exc
-                if refused is None:
-                    self.opt.step()
-        except RuntimeError:
-            if refused is None:
-                raise
-        if refused is not None:
-            raise CollectiveCaptureRefused(f"{type(refused).__name__}: {refused}") from refused
-        return g
+        return cap
 
     def _capture_update(self):
-        """The update graph shared by all buckets, captured at the second close of a group (the first ran eagerly: every
-        launch of the update and the communicator exist).  The ranks settle ``collective_mode`` here as ``_capture`` does
-        for k = 1: "in_graph" only if every rank captured the collective, else the all-reduce stays in front of the graph."""
-        import gc
+        """The update graph shared by all buckets (accum_steps > 1), captured at the second close of a group (the first ran
+        eagerly: every launch of the update and the communicator exist): ``opt.step()`` in its ``clip_gnorm`` / ``ema_decay``
+        form, behind the gradient all-reduce where the ranks settle on "in_graph", else the all-reduce stays in front of it."""
         gc.collect()
-        multi = self._multi()
-        mode = "none"
-        if multi:
-            mode = "in_graph" if (self.graph_collective and dist.get_backend() in self.in_graph_backends) else "split"
-        g = None
-        if mode == "in_graph":
-            try:
-                g = self._capture_update_pass(True)
-            except CollectiveCaptureRefused as exc:
-                self.capture_error = str(exc)
-                torch.cuda.synchronize()
-                mode = "split"
-                gc.collect()        # (the abandoned graph is destroyed now, not inside the next capture)
-        if multi and not self._mode_agreed:
-            agreed = self._agree_on_mode(mode)
-            self._mode_agreed = True
-            if agreed != mode:
-                self.capture_error = "another rank could not capture the collective"
-                g, mode = None, agreed
-                gc.collect()
-        if g is None:
-            g = self._capture_update_pass(False)
-        self.collective_mode = mode
-        self._g_update = g
+
+        def update(in_graph):
+            def body(collective):
+                if not in_graph or collective(self._captured_all_reduce):
+                    self.opt.step()
+            return capture_graph(body)[0]
+        self._g_update = self._settle_mode(update)
 
     def _close_group(self):
         """accum_steps > 1: the one collective and the one update of a group, on the sum ``gflat`` holds (scaled
@@ -1063,14 +978,6 @@ class GraphedTrainStep(_Averaged):
             self._g_update.replay()
         self.micro = 0
         self.updates += 1
-
-    def flush(self):
-        """Close an open group early (the end of an epoch): the update runs on what the group holds, with the scale of a
-        full group.  Nothing when no group is open (always so for accum_steps = 1)."""
-        if self._averaging:
-            raise RuntimeError("GraphedTrainStep.flush(): inside averaged() pflat holds the average, not the live weights")
-        if self.micro:
-            self._close_group()
 
     @property
     def ema_flat(self) -> Optional[torch.Tensor]:
@@ -1106,10 +1013,8 @@ class GraphedTrainStep(_Averaged):
     def index_prefetch(self, on: bool):
         self._prefetch_on = bool(on)
         self.prefetch_policy = "on" if on else "off"
-        self._cal = None
-        if self._alt_slots is not None:
-            self._alt_slots = None
-            import gc
+        dropped, self.form_calibration = getattr(self.form_calibration, "aside", None) is not None, None
+        if dropped:
             gc.collect()
 
     @property
@@ -1118,116 +1023,26 @@ class GraphedTrainStep(_Averaged):
         bench.py -- run steps until this clears before their own warm-up)."""
         return self.prefetch_policy == "auto" and self.calibration is None
 
-    CAL_WARM, CAL_STEPS = 3, 12          # replays before a timed window, steps in it
-
-    def _cal_steps(self) -> int:
-        """Steps in a timed window: CAL_STEPS, rounded up to whole groups of ``accum_steps`` -- any run of whole groups holds
-        the same number of update launches, wherever in a group it starts, so both forms are timed over the same work."""
-        k = self.accum_steps
-        return (self.CAL_STEPS + k - 1) // k * k
-
     def _calibrate(self, key):
-        """Auto policy, called at the head of every graphed step until the decision: per form, one capture step, CAL_WARM
-        replays, then CAL_STEPS steps between two device synchronisations (wall clock: the two streams overlap, so no single
-        stream's events see a step).  A step of another bucket restarts the window."""
-        import gc
-        import time
-        c = self._cal
-        if c is None:
-            c = self._cal = {"form": "built_ahead", "key": key, "n": 0, "t": {}, "restarts": 0}
-        if key != c["key"]:
-            c["key"], c["n"] = key, 0
-            c["restarts"] += 1
-            if c["restarts"] > 16:          # buckets alternate too fast to time a window: keep the form that is running
-                self._decide(None)
-            return
-        c["n"] += 1
-        first_timed = 1 + self.CAL_WARM + 1
-        steps = self._cal_steps()
-        if c["n"] == first_timed:
-            torch.cuda.synchronize()
-            c["t0"] = time.perf_counter()
-        elif c["n"] == first_timed + steps:
-            torch.cuda.synchronize()
-            c["t"][c["form"]] = (time.perf_counter() - c["t0"]) / steps * 1e3
-            if c["form"] == "built_ahead":  # now the other form: every bucket is captured again, the graphs so far are kept aside
-                self._alt_slots, self.slots = self.slots, {}
-                self._prefetch_on = False
-                c["form"], c["n"] = "in_step", 1
-            else:
-                self._decide(c["t"])
-
-    def _decide(self, t):
-        import gc
-        ahead = t is not None and t["built_ahead"] < 0.99 * t["in_step"]
-        if t is None:
-            ahead = self._prefetch_on
-        elif ahead:                          # back to the graphs of the first window
-            self.slots, self._alt_slots = self._alt_slots, None
-            self._prefetch_on = True
-        self._alt_slots = None
-        gc.collect()                         # (dropped graphs are destroyed now, not inside a later capture)
-        self.calibration = {"built_ahead_ms": None if t is None else round(t["built_ahead"], 4),
-                            "in_step_ms": None if t is None else round(t["in_step"], 4),
-                            "steps_per_window": self._cal_steps(), "chosen": "built_ahead" if ahead else "in_step"}
-        self._cal = None
-
-    @staticmethod
-    def _token(data):
-        """Identity of a batch's CONTENTS: loaders hand the same device buffers out again with new molecules (and bump
-        ``_generation``, fit.BucketedLoader)."""
-        return (id(data), getattr(data, "_generation", 0))
-
-    def _stage(self, pf, data, after_signal=None):
-        """Write ``data`` into the bucket's staged batch and build its index there, on the prefetch stream: ordered behind
-        the head copy of the last step that read the staged buffers (``free``), not behind the step itself -- and, with
-        ``after_signal`` (the count the running step's signal node brings the counter to), held back until that step has
-        reached its signal point."""
-        st = pf["staged"]
-        with torch.cuda.stream(pf["stream"]):
-            if pf["light"]:
-                pf["free"].wait(pf["stream"])
-            else:
-                pf["stream"].wait_event(pf["free"])
-            if after_signal is not None:
-                self._signal.wait(after_signal)
-            lay = getattr(data, "_layout", None)
-            if lay is not None and lay == getattr(st, "_layout", None):
-                st._flat.copy_(data._flat, non_blocking=True)
-            else:
-                for f in data.__dataclass_fields__:
-                    v = getattr(data, f)
-                    if torch.is_tensor(v):
-                        getattr(st, f).copy_(v, non_blocking=True)
-            pf["g_index"].replay()
-            if pf["light"]:
-                ready = pf["ready_ev"]
-                ready.record(pf["stream"])
-            else:
-                ready = torch.cuda.Event()
-                ready.record(pf["stream"])
-        pf["ready"], pf["holds"] = ready, self._token(data)
-
-    def _refresh(self, pf):
-        """Head of a step: staged -> live (index tensors and the batch itself) in one launch on the step's stream."""
-        from . import ops
-        cur = torch.cuda.current_stream()
-        if pf["light"]:
-            pf["ready"].wait(cur)
-            ops.copy_many(pf["dsts"], pf["srcs"])
-            pf["free"].record(cur)
-        else:
-            cur.wait_event(pf["ready"])
-            ops.copy_many(pf["dsts"], pf["srcs"])
-            pf["free"] = torch.cuda.Event()
-            pf["free"].record(cur)
+        """Auto policy, at the head of every graphed step until the decision: carries out FormCalibration's answers on ``slots``."""
+        cal = self.form_calibration = self.form_calibration or FormCalibration(self.accum_steps)
+        act = cal.step(key)
+        if act == cal.SET_ASIDE:            # now the other form: every bucket is captured again
+            cal.aside, self.slots = self.slots, {}
+            self._prefetch_on = False
+        elif act is not None:
+            if act == cal.RESTORE:          # back to the graphs of the first window
+                self.slots = cal.aside
+                self._prefetch_on = True
+            cal.aside = None
+            self.calibration, self.form_calibration = cal.result, None
+            gc.collect()                    # (dropped graphs are destroyed now, not inside a later capture)
 
     def step(self, data, next_data=None) -> torch.Tensor:
         """One training step on ``data``.  ``next_data``: the batch of the NEXT call, if the caller has it (a loader with one
         batch of look-ahead, ``with_next``): its per-batch index is then built beside this step instead of at the head of
         the next one.  Numerically the two forms are the same step."""
-        if self._averaging:
-            raise RuntimeError("GraphedTrainStep.step(): inside averaged() pflat holds the average, not the live weights")
+        self._refuse_averaging("step()")
         if self.live is None:
             loss = self._bootstrap(data)
             if self.loss_readout:
@@ -1238,33 +1053,19 @@ class GraphedTrainStep(_Averaged):
             self._calibrate(key)
         slot = self.slots.get(key)
         if slot is None:
-            if hasattr(data, "packed"):
-                static = data.packed()       # one flat buffer: refreshed by ONE copy per step
-            else:
-                static = type(data)(**{f: (getattr(data, f).clone() if torch.is_tensor(getattr(data, f))
-                                           else getattr(data, f)) for f in data.__dataclass_fields__})
-            static.num_real_graphs = getattr(data, "num_real_graphs", None)
-            slot = self.slots[key] = self._capture(static)
-        st = slot["static"]
+            slot = self.slots[key] = self._capture(static_copy_of(data))
         pf = slot.get("prefetch")
         if pf is not None:
-            if pf["holds"] != self._token(data):
+            token = batch_token(data)
+            if pf.holds != token:
                 self.prefetch_misses += 1
-                pf["stream"].wait_stream(torch.cuda.current_stream())     # (data may have been produced on this stream)
-                self._stage(pf, data)
+                pf.stream.wait_stream(torch.cuda.current_stream())     # (data may have been produced on this stream)
+                pf.stage(data, token)
             else:
                 self.prefetch_hits += 1
-            self._refresh(pf)
-            pf["holds"] = None
+            pf.refresh()
         else:
-            lay = getattr(data, "_layout", None)
-            if lay is not None and lay == getattr(st, "_layout", None):
-                st._flat.copy_(data._flat, non_blocking=True)
-            else:
-                for f in data.__dataclass_fields__:
-                    v = getattr(data, f)
-                    if torch.is_tensor(v):
-                        getattr(st, f).copy_(v, non_blocking=True)
+            copy_into_static(slot["static"], data)
         self.opt.sync_lr()
         if self._has_buffers and slot["mode"] != "in_graph":
             self.sync_buffers()
@@ -1288,7 +1089,7 @@ class GraphedTrainStep(_Averaged):
             nslot = self.slots.get(self._key(next_data))
             npf = nslot.get("prefetch") if nslot is not None else None
             if npf is not None:
-                self._stage(npf, next_data, after_signal=self._signal.posted if pf is not None else None)
+                npf.stage(next_data, batch_token(next_data), after_signal=self._signal.posted if pf is not None else None)
         return slot["loss"].detach()
 
 
@@ -1342,21 +1143,7 @@ class GraphedEvalStep:
             self.addresses = addr
         slot = self.slots.get(key)
         if slot is None:
-            if hasattr(data, "packed"):
-                static = data.packed()
-            else:
-                static = type(data)(**{f: (getattr(data, f).clone() if torch.is_tensor(getattr(data, f))
-                                           else getattr(data, f)) for f in data.__dataclass_fields__})
-            static.num_real_graphs = getattr(data, "num_real_graphs", None)
-            slot = self.slots[key] = self._capture(static)
-        st = slot["static"]
-        lay = getattr(data, "_layout", None)
-        if lay is not None and lay == getattr(st, "_layout", None):
-            st._flat.copy_(data._flat, non_blocking=True)
-        else:
-            for f in data.__dataclass_fields__:
-                v = getattr(data, f)
-                if torch.is_tensor(v):
-                    getattr(st, f).copy_(v, non_blocking=True)
+            slot = self.slots[key] = self._capture(static_copy_of(data))
+        copy_into_static(slot["static"], data)
         slot["graph"].replay()
         return slot["out"]

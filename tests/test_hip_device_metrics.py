@@ -158,7 +158,7 @@ def test_graphed_step_keeps_the_sum_of_its_losses_on_the_device(mols):
     assert count == 20.0 and total == want and want > 0.0
     assert len(tr_on.slots) == 2                                          # both buckets captured
     if tr_on.prefetch_policy == "auto":       # 17 graphed steps of bucket A: the first window timed, the second form captured
-        assert tr_on.calibrating and tr_on._alt_slots and tr_on._cal["form"] == "in_step"
+        assert tr_on.calibrating and tr_on.form_calibration.aside and tr_on.form_calibration.form == "in_step"
     assert tr_off.loss_sum is None and not tr_off.loss_readout
     for (k, p), q in zip(on.state_dict().items(), off.state_dict().values()):
         assert torch.equal(p, q), k

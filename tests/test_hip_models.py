@@ -814,6 +814,50 @@ def test_index_built_ahead_on_the_side_stream_gives_the_same_steps(method):
             assert torch.equal(v, finals["in_step"][0][k]), (label, k)
 
 
+def test_index_built_ahead_under_torch_events_gives_the_same_steps(monkeypatch):
+    """EQH_TORCH_EVENTS=1: the prefetch orders its two streams with ``torch.cuda.Event``s (prefetch.TorchEvent, a fresh event
+    per record) instead of ``ops.StreamEvent``.  Same setup as above for egnn_equihnns: the trainer that finds every index
+    built ahead equals the one that builds it in the step graph bit for bit, with the same hits and misses."""
+    import copy
+
+    from common import zero_dropouts
+    from equihgnn_amd.batch import bucket_sizes, pad_batch, synth_batch
+    from equihgnn_amd.prefetch import TorchEvent
+    from equihgnn_amd.registry import default_args
+    from equihgnn_amd.trainer import GraphedTrainStep, with_next
+    monkeypatch.setenv("EQH_TORCH_EVENTS", "1")
+    args = default_args(method="egnn_equihnns", MLP_hidden=64, output_hidden=32)
+    m0 = _models()["egnn_equihnns"](1, args)
+    fill_state_dict(m0, 4)
+    zero_dropouts(m0)
+    m0.to(DEV)
+    raw = [synth_batch(8, 1300 + i) for i in range(4)]
+    ext = [bucket_sizes(b.num_nodes, b.num_hyperedges, b.nnz, 64) for b in raw]
+    tgt = tuple(max(e[i] for e in ext) for i in range(3))
+    padded = [pad_batch(b, *tgt).packed().to(DEV) for b in raw]
+    for b in padded:
+        b.num_real_graphs = 8
+    order = [padded[i % 4] for i in range(7)]
+    finals = {}
+    for label in ("in_step", "ahead"):
+        m = copy.deepcopy(m0)
+        tr = GraphedTrainStep(m, lr=1e-3)
+        tr.index_prefetch = label == "ahead"
+        losses = [float(tr.step(b, nxt if label == "ahead" else None)) for b, nxt in with_next(order)]
+        torch.cuda.synchronize()
+        pf = next(iter(tr.slots.values()))["prefetch"]
+        if label == "ahead":
+            assert isinstance(pf.free, TorchEvent) and isinstance(pf.ready, TorchEvent)
+            assert tr.prefetch_hits == 5 and tr.prefetch_misses == 1
+        else:
+            assert pf is None
+        finals[label] = ({k: v.detach().cpu().clone() for k, v in m.state_dict().items()}, losses)
+        tr.close()
+    assert finals["ahead"][1] == finals["in_step"][1], (finals["ahead"][1], finals["in_step"][1])
+    for k, v in finals["ahead"][0].items():
+        assert torch.equal(v, finals["in_step"][0][k]), k
+
+
 @pytest.mark.gpu
 def test_the_trainer_times_both_forms_of_the_index_build_and_keeps_one_without_changing_the_steps():
     """Auto policy (GraphedTrainStep._calibrate): a window of steps with the next index built ahead, a window with it built in
@@ -851,7 +895,7 @@ def test_the_trainer_times_both_forms_of_the_index_build_and_keeps_one_without_c
         if label == "auto":
             assert not tr.calibrating and tr.calibration["chosen"] in ("built_ahead", "in_step")
             assert tr.calibration["built_ahead_ms"] > 0 and tr.calibration["in_step_ms"] > 0
-            assert tr._alt_slots is None
+            assert tr.form_calibration is None          # (with it, whatever was set aside)
             slot = next(iter(tr.slots.values()))
             assert (slot["prefetch"] is not None) == (tr.calibration["chosen"] == "built_ahead") == tr.index_prefetch
         finals[label] = ({k: v.detach().cpu().clone() for k, v in m.state_dict().items()}, losses)
