@@ -30,6 +30,7 @@
 // (v_permlane16/32_swap) with ONE pass through LDS instead of three staged tiles and seven barriers.
 #include <cstdlib>
 #include <initializer_list>
+#include <type_traits>
 
 #include "act.h"
 #include "common.h"
@@ -1695,25 +1696,36 @@ inline bool pn_mode(int32_t products, int32_t planes, int& np, int& ip) {
     return ip >= pn_planes(np) && ip <= 3;
 }
 
-// X(NW, NP) for the (wavefronts, products) of a launch
-#define PN_BY_MODE(X)                  \
-    do {                               \
-        if (np == 6) {                 \
-            if (nw == 8) X(8, 6);      \
-            else X(4, 6);              \
-        } else if (np == 3) X(8, 3);   \
-        else X(8, 1);                  \
-    } while (0)
+// ---- the (width, wavefronts, products) of a launch -> template arguments ------------------------------------------------------
+// pn_for_shape is the ONLY list of built shapes: the (wavefronts, products) of pn_waves / pn_mode, (8, 6), (4, 6), (8, 3), (8, 1)
+// -- four wavefronts exist at six products only -- x the widths of pn_width_ok.  f is a generic lambda with one
+// hipLaunchKernelGGL in it, called as f(s) with s.C, s.NW, s.NP static; the caller has validated the triple.  (The order of the
+// list, mode then width, is the order in which the kernels are instantiated: the compiler's output depends on it.)
+template <int C_, int NW_, int NP_> struct PnBuilt { static constexpr int C = C_, NW = NW_, NP = NP_; };
+template <int NW, int NP, class F> void pn_for_width(int C, F&& f) {
+    if (C == 256) f(PnBuilt<256, NW, NP>{});
+    else if (C == 128) f(PnBuilt<128, NW, NP>{});
+    else f(PnBuilt<64, NW, NP>{});
+}
+template <class F> void pn_for_shape(int C, int nw, int np, F&& f) {
+    if (np == 6) {
+        if (nw == 8) pn_for_width<8, 6>(C, f);
+        else pn_for_width<4, 6>(C, f);
+    } else if (np == 3) pn_for_width<8, 3>(C, f);
+    else pn_for_width<8, 1>(C, f);
+}
+// n in 1..3 (products of one launch: hg_panel_multi, hg_panel_sum) -> f(std::integral_constant<int, n>)
+template <class F> void pn_for_count(int n, F&& f) {
+    if (n == 1) f(std::integral_constant<int, 1>{});
+    else if (n == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
+}
 
 // Whether hg_conv_stack_drop runs F3 CHAINED with the next application's F1 (k_conv_f3<.., true, 2>) at this shape, or as F3
 // without tail plus a lone F1 launch.  The rule: chained unless that form spills more than its p = 0 twin (DESIGN 4.8 has the
 // table this was read from): at C = 256 with 8 wavefronts and 6 products the chained form needs 120 bytes of scratch per lane
 // where k_conv_f3<256, 8, 6, false> has 68, so that shape runs unchained and its chained form is not built.
 constexpr bool stack_f3_chained(int C, int nw, int np) { return !(C == 256 && nw == 8 && np == 6); }
-template <int C, int NW, int NP>
-void launch_stack_f3_chained(dim3 grid, dim3 block, hipStream_t stream, const ConvStackDropArgs& as) {
-    if constexpr (stack_f3_chained(C, NW, NP)) hipLaunchKernelGGL((k_conv_f3<C, NW, NP, true, 2>), grid, block, 0, stream, as);
-}
 
 // hg_conv_panel (drop == NULL), hg_conv_panel_drop (F3 / B3) and hg_conv_stack_drop (sd != NULL: F1 / F3 / B1 / B3), each
 // validated by its entry: one validation, one dispatch
@@ -1770,32 +1782,17 @@ int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* dro
     auto f1_ok = [&](const void* wa, const void* wb, const void* b, const void* g, const void* be, const void* o0, const void* o1, const void* o2) {
         return need({wa, wb, b, g, be, o0, o1, o2});
     };
-    // (A: the argument block; the trailing arguments: further template arguments of K -- `true` for a DROP form)
-#define PN_LAUNCH_W(K, A, NW_, NP_, ...)                                                                  \
-    do {                                                                                                  \
-        if (C == 256) hipLaunchKernelGGL((K<256, NW_, NP_, ##__VA_ARGS__>), grid, block, 0, stream, A);   \
-        else if (C == 128) hipLaunchKernelGGL((K<128, NW_, NP_, ##__VA_ARGS__>), grid, block, 0, stream, A); \
-        else hipLaunchKernelGGL((K<64, NW_, NP_, ##__VA_ARGS__>), grid, block, 0, stream, A);             \
-    } while (0)
-#define PN_LAUNCH_A(K, A, ...)                                                                            \
-    do {                                                                                                  \
-        if (np == 6) {                                                                                    \
-            if (nw == 8) PN_LAUNCH_W(K, A, 8, 6, ##__VA_ARGS__);                                          \
-            else PN_LAUNCH_W(K, A, 4, 6, ##__VA_ARGS__);                                                  \
-        } else if (np == 3) PN_LAUNCH_W(K, A, 8, 3, ##__VA_ARGS__);                                       \
-        else PN_LAUNCH_W(K, A, 8, 1, ##__VA_ARGS__);                                                      \
-        EQH_CHECK_LAUNCH();                                                                               \
-    } while (0)
-#define PN_LAUNCH(K) PN_LAUNCH_A(K, a)
     switch (stage) {
         case HG_CONV_F1:
             if (!q->in0 || !f1_ok(q->w0, q->w1, q->b0, q->g0, q->be0, q->out0, q->out1, q->out2)) return EQH_ERR_ARG;
-            if (sd) PN_LAUNCH_A(k_conv_f1, as, true);
-            else PN_LAUNCH(k_conv_f1);
+            if (sd) pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_f1<s.C, s.NW, s.NP, true>), grid, block, 0, stream, as); });
+            else pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_f1<s.C, s.NW, s.NP>), grid, block, 0, stream, a); });
+            EQH_CHECK_LAUNCH();
             return EQH_OK;
         case HG_CONV_F2:
             if (!need({q->in0, q->rowptr, q->col, q->w0, q->bias_out, q->out0, q->out1})) return EQH_ERR_ARG;
-            PN_LAUNCH(k_conv_f2);
+            pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_f2<s.C, s.NW, s.NP>), grid, block, 0, stream, a); });
+            EQH_CHECK_LAUNCH();
             return EQH_OK;
         case HG_CONV_F3:
             if (!need({q->in0, q->in1, q->w0, q->b0, q->g0, q->be0, q->w1, q->bias_out, q->out0, q->out1, q->out2})) return EQH_ERR_ARG;
@@ -1804,34 +1801,32 @@ int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* dro
             if (sd) {
                 // (unchained: F3 without tail, then a lone F1 that reads the stored Xn and takes its operands from the tail's slots)
                 if (!q->tail) {
-                    PN_LAUNCH_A(k_conv_f3, as, true, 1);
+                    pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_f3<s.C, s.NW, s.NP, true, 1>), grid, block, 0, stream, as); });
                 } else if (stack_f3_chained(C, nw, np)) {
-#define PN_F3_CHAINED(NW_, NP_)                                                                  \
-    do {                                                                                         \
-        if (C == 256) launch_stack_f3_chained<256, NW_, NP_>(grid, block, stream, as);            \
-        else if (C == 128) launch_stack_f3_chained<128, NW_, NP_>(grid, block, stream, as);       \
-        else launch_stack_f3_chained<64, NW_, NP_>(grid, block, stream, as);                      \
-    } while (0)
-                    PN_BY_MODE(PN_F3_CHAINED);
-                    EQH_CHECK_LAUNCH();
-#undef PN_F3_CHAINED
+                    pn_for_shape(C, nw, np, [&](auto s) {
+                        if constexpr (stack_f3_chained(s.C, s.NW, s.NP))
+                            hipLaunchKernelGGL((k_conv_f3<s.C, s.NW, s.NP, true, 2>), grid, block, 0, stream, as);
+                    });
                 } else {
                     as.tail = 0;
-                    PN_LAUNCH_A(k_conv_f3, as, true, 1);
+                    pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_f3<s.C, s.NW, s.NP, true, 1>), grid, block, 0, stream, as); });
+                    EQH_CHECK_LAUNCH();
                     ConvStackDropArgs f1 = as;
                     f1.in0 = q->out2; f1.ld0 = C;
                     f1.w0 = as.w2; f1.w1 = as.w3; f1.b0 = q->b1; f1.g0 = q->g1; f1.be0 = q->be1;
                     f1.out0 = q->out3; f1.out1 = q->out4; f1.out2 = q->out5;
-                    PN_LAUNCH_A(k_conv_f1, f1, true);
+                    pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_f1<s.C, s.NW, s.NP, true>), grid, block, 0, stream, f1); });
                 }
-            } else if (drop) PN_LAUNCH_A(k_conv_f3, ad, true);
-            else PN_LAUNCH(k_conv_f3);
+            } else if (drop) pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_f3<s.C, s.NW, s.NP, true>), grid, block, 0, stream, ad); });
+            else pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_f3<s.C, s.NW, s.NP>), grid, block, 0, stream, a); });
+            EQH_CHECK_LAUNCH();
             return EQH_OK;
         case HG_CONV_B3: {
             if (!need({q->in0, q->w0, q->w1, q->in2, q->b0, q->g0, q->out1, q->out2, q->slab, q->dbias, q->dgamma, q->dbeta})) return EQH_ERR_ARG;
             if (q->in1 && !q->out0) return EQH_ERR_ARG;
-            if (drop || sd) PN_LAUNCH_A(k_conv_b3, ad, true);
-            else PN_LAUNCH(k_conv_b3);
+            if (drop || sd) pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_b3<s.C, s.NW, s.NP, true>), grid, block, 0, stream, ad); });
+            else pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_b3<s.C, s.NW, s.NP>), grid, block, 0, stream, a); });
+            EQH_CHECK_LAUNCH();
             return eqh_reduce_slabs3_async(q->slab, blocks, 3 * (int64_t)C, q->dbias, q->dgamma, q->dbeta, C, C, q->accumulate, stream);
         }
         case HG_CONV_B1: {
@@ -1842,8 +1837,9 @@ int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* dro
                                   q->dgamma2, q->dbeta2}))
                 return EQH_ERR_ARG;
             if (q->tail && q->in3 && !q->out2) return EQH_ERR_ARG;
-            if (sd) PN_LAUNCH_A(k_conv_b1, as, true);
-            else PN_LAUNCH(k_conv_b1);
+            if (sd) pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_b1<s.C, s.NW, s.NP, true>), grid, block, 0, stream, as); });
+            else pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_conv_b1<s.C, s.NW, s.NP>), grid, block, 0, stream, a); });
+            EQH_CHECK_LAUNCH();
             int rc = eqh_reduce_slabs3_async(q->slab, blocks, 3 * (int64_t)C, q->dbias, q->dgamma, q->dbeta, C, C, q->accumulate, stream);
             if (rc || !q->tail) return rc;
             return eqh_reduce_slabs3_async(q->slab2, blocks, 3 * (int64_t)C, q->dbias2, q->dgamma2, q->dbeta2, C, C, q->accumulate, stream);
@@ -1851,21 +1847,20 @@ int conv_panel_launch(int32_t stage, const HgConvPanel* q, const HgConvDrop* dro
         case HG_EGNN_NODE_F:
             if (!need({q->in0, q->in1, q->w0, q->w1, q->w2, q->b0, q->bias_out, q->out0, q->out1, q->out2, q->out3})) return EQH_ERR_ARG;
             if (q->g0 ? !q->be0 : !q->in2) return EQH_ERR_ARG;      // LayerNorm of in0 inside (g0, be0) -- or normed rows + the residual in2
-            PN_LAUNCH(k_node_f);
+            pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_node_f<s.C, s.NW, s.NP>), grid, block, 0, stream, a); });
+            EQH_CHECK_LAUNCH();
             return EQH_OK;
         case HG_EGNN_NODE_B:
             if (!need({q->in0, q->in1, q->w0, q->w1, q->w2, q->out0, q->out1})) return EQH_ERR_ARG;
             if (q->g0 && !need({q->in3, q->out2, q->slab, q->dbias, q->dgamma, q->dbeta})) return EQH_ERR_ARG;
-            PN_LAUNCH(k_node_b);
+            pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_node_b<s.C, s.NW, s.NP>), grid, block, 0, stream, a); });
+            EQH_CHECK_LAUNCH();
             if (!q->g0) return EQH_OK;
             // (dbias: a [C] scratch row -- a plain LayerNorm has no bias in front of it; the slab's first third is zeros)
             return eqh_reduce_slabs3_async(q->slab, blocks, 3 * (int64_t)C, q->dbias, q->dgamma, q->dbeta, C, C, q->accumulate, stream);
         default:
             return EQH_ERR_ARG;
     }
-#undef PN_LAUNCH
-#undef PN_LAUNCH_A
-#undef PN_LAUNCH_W
 }
 
 }  // namespace
@@ -1999,22 +1994,10 @@ extern "C" int hg_panel_sum(const HgPanelSum* q, void* stream_) {
     const int nw = pn_waves(np);
     const dim3 grid((unsigned)((q->rows + PN_ROWS - 1) / PN_ROWS)), block(64 * nw);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define PN_SUM_C(NW_, NP_, NG_)                                                                                \
-    do {                                                                                                       \
-        if (C == 256) hipLaunchKernelGGL((k_panel_sum<256, NW_, NG_, NP_>), grid, block, 0, stream, p);        \
-        else if (C == 128) hipLaunchKernelGGL((k_panel_sum<128, NW_, NG_, NP_>), grid, block, 0, stream, p);   \
-        else hipLaunchKernelGGL((k_panel_sum<64, NW_, NG_, NP_>), grid, block, 0, stream, p);                  \
-    } while (0)
-#define PN_SUM1(NW_, NP_) PN_SUM_C(NW_, NP_, 1)
-#define PN_SUM2(NW_, NP_) PN_SUM_C(NW_, NP_, 2)
-#define PN_SUM3(NW_, NP_) PN_SUM_C(NW_, NP_, 3)
-    if (q->n == 1) PN_BY_MODE(PN_SUM1);
-    else if (q->n == 2) PN_BY_MODE(PN_SUM2);
-    else PN_BY_MODE(PN_SUM3);
-#undef PN_SUM1
-#undef PN_SUM2
-#undef PN_SUM3
-#undef PN_SUM_C
+    pn_for_count(q->n, [&](auto n) {
+        constexpr int NG = decltype(n)::value;
+        pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_panel_sum<s.C, s.NW, NG, s.NP>), grid, block, 0, stream, p); });
+    });
     EQH_CHECK_LAUNCH();
     return EQH_OK;
 }
@@ -2040,22 +2023,10 @@ extern "C" int hg_panel_multi(const HgPanelMulti* q, void* stream_) {
     const int nw = pn_waves(np);
     const dim3 grid((unsigned)((q->rows + PN_ROWS - 1) / PN_ROWS)), block(64 * nw);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define PN_MULTI_C(NW_, NP_, NG_)                                                                              \
-    do {                                                                                                       \
-        if (C == 256) hipLaunchKernelGGL((k_panel_multi<256, NW_, NG_, NP_>), grid, block, 0, stream, p);      \
-        else if (C == 128) hipLaunchKernelGGL((k_panel_multi<128, NW_, NG_, NP_>), grid, block, 0, stream, p); \
-        else hipLaunchKernelGGL((k_panel_multi<64, NW_, NG_, NP_>), grid, block, 0, stream, p);                \
-    } while (0)
-#define PN_MULTI1(NW_, NP_) PN_MULTI_C(NW_, NP_, 1)
-#define PN_MULTI2(NW_, NP_) PN_MULTI_C(NW_, NP_, 2)
-#define PN_MULTI3(NW_, NP_) PN_MULTI_C(NW_, NP_, 3)
-    if (q->n == 1) PN_BY_MODE(PN_MULTI1);
-    else if (q->n == 2) PN_BY_MODE(PN_MULTI2);
-    else PN_BY_MODE(PN_MULTI3);
-#undef PN_MULTI1
-#undef PN_MULTI2
-#undef PN_MULTI3
-#undef PN_MULTI_C
+    pn_for_count(q->n, [&](auto n) {
+        constexpr int NG = decltype(n)::value;
+        pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_panel_multi<s.C, s.NW, NG, s.NP>), grid, block, 0, stream, p); });
+    });
     EQH_CHECK_LAUNCH();
     return EQH_OK;
 }
@@ -2170,14 +2141,7 @@ extern "C" int hg_panel_gemm_f32_p(const float* a, int64_t lda, int64_t rows, in
         EQH_CHECK_LAUNCH();
         return EQH_OK;
     }
-#define PN_PLAIN(NW_, NP_)                                                                                  \
-    do {                                                                                                    \
-        if (C == 256) hipLaunchKernelGGL((k_panel_plain<256, NW_, NP_>), grid, block, 0, stream, p);       \
-        else if (C == 128) hipLaunchKernelGGL((k_panel_plain<128, NW_, NP_>), grid, block, 0, stream, p);  \
-        else hipLaunchKernelGGL((k_panel_plain<64, NW_, NP_>), grid, block, 0, stream, p);                 \
-    } while (0)
-    PN_BY_MODE(PN_PLAIN);
-#undef PN_PLAIN
+    pn_for_shape(C, nw, np, [&](auto s) { hipLaunchKernelGGL((k_panel_plain<s.C, s.NW, s.NP>), grid, block, 0, stream, p); });
     EQH_CHECK_LAUNCH();
     return EQH_OK;
 }

@@ -35,7 +35,8 @@ bn_rows.hip:226 bn_check              R < 2^31                            MHNN B
 segment_reduce.hip:118                rows < 2^31 - 1                     aggregations                                   (a)
 rowgemm.hip:686                       rows < 2^31 - 1                     Equiformer radial products                     (a)
 incidence.hip:737                     rows < 2^31 - 1                     MHNN incidence gathers                         (a)
-panel.hip:1555,1714,1751,1841,1868    rows < 2^31 - 64                    MHNN / EGNN row panels                         (a)
+panel.hip                             rows < 2^31 - 64                    MHNN / EGNN row panels                         (a)
+  (conv_panel_launch, hg_panel_sum, hg_panel_multi, hg_panel_stream_gemm_f32_p, hg_panel_gemm_f32_p)
 gnn2d.hip:208                         N < 2^31 - 1                        GNN_2D message passing                         (a)
 ====================================  ==================================  =============================================  ====
 

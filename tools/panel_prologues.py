@@ -33,7 +33,7 @@ def measure(method="egnn_equihnns", batch=256, flavour="qm9", C=256, dev=None, v
     so = _build.STAMPS_LIB
     if not os.path.exists(so):
         so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libpanel_stamps.so")
-        _build.compile_variant(["panel.hip", "api.hip"], ["PN_STAMPS"], so)
+        _build.compile_variant(_build.PANEL_SOURCES, ["PN_STAMPS"], so)
     L = hip.load(so, partial=True)
     dev = torch.device("cuda:0") if dev is None else dev
     host = synth_batch(batch, 2000, flavour)

@@ -19,7 +19,7 @@ def main():
     rows = int(sys.argv[1]) if len(sys.argv) > 1 else 4864
     C = 256
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libpanel_stamps.so")
-    build.compile_variant(["panel.hip", "api.hip"], ["PN_STAMPS", *os.environ.get("PN_DEFS", "").split()], so)
+    build.compile_variant(build.PANEL_SOURCES, ["PN_STAMPS", *os.environ.get("PN_DEFS", "").split()], so)
     L = hip.load(so, partial=True)
     dev = "cuda:0"
     g = torch.Generator(device=dev).manual_seed(0)

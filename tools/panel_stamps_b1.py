@@ -19,7 +19,7 @@ from equihgnn_amd.index import HyperIndex
 def main():
     C = 256
     so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libpanel_stamps.so")
-    build.compile_variant(["panel.hip", "api.hip"], ["PN_STAMPS"], so)
+    build.compile_variant(build.PANEL_SOURCES, ["PN_STAMPS"], so)
     L = hip.load(so, partial=True)
     dev = torch.device("cuda:0")
     host = synth_batch(256, 2000, "qm9")
